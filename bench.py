@@ -2,7 +2,7 @@
 """Headline benchmark: epochs/sec of IGN 3-class training on synthetic CHISCO-shaped EEG
 (B=256 per GPU, C=122, T=1000; N_train=8192 samples per epoch) -- BASELINE.json's metric.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1: one rank per GPU over RCCL.  Either the caller starts the ranks (`python -m torch.distributed.run --nproc-per-node N
 bench.py --gpus N ...`: WORLD_SIZE / RANK / LOCAL_RANK come from the environment) or, when WORLD_SIZE is not set, this
@@ -355,6 +355,52 @@ class Bench:
         return dt, last
 
 
+DUMP_BUDGET_BYTES = 60 << 20        # array data; with the .npy headers the files stay under 64 MB
+
+
+def dump_outputs(b, last, out_dir, budget=DUMP_BUDGET_BYTES):
+    """`--dump-outputs DIR`: what the timed path handed its caller after the LAST timed step, one DIR/<name>.npy each --
+    `loss` (that step's loss), `param.<name>` / `buffer.<name>` (the model's floating-point state after its Adam update) and
+    `adam.exp_avg` / `adam.exp_avg_sq` (the flat optimizer moments, which carry the gradients).  float64 stays float64,
+    everything else is written as float32.  Over `budget` bytes of data, every array longer than a common cap is replaced by
+    the same fixed sample of its flattened elements (sorted indices drawn from a generator seeded by the array's length),
+    the cap being the largest that fits.  DIR holds nothing but the .npy files; the summary returned goes into the result
+    line (`dump_outputs`: directory, array count, bytes, the names of the sampled arrays)."""
+    import numpy as np
+    if last.is_cuda:
+        torch.cuda.synchronize()
+    arrays = {"loss": last}
+    arrays.update({f"param.{n}": p for n, p in b.model.named_parameters()})
+    arrays.update({f"buffer.{n}": t for n, t in b.model.named_buffers() if t.is_floating_point()})
+    arrays.update({"adam.exp_avg": b.opt.exp_avg, "adam.exp_avg_sq": b.opt.exp_avg_sq})
+    arrays = {k: v.detach().cpu().numpy().astype(np.float64 if v.dtype == torch.float64 else np.float32)
+              for k, v in arrays.items()}
+    sizes = sorted(a.size for a in arrays.values())
+    cap = sizes[-1]
+    if sum(a.nbytes for a in arrays.values()) > budget:
+        # largest per-array element cap with sum(min(size, cap) * itemsize) <= budget (all float32 unless float64 appears)
+        item = max(a.itemsize for a in arrays.values())
+        lo, hi = 1, sizes[-1]
+        while lo < hi:
+            mid = (lo + hi + 1) // 2
+            if sum(min(s, mid) for s in sizes) * item <= budget:
+                lo = mid
+            else:
+                hi = mid - 1
+        cap = lo
+    os.makedirs(out_dir, exist_ok=True)
+    sampled, nbytes = [], 0
+    for name, a in arrays.items():
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(a.size).choice(a.size, cap, replace=False))
+            a = a.reshape(-1)[idx]
+            sampled.append(name)
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        nbytes += a.nbytes
+    log(f"wrote {len(arrays)} arrays ({len(sampled)} sampled) to {out_dir}")
+    return {"dir": out_dir, "arrays": len(arrays), "bytes": nbytes, "sampled": sampled}
+
+
 def count_launches(step_fn, n=2):
     """GPU kernel launches of one step, counted by torch.profiler over `n` steps (None if the profiler is unavailable)."""
     try:
@@ -535,7 +581,13 @@ def main():
     ap.add_argument("--planted", action="store_true",
                     help="SURVEY 8(d)'s learnable synthetic variant (class-specific sine bursts planted in the noise): shows the "
                          "training loss falling at the full benchmark size; reported in config.loss_curve, never the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (loss, parameters and buffers after "
+                         "its Adam update, Adam moments) as DIR/<name>.npy, float32 / float64, at most 64 MB in all (rank 0); "
+                         "the inputs are seeded, so two builds run with the same arguments can be compared array by array")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args.gpus, sys.argv[1:])           # nothing above has touched the GPU
@@ -602,6 +654,9 @@ def main():
     fwd_ms, fwd_n = _lib.timing_read("shp_fwd")
     bwd_ms, bwd_n = _lib.timing_read("shp_bwd")
     ar_ms = sum(e0.elapsed_time(e1) for e0, e1 in b.ar_events) / max(1, len(b.ar_events)) if b.ar_events else 0.0
+    dumped = None
+    if args.dump_outputs and rank == 0:      # before the passes below step the same model further
+        dumped = dump_outputs(b, last, args.dump_outputs)
 
     if args.config != "ign":
         res_b = baseline_result(b, _lib, args.steps, dt, last, args.cpu_sample)
@@ -660,6 +715,8 @@ def main():
             "dtype": "f32" if not amp else "bf16 (autocast: GEMM operands bf16, fp32 accumulate; shapelet path and softmax fp32)",
             "data": "synthetic",
         }
+        if dumped is not None:
+            res["dump_outputs"] = dumped
         if amp:
             res["metric"] += " [reference default precision: bf16 autocast]"
         if args.config == "ign" and args.dnn != "FCN":

@@ -37,6 +37,72 @@ def test_explicit_world_size_mismatch_is_refused():
     assert r.returncode != 0 and "WORLD_SIZE=4" in r.stderr
 
 
+def test_steps_below_one_is_refused():
+    r = _run({}, "--gpus", "1", "--steps", "0")
+    assert r.returncode == 2 and "--steps must be >= 1" in r.stderr and not r.stdout.strip()
+
+
+def test_dump_outputs_writes_every_array_and_samples_to_the_budget(tmp_path):
+    """bench.dump_outputs on a small CPU stand-in of the Bench object: loss, every parameter, the floating-point buffers and
+    both Adam moments as float32 .npy files; over the budget, the long arrays become the same fixed sample on every call."""
+    import numpy as np
+    import torch
+    from types import SimpleNamespace
+    import bench
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(300, 200), torch.nn.BatchNorm1d(200), torch.nn.Linear(200, 3))
+    n = sum(p.numel() for p in model.parameters())
+    b = SimpleNamespace(model=model, opt=SimpleNamespace(exp_avg=torch.randn(n), exp_avg_sq=torch.rand(n)))
+    loss = torch.tensor(1.25)
+    want = {"loss": loss, "adam.exp_avg": b.opt.exp_avg, "adam.exp_avg_sq": b.opt.exp_avg_sq,
+            "buffer.1.running_mean": model[1].running_mean, "buffer.1.running_var": model[1].running_var,
+            **{f"param.{k}": p for k, p in model.named_parameters()}}
+
+    full = bench.dump_outputs(b, loss, str(tmp_path / "full"))
+    assert sorted(os.listdir(tmp_path / "full")) == sorted(f"{k}.npy" for k in want)
+    assert full["arrays"] == len(want) and full["sampled"] == [] and full["bytes"] == 4 * sum(v.numel() for v in want.values())
+    for k, v in want.items():
+        a = np.load(tmp_path / "full" / f"{k}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, v.detach().numpy()), k
+
+    budget = 100_000
+    small = [bench.dump_outputs(b, loss, str(tmp_path / d), budget=budget) for d in ("a", "b")]
+    assert small[0] == dict(small[1], dir=small[0]["dir"]) and small[0]["bytes"] <= budget
+    assert {"adam.exp_avg", "adam.exp_avg_sq", "param.0.weight"} <= set(small[0]["sampled"]) and "loss" not in small[0]["sampled"]
+    for k, v in want.items():
+        a, a2 = np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy")
+        assert np.array_equal(a, a2), k
+        if k in small[0]["sampled"]:
+            assert a.ndim == 1 and a.size < v.numel() and np.isin(a, v.detach().numpy()).all(), k
+        else:
+            assert np.array_equal(a, v.detach().numpy()), k
+
+
+@pytest.mark.gpu
+def test_dump_outputs_holds_the_last_timed_step(tmp_path):
+    """`--dump-outputs DIR` on the GPU: the loss written is the result line's final loss, every file is float32, nothing is
+    sampled at this size, and the files stay under 64 MB."""
+    if not has_gpu():
+        pytest.skip("needs a GPU")
+    import numpy as np
+    r = _run({}, "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8", "--alt-steps", "0", "--iso-steps", "1",
+             "--cpu-sample", "0", "--baseline-steps", "0", "--harness-epochs", "0", "--dump-outputs", str(tmp_path))
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    res = json.loads(lines[0])
+    assert res["steps"] == 3 and res["ms_per_step"] > 0
+    dumped = res["dump_outputs"]
+    names = sorted(f[:-len(".npy")] for f in os.listdir(tmp_path))
+    assert all(f.endswith(".npy") for f in os.listdir(tmp_path)) and len(names) == dumped["arrays"] and dumped["sampled"] == []
+    assert {"loss", "adam.exp_avg", "adam.exp_avg_sq"} <= set(names) and any(k.startswith("param.sbm.") for k in names)
+    assert float(np.load(tmp_path / "loss.npy")) == res["config"]["final_loss"]
+    for k in names:
+        a = np.load(tmp_path / f"{k}.npy")
+        assert a.dtype == np.float32 and np.isfinite(a).all(), k
+    assert sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path)) < 64_000_000
+
+
 @pytest.mark.gpu
 def test_two_rank_rehearsal_end_to_end():
     if not has_gpu():

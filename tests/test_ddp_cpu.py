@@ -26,6 +26,7 @@ def _init(rank, world, port):
                       LOCAL_RANK=str(rank))
     sys.path.insert(0, ROOT)
     import speech_imagery_eeg_amd  # noqa: F401
+    torch.cuda.is_available = lambda: False        # CPU ranks even where a GPU is visible (Experiment picks cuda:LOCAL_RANK)
     torch.set_num_threads(2)
     dist.init_process_group("gloo", rank=rank, world_size=world)
 

@@ -212,6 +212,7 @@ def test_experiment_harness_with_oracle_models(tmp_path, monkeypatch):
     from oracle import ign_oracle as O
     d = _write_bm(str(tmp_path))
     monkeypatch.chdir(tmp_path)
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)      # on CPU even where a GPU is visible
     monkeypatch.setitem(Experiment.model_dict, 'InterpGN', lambda cfg: O.OracleIGN(cfg))
     monkeypatch.setitem(Experiment.model_dict, 'SBM', lambda configs, num_shapelet, shapelet_len:
                         O.OracleSBM(configs, num_shapelet, shapelet_len))
