@@ -130,8 +130,8 @@ int ign_shapelet_bwd_bank(const float* xn_bct, int G, const float* const* w_kcl,
                           int B, int C, int T, const int* K, const int* L, const int* stride, float eps, int mode, void* stream);
 
 /* Fused attention core softmax(scale * Q K^T) V, exact fp32 on the matrix cores (v_mfma_f32_32x32x2_f32), scores never
- * materialised.  Replaces IGN/layers/SelfAttention_Family.py:56-75 (FullAttention: no mask, dropout 0) and the
- * attention inside nn.TransformerEncoderLayer of IGN/model/eegcnn.py:219-228.
+ * materialised.  Replaces IGN/layers/SelfAttention_Family.py:56-75 (FullAttention: no mask; dropout 0 here -- dropout p > 0
+ * is ign_attn_*_dropout below) and the attention inside nn.TransformerEncoderLayer of IGN/model/eegcnn.py:219-228.
  *   q (B,L,H,E), k/v (B,S,H,E): unit stride over E, stride E over H; *_sb / *_sl are the ELEMENT strides of the
  *   batch and sequence axes (multiples of 4), so packed qkv projections can be passed without a copy.
  *   out (B,L,H,E) contiguous; lse (B,H,L) log-sum-exp of the scaled scores (saved for the backward).
@@ -198,6 +198,42 @@ int ign_attn_bwd_h3(const float* q, const float* k, const float* v, const float*
                     const float* bq, const float* bk, const float* bv, const float* bgo,
                     float* g_amax /* nullable: max over |gq|, |gk|, |gv| as an atomic maximum (caller zeroes) -- the bound of
                                      the packed gradient for the projection's backward GEMMs */);
+
+/* Attention dropout: A = dropout(softmax(scale Q K^T)) as in IGN/layers/SelfAttention_Family.py:56-75 and the self_attn of
+ * nn.TransformerEncoderLayer (IGN/model/eegcnn.py:219-228), inside the fused kernels (the DROPOUT instantiations of all six).
+ * Keep mask (csrc/ign_dropout.h, the one definition every kernel and ign_attn_dropout_mask evaluate): the decision for score
+ * element (b, h, i, j) is a pure function of (seed, b*H + h, i, j, p) -- independent of tiles, launch geometry, kernel and
+ * arithmetic.  Philox4x32-10 (Random123 constants), key = seed (low word first), counter = (i>>2, j>>2, b*H + h, c); the 4x4
+ * block (i>>2, j>>2) takes its 16 halfwords from the calls c = 0, 1 and element (i, j) reads halfword n = (i&3)*4 + (j&3):
+ * call n>>3, word (n&7)>>1, low half for even n.  keep <=> halfword >= thr, thr = round(p * 65536) (p_eff = thr / 65536); kept
+ * values are scaled by s = 65536 / (65536 - thr) (fp32).  p in [0, 1) with thr < 65536, else IGN_E_ARG.
+ *   forward:  O = (Z o P) V s, P = softmax(scale Q K^T); lse stays the statistic of the UN-dropped softmax; s is folded into the
+ *             final normalisation, so P <= 1 still holds for the h3 split;
+ *   backward: dV = (Z o P)^T dO s; dP = dO V^T; dS = P o (Z o dP s - D), D = rowsum(dO o O) as without dropout.
+ *   h3: the score-gradient bound grows to 2 E max|dO| max|V| s; a bound of the output is max|v| s (not max|v|).
+ * Arguments: those of ign_attn_fwd / ign_attn_bwd_h3, plus `math` (IGN_ATTN_MATH_*; bq / bk / bv / bgo / g_amax are read for H3
+ * only and may be null otherwise; BF16 and H3 need E <= 64), g_sb / g_sl (0, 0: contiguous gradients; else the strided
+ * gradients of ign_attn_bwd_x6_strided -- not with F32), and p, seed.  The backward regenerates the mask from (p, seed): pass
+ * the forward's values.                                                                                                       */
+#define IGN_ATTN_MATH_F32  0   /* fp32 MFMA (ign_attn_fwd / ign_attn_bwd)                                          */
+#define IGN_ATTN_MATH_X6   1   /* three bf16 planes, six products (ign_attn_fwd_x6 / ign_attn_bwd_x6)            */
+#define IGN_ATTN_MATH_BF16 2   /* one bf16 product: the autocast arithmetic (ign_attn_fwd_bf16 / _bwd_bf16)       */
+#define IGN_ATTN_MATH_H3   3   /* two fp16 planes, three products (ign_attn_fwd_h3 / ign_attn_bwd_h3)             */
+int ign_attn_fwd_dropout(const float* q, const float* k, const float* v, float* out, float* lse,
+                         int B, int L, int S, int H, int E,
+                         long long q_sb, long long q_sl, long long k_sb, long long k_sl, long long v_sb, long long v_sl,
+                         float scale, void* stream, int math, const float* bq, const float* bk, const float* bv,
+                         float p, unsigned long long seed);
+int ign_attn_bwd_dropout(const float* q, const float* k, const float* v, const float* out, const float* lse, const float* gout,
+                         float* gq, float* gk, float* gv, float* delta_ws,
+                         int B, int L, int S, int H, int E,
+                         long long q_sb, long long q_sl, long long k_sb, long long k_sl, long long v_sb, long long v_sl,
+                         float scale, void* stream, int math, long long g_sb, long long g_sl,
+                         const float* bq, const float* bk, const float* bv, const float* bgo, float* g_amax,
+                         float p, unsigned long long seed);
+/* The (B, H, L, S) keep mask of one call as bytes (1 = kept), through the same device function as the kernels: test and
+ * debugging infrastructure.                                                                                                   */
+int ign_attn_dropout_mask(unsigned char* keep, int B, int H, int L, int S, float p, unsigned long long seed, void* stream);
 
 /* Skinny expert-head GEMM  out[b,n] = sum_f X[b,f] W[n,f] (+ bias[n]),  N <= 16 classes, F % 4 == 0, row pitch ldx.
  * Replaces nn.Linear at IGN/model/Shapelet.py:171,200 (SBM head), IGN/model/Transformer.py:72,109,

@@ -17,6 +17,7 @@
 // The k index of a 32x32x2 step is split over the lane halves: half h covers e in [h*E/2, (h+1)*E/2), so a lane's
 // operand stream is E/2 CONTIGUOUS floats (ds_read_b128), not a stride-2 gather.
 #include "ign_common.h"
+#include "ign_dropout.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -27,6 +28,10 @@ struct AttnArgs {
     long long q_sb, q_sl, k_sb, k_sl, v_sb, v_sl;
     int B, L, S, H, E;
     float scale;
+    // DROPOUT instantiations (ign_dropout.h): per-call seed, keep threshold, 1 / (1 - p_eff)
+    unsigned long long seed;
+    unsigned thr;
+    float dscale;
 };
 
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
@@ -48,7 +53,7 @@ __device__ __forceinline__ void stage_tile(float* dst, const float* src, long lo
 }
 
 // ------------------------------------------------------------------------------------------------ forward
-template <int E>
+template <int E, bool DROPOUT = false>
 __global__ void __launch_bounds__(256) attn_fwd_kernel(const AttnArgs a) {
     constexpr int EH = E / 2, ED = (E + 31) / 32, PITCH = E + 4;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -118,6 +123,15 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const AttnArgs a) {
                 psum += __shfl_xor(psum, 32, 64);
                 l = l * alpha + psum;
                 m = mnew;
+                if constexpr (DROPOUT) {                     // l (and the lse) stay the un-dropped softmax's; Z o P enters O
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        const uint32_t kp = ign_drop_row4(a.seed, b * a.H + head, qi, kt0 + kb + 8 * g + 4 * h, a.thr);
+#pragma unroll
+                        for (int t = 0; t < 4; ++t)
+                            if (!((kp >> t) & 1u)) acc[4 * g + t] = 0.f;
+                    }
+                }
 #pragma unroll
                 for (int d = 0; d < ED; ++d) {
 #pragma unroll
@@ -134,7 +148,7 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const AttnArgs a) {
         }
     }
     if (q_ok) {
-        const float inv = 1.f / l;
+        const float inv = DROPOUT ? a.dscale / l : 1.f / l;
         float* op = a.out + (((long long)b * a.L + qi) * a.H + head) * E;
 #pragma unroll
         for (int d = 0; d < ED; ++d)
@@ -172,7 +186,7 @@ __global__ void __launch_bounds__(256) attn_delta_kernel(const float* __restrict
 // ------------------------------------------------------------------------------------------------ backward: dK, dV
 // Block = 4 waves x 32 keys; loops over query tiles.  Per (32 queries x 32 keys): S = Q K^T, dP = dO V^T,
 // P = exp(S - lse), dS = P (dP - delta) scale, dV^T += dO^T P, dK^T += Q^T dS.
-template <int E>
+template <int E, bool DROPOUT = false>
 __global__ void __launch_bounds__(256, 2) attn_bwd_dkdv_kernel(const AttnArgs a) {
     constexpr int EH = E / 2, ED = (E + 31) / 32, PITCH = E + 4;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -240,12 +254,27 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_dkdv_kernel(const AttnArgs a)
                     s = MFMA(qv.w, Kf[kk + 3], s);  dp = MFMA(gv.w, Vf[kk + 3], dp);
                 }
                 // rows = queries qb + acc_row(r,h); column = this lane's key
+                if constexpr (DROPOUT) {                     // s <- Z o P (dV, scaled by 1/(1-p) at the end); dS = P (Z o dP / (1-p) - delta)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int qq = qb + acc_row(r, h);
-                    const float p = k_ok ? __expf(s[r] - Ls[qq]) : 0.f;
-                    s[r] = p;
-                    dp[r] = p * (dp[r] - Ds[qq]) * a.scale;
+                    for (int g = 0; g < 4; ++g) {
+                        const uint32_t kp = ign_drop_col4(a.seed, b * a.H + head, qt0 + qb + 8 * g + 4 * h, ki, a.thr);
+#pragma unroll
+                        for (int t = 0; t < 4; ++t) {
+                            const int r = 4 * g + t, qq = qb + acc_row(r, h);
+                            const bool keep = (kp >> t) & 1u;
+                            const float p = k_ok ? __expf(s[r] - Ls[qq]) : 0.f;
+                            s[r] = keep ? p : 0.f;
+                            dp[r] = p * ((keep ? dp[r] * a.dscale : 0.f) - Ds[qq]) * a.scale;
+                        }
+                    }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int qq = qb + acc_row(r, h);
+                        const float p = k_ok ? __expf(s[r] - Ls[qq]) : 0.f;
+                        s[r] = p;
+                        dp[r] = p * (dp[r] - Ds[qq]) * a.scale;
+                    }
                 }
 #pragma unroll
                 for (int d = 0; d < ED; ++d) {
@@ -263,6 +292,12 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_dkdv_kernel(const AttnArgs a)
                 }
             }
         }
+    }
+    if constexpr (DROPOUT) {
+#pragma unroll
+        for (int d = 0; d < ED; ++d)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) dV[d][r] *= a.dscale;
     }
     if (k_ok) {
         float* pk = a.gk + (((long long)b * a.S + ki) * a.H + head) * E;
@@ -284,7 +319,7 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_dkdv_kernel(const AttnArgs a)
 // Block = 4 waves x 32 queries; loops over key tiles.  S^T = K Q^T, dP^T = V dO^T, dS^T = P^T (dP^T - delta) scale,
 // dQ^T += K^T dS^T.  Recomputing S and dP here (7 products in total instead of 5) keeps dQ free of float atomics:
 // the result is bitwise reproducible.
-template <int E>
+template <int E, bool DROPOUT = false>
 __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const AttnArgs a) {
     constexpr int EH = E / 2, ED = (E + 31) / 32, PITCH = E + 4;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -342,11 +377,25 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const AttnArgs a) {
                     s = MFMA(kv.z, Qf[kk + 2], s);  dp = MFMA(vv.z, Gf[kk + 2], dp);
                     s = MFMA(kv.w, Qf[kk + 3], s);  dp = MFMA(vv.w, Gf[kk + 3], dp);
                 }
+                if constexpr (DROPOUT) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const bool key_ok = kt0 + kb + acc_row(r, h) < a.S;
-                    const float p = key_ok ? __expf(s[r] - lse) : 0.f;
-                    dp[r] = p * (dp[r] - delta) * a.scale;
+                    for (int g = 0; g < 4; ++g) {
+                        const uint32_t kp = ign_drop_row4(a.seed, b * a.H + head, qi, kt0 + kb + 8 * g + 4 * h, a.thr);
+#pragma unroll
+                        for (int t = 0; t < 4; ++t) {
+                            const int r = 4 * g + t;
+                            const bool key_ok = kt0 + kb + acc_row(r, h) < a.S;
+                            const float p = key_ok ? __expf(s[r] - lse) : 0.f;
+                            dp[r] = p * ((((kp >> t) & 1u) ? dp[r] * a.dscale : 0.f) - delta) * a.scale;
+                        }
+                    }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const bool key_ok = kt0 + kb + acc_row(r, h) < a.S;
+                        const float p = key_ok ? __expf(s[r] - lse) : 0.f;
+                        dp[r] = p * (dp[r] - delta) * a.scale;
+                    }
                 }
 #pragma unroll
                 for (int d = 0; d < ED; ++d) {
@@ -464,4 +513,71 @@ extern "C" int ign_attn_bwd(const float* q, const float* k, const float* v, cons
         ATTN_DISPATCH(E, attn_bwd_dq_kernel, grid, lds, s, a);
     }
     return ign_check_launch("attn_bwd_dq_kernel");
+}
+
+// ------------------------------------------------------------------------------------------------ dropout (ign_attn_*_dropout)
+// The DROPOUT instantiations of the three kernels above; arguments checked by the caller (ign_attention_x6.hip) except for the
+// common dimension / pointer / stride checks.
+#define ATTN_DISPATCH_D(E_, KERNEL, grid, lds, stream, args)                                         \
+    switch (E_) {                                                                                   \
+        case 16: hipLaunchKernelGGL((KERNEL<16, true>), grid, dim3(256), lds, stream, args); break; \
+        case 32: hipLaunchKernelGGL((KERNEL<32, true>), grid, dim3(256), lds, stream, args); break; \
+        case 64: hipLaunchKernelGGL((KERNEL<64, true>), grid, dim3(256), lds, stream, args); break; \
+        default: hipLaunchKernelGGL((KERNEL<128, true>), grid, dim3(256), lds, stream, args); break;\
+    }
+
+int ign_attn_f32_dropout_fwd(const char* who, const float* q, const float* k, const float* v, float* out, float* lse, int B, int L,
+                             int S, int H, int E, long long q_sb, long long q_sl, long long k_sb, long long k_sl, long long v_sb,
+                             long long v_sl, float scale, void* stream, unsigned long long seed, unsigned thr, float dscale) {
+    const long long st[6] = {q_sb, q_sl, k_sb, k_sl, v_sb, v_sl};
+    const void* ptrs[5] = {q, k, v, out, lse};
+    int rc;
+    if ((rc = attn_check(who, B, L, S, H, E, st, ptrs, 5))) return rc;
+    AttnArgs a = {};
+    a.q = q; a.k = k; a.v = v; a.out = out; a.lse_out = lse;
+    a.q_sb = q_sb; a.q_sl = q_sl; a.k_sb = k_sb; a.k_sl = k_sl; a.v_sb = v_sb; a.v_sl = v_sl;
+    a.B = B; a.L = L; a.S = S; a.H = H; a.E = E; a.scale = scale;
+    a.seed = seed; a.thr = thr; a.dscale = dscale;
+    const size_t lds = (size_t)2 * ATT_KT * (E + 4) * sizeof(float);
+    const dim3 grid((L + 127) / 128, H, B);
+    IgnScopedTimer tm("attn_fwd", (hipStream_t)stream);
+    ATTN_DISPATCH_D(E, attn_fwd_kernel, grid, lds, (hipStream_t)stream, a);
+    return ign_check_launch("attn_fwd_kernel<dropout>");
+}
+
+int ign_attn_f32_dropout_bwd(const char* who, const float* q, const float* k, const float* v, const float* out, const float* lse,
+                             const float* gout, float* gq, float* gk, float* gv, float* delta_ws, int B, int L, int S, int H, int E,
+                             long long q_sb, long long q_sl, long long k_sb, long long k_sl, long long v_sb, long long v_sl,
+                             float scale, void* stream, unsigned long long seed, unsigned thr, float dscale) {
+    const long long st[6] = {q_sb, q_sl, k_sb, k_sl, v_sb, v_sl};
+    const void* ptrs[10] = {q, k, v, out, lse, gout, gq, gk, gv, delta_ws};
+    int rc;
+    if ((rc = attn_check(who, B, L, S, H, E, st, ptrs, 10))) return rc;
+    AttnArgs a = {};
+    a.q = q; a.k = k; a.v = v; a.o = out; a.lse = lse; a.go = gout; a.delta = delta_ws;
+    a.gq = gq; a.gk = gk; a.gv = gv; a.delta_out = delta_ws;
+    a.q_sb = q_sb; a.q_sl = q_sl; a.k_sb = k_sb; a.k_sl = k_sl; a.v_sb = v_sb; a.v_sl = v_sl;
+    a.B = B; a.L = L; a.S = S; a.H = H; a.E = E; a.scale = scale;
+    a.seed = seed; a.thr = thr; a.dscale = dscale;
+    hipStream_t s = (hipStream_t)stream;
+    {
+        const long long n = (long long)B * L * H;
+        IgnScopedTimer tm("attn_delta", s);
+        hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, out, gout, delta_ws, B, L, H, E);
+    }
+    if ((rc = ign_check_launch("attn_delta_kernel"))) return rc;
+    {
+        const size_t lds = ((size_t)2 * ATT_KT * (E + 4) + 2 * ATT_KT) * sizeof(float);
+        const dim3 grid((S + 127) / 128, H, B);
+        IgnScopedTimer tm("attn_bwd_dkdv", s);
+        ATTN_DISPATCH_D(E, attn_bwd_dkdv_kernel, grid, lds, s, a);
+    }
+    if ((rc = ign_check_launch("attn_bwd_dkdv_kernel<dropout>"))) return rc;
+    {
+        const size_t lds = (size_t)2 * ATT_KT * (E + 4) * sizeof(float);
+        const dim3 grid((L + 127) / 128, H, B);
+        IgnScopedTimer tm("attn_bwd_dq", s);
+        ATTN_DISPATCH_D(E, attn_bwd_dq_kernel, grid, lds, s, a);
+    }
+    return ign_check_launch("attn_bwd_dq_kernel<dropout>");
 }

@@ -15,6 +15,7 @@
 //     what gfx950's transposing LDS read ds_read_b64_tr_b16 delivers for the A operand V^T (lane = feature column, 4 rows per
 //     read) from a V tile staged row-major.  No LDS round trip for P, no transposed copy of V.
 #include "ign_common.h"
+#include "ign_dropout.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -30,6 +31,9 @@ struct AttnX6Args {
     int B, L, S, H, E;
     float scale;
     const float *bq, *bk, *bv;               // NP = 2 (two fp16 planes, three products): device-side bounds of |q|, |k|, |v|
+    unsigned long long seed;                 // DROPOUT instantiations (ign_dropout.h): per-call seed, keep threshold, 1 / (1 - p_eff)
+    unsigned thr;
+    float dscale;
 };
 
 // ---- NP = 2: two fp16 planes of power-of-two-scaled operands, THREE products (include/ign_abi.h, "h3").  Scales come from
@@ -145,7 +149,7 @@ template <int E> struct AxPitch {
     static constexpr int V = E >= 64 ? E + 32 : E + E / 2;        // transposing reads: rows 0..3 of a block 16 banks apart
 };
 
-template <int E, int NP>
+template <int E, int NP, bool DROPOUT = false>
 __global__ void __launch_bounds__(256, 2) attn_fwd_x6_kernel(const AttnX6Args a) {
     constexpr int NS = E / 16, ED = (E + 31) / 32, PK = AxPitch<E>::K, PV = AxPitch<E>::V, AX_KT = AxPitch<E>::KT;
     constexpr int KPLANE = AX_KT * PK, VPLANE = AX_KT * PV;
@@ -276,6 +280,15 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_x6_kernel(const AttnX6Args a)
                 psum += __shfl_xor(psum, 32, 64);
                 l = l * alpha + psum;
                 m = mnew;
+                if constexpr (DROPOUT) {      // l (and the lse) stay the un-dropped softmax's; Z o P (still <= 1, or 2^14) enters O
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        const uint32_t kp = ign_drop_row4(a.seed, b * a.H + head, qi, kt0 + kb + 8 * g + 4 * h, a.thr);
+#pragma unroll
+                        for (int t = 0; t < 4; ++t)
+                            if (!((kp >> t) & 1u)) acc[4 * g + t] = 0.f;
+                    }
+                }
                 // P^T operand: registers 8*s2 .. 8*s2+7 are the 16-key slab s2
                 bf16x8 Pf[3][2];
 #pragma unroll
@@ -312,7 +325,8 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_x6_kernel(const AttnX6Args a)
     }
     if (q_ok) {
         // NP = 2: O holds sv * 2^14 * sum p v and l holds 2^14 * sum p
-        const float inv = (NP == 2) ? 1.f / (l * sv) : 1.f / l;
+        // DROPOUT: 1 / (1 - p_eff) is folded in here, not into P
+        const float inv = (NP == 2) ? (DROPOUT ? a.dscale : 1.f) / (l * sv) : (DROPOUT ? a.dscale : 1.f) / l;
         if constexpr (NP == 2) l *= 6.103515625e-05f;              // 2^-14: the log-sum-exp below is of the unscaled sum
         float* op = a.out + (((long long)b * a.L + qi) * a.H + head) * E;
 #pragma unroll
@@ -344,6 +358,9 @@ struct AttnX6BwdArgs {
     float scale;
     const float *bq, *bk, *bv, *bg;                // NP = 2: device-side bounds of |q|, |k|, |v|, |dO|
     float* gmax;                                   // nullable: max |dq|, |dk|, |dv| as an atomic maximum (bound of the packed gradient)
+    unsigned long long seed;                       // DROPOUT instantiations (ign_dropout.h): seed, keep threshold, 1 / (1 - p_eff)
+    unsigned thr;
+    float dscale;
 };
 
 constexpr int AB_T = 32;                                          // rows per staged tile
@@ -489,7 +506,7 @@ __device__ __forceinline__ void wave_amax_to(float* slot, float am, int lane) {
 
 // ---- dQ: block = 4 waves x 32 queries (lanes); loops over key tiles.  S^T = K Q^T, dP^T = V dO^T, dS^T = P^T (dP^T - delta),
 // dQ^T += K^T dS^T, scaled once at the end.
-template <int E, int NP>
+template <int E, int NP, bool DROPOUT = false>
 __global__ void __launch_bounds__(256, 2) attn_bwd_dq_x6_kernel(const AttnX6BwdArgs a) {
     constexpr int NS = E / 16, ED = (E + 31) / 32, P = AbCfg<E>::P, PLANE = AbCfg<E>::PLANE;
     constexpr int V4 = AbCfg<E>::V4, RPP = AbCfg<E>::RPP, NP4 = AbCfg<E>::NP4;
@@ -504,12 +521,12 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_dq_x6_kernel(const AttnX6BwdA
     const long long qrow = q_ok ? qi : a.L - 1;
 
     // NP = 2 scales: registers Q (sq, incl. the softmax scale) and dO (sg); staged tiles K (sta = sk) and V (stb = sv);
-    // dS by the hard bound |dS| <= p (|dP| + |delta|) <= 2 E max|dO| max|V|
+    // dS by the hard bound |dS| <= p (|dP| + |delta|) <= 2 E max|dO| max|V| (DROPOUT: |dP| s + |delta| <= 2 E max|dO| max|V| s)
     const float sc2u = a.scale * 1.44269504088896341f;
     const float sq = (NP == 2) ? pow2_scale_v(*a.bq * fabsf(sc2u)) : 1.f;
     const float sg = (NP == 2) ? pow2_scale_v(*a.bg) : 1.f;
     const float sta = (NP == 2) ? pow2_scale_v(*a.bk) : 1.f, stb = (NP == 2) ? pow2_scale_v(*a.bv) : 1.f;
-    const float sds = (NP == 2) ? pow2_scale_v(2.f * (float)E * *a.bg * *a.bv) : 1.f;
+    const float sds = (NP == 2) ? pow2_scale_v(DROPOUT ? 2.f * (float)E * *a.bg * *a.bv * a.dscale : 2.f * (float)E * *a.bg * *a.bv) : 1.f;
     const float us = (NP == 2) ? 1.f / (sq * sta) : 1.f, up = (NP == 2) ? 1.f / (sg * stb) : 1.f;
     bf16x8 Qf[3][NS], Gf[3][NS];
     float del_q = 0.f;                                         // delta = rowsum(dO * O): this lane's half of the row, then lane ^ 32
@@ -558,10 +575,25 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_dq_x6_kernel(const AttnX6BwdA
             for (int r = 0; r < 16; ++r)
                 if (kt0 + acc_row(r, h) >= a.S) st[r] = -INFINITY;
         }
+        if constexpr (DROPOUT) {                                 // dS = P (Z o dP / (1 - p) - delta)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            if constexpr (NP == 2) dp[r] = __builtin_amdgcn_exp2f(fmaf(st[r], us, -lse_q)) * fmaf(dp[r], up * sds, -del_q * sds);
-            else dp[r] = __builtin_amdgcn_exp2f(st[r] - lse_q) * (dp[r] - del_q);
+            for (int g = 0; g < 4; ++g) {
+                const uint32_t kp = ign_drop_row4(a.seed, b * a.H + head, qi, kt0 + 8 * g + 4 * h, a.thr);
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const int r = 4 * g + t;
+                    const bool keep = (kp >> t) & 1u;
+                    if constexpr (NP == 2)
+                        dp[r] = __builtin_amdgcn_exp2f(fmaf(st[r], us, -lse_q)) * (keep ? fmaf(dp[r], up * sds * a.dscale, -del_q * sds) : -del_q * sds);
+                    else dp[r] = __builtin_amdgcn_exp2f(st[r] - lse_q) * ((keep ? dp[r] * a.dscale : 0.f) - del_q);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                if constexpr (NP == 2) dp[r] = __builtin_amdgcn_exp2f(fmaf(st[r], us, -lse_q)) * fmaf(dp[r], up * sds, -del_q * sds);
+                else dp[r] = __builtin_amdgcn_exp2f(st[r] - lse_q) * (dp[r] - del_q);
+            }
         }
         x6_tileT_times_acc<E, NP>(dQ, Ks, dp, lane);
     }
@@ -575,7 +607,7 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_dq_x6_kernel(const AttnX6BwdA
 // ---- dK / dV: block = 4 waves x 32 keys (lanes); loops over query tiles.  S = Q K^T (rows = queries), P = exp(S - lse);
 //   DV:  dV^T += dO^T P                                   (K^T in registers)
 //   !DV: dP = dO V^T, dS = P (dP - delta), dK^T += Q^T dS  (K^T and V^T in registers), scaled once at the end
-template <int E, bool DV, int NP>
+template <int E, bool DV, int NP, bool DROPOUT = false>
 __global__ void __launch_bounds__(256, 2) attn_bwd_dkv_x6_kernel(const AttnX6BwdArgs a) {
     constexpr int NS = E / 16, ED = (E + 31) / 32, P = AbCfg<E>::P, PLANE = AbCfg<E>::PLANE;
     constexpr int V4 = AbCfg<E>::V4, RPP = AbCfg<E>::RPP, NP4 = AbCfg<E>::NP4;
@@ -598,7 +630,7 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_dkv_x6_kernel(const AttnX6Bwd
     const float sk = (NP == 2) ? pow2_scale_v(*a.bk * fabsf(sc2u)) : 1.f;
     const float sv = (NP == 2) ? pow2_scale_v(*a.bv) : 1.f;
     const float sta = (NP == 2) ? pow2_scale_v(*a.bq) : 1.f, stb = (NP == 2) ? pow2_scale_v(*a.bg) : 1.f;
-    const float sds = (NP == 2) ? pow2_scale_v(2.f * (float)E * *a.bg * *a.bv) : 1.f;
+    const float sds = (NP == 2) ? pow2_scale_v(DROPOUT ? 2.f * (float)E * *a.bg * *a.bv * a.dscale : 2.f * (float)E * *a.bg * *a.bv) : 1.f;
     const float us = (NP == 2) ? 1.f / (sk * sta) : 1.f, up = (NP == 2) ? 1.f / (sv * stb) : 1.f;
     const float pexp = (NP == 2 && DV) ? 14.f : 0.f;              // the dV product takes 2^14 p as its operand
     bf16x8 Kf[3][NS], Vf[3][DV ? 1 : NS];
@@ -664,7 +696,18 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_dkv_x6_kernel(const AttnX6Bwd
                 s[4 * g + 3] = __builtin_amdgcn_exp2f(s[4 * g + 3] - lv.w + kmask);
             }
         }
+        // DROPOUT: this lane's key against the tile's queries qt0 + 8 g + 4 h + t (bit t of kp[g])
+        uint32_t kp[4] = {0xfu, 0xfu, 0xfu, 0xfu};
+        if constexpr (DROPOUT) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) kp[g] = ign_drop_col4(a.seed, b * a.H + head, qt0 + 8 * g + 4 * h, ki, a.thr);
+        }
         if constexpr (DV) {
+            if constexpr (DROPOUT) {                               // dV^T += dO^T (Z o P), scaled by 1 / (1 - p) at the end
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    if (!((kp[r >> 2] >> (r & 3)) & 1u)) s[r] = 0.f;
+            }
             x6_tileT_times_acc<E, NP>(G, Gs, s, lane);
         } else {
             f32x16 dp;
@@ -674,7 +717,16 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_dkv_x6_kernel(const AttnX6Bwd
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const float4 dv = *reinterpret_cast<const float4*>(Ds + 8 * g + 4 * h);
-                if constexpr (NP == 2) {
+                if constexpr (DROPOUT) {                           // dS = P (Z o dP / (1 - p) - delta)
+                    const float ups = (NP == 2) ? up * sds * a.dscale : a.dscale;
+                    const float dd[4] = {dv.x, dv.y, dv.z, dv.w};
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {
+                        const int r = 4 * g + t;
+                        const float ds_ = (NP == 2) ? dd[t] * sds : dd[t];
+                        dp[r] = s[r] * (((kp[g] >> t) & 1u) ? fmaf(dp[r], ups, -ds_) : -ds_);
+                    }
+                } else if constexpr (NP == 2) {
                     const float ups = up * sds;
                     dp[4 * g] = s[4 * g] * fmaf(dp[4 * g], ups, -dv.x * sds);
                     dp[4 * g + 1] = s[4 * g + 1] * fmaf(dp[4 * g + 1], ups, -dv.y * sds);
@@ -694,16 +746,19 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_dkv_x6_kernel(const AttnX6Bwd
     if (k_ok) {
         float* dst = (DV ? a.gv : a.gk) + b * a.gkv_sb + (long long)ki * a.g_sl + head * E;
         // NP = 2: dV holds sg 2^14 dO^T P; dK holds sq sds Q^T dS
-        am = store_grad_rows<E>(dst, G, DV ? ((NP == 2) ? 6.103515625e-05f / stb : 1.f) : ((NP == 2) ? a.scale / (sta * sds) : a.scale), h);
+        float gsc = DV ? ((NP == 2) ? 6.103515625e-05f / stb : 1.f) : ((NP == 2) ? a.scale / (sta * sds) : a.scale);
+        if constexpr (DROPOUT && DV) gsc *= a.dscale;             // dV = (Z o P)^T dO / (1 - p)
+        am = store_grad_rows<E>(dst, G, gsc, h);
     }
     if (a.gmax) wave_amax_to(a.gmax, am, lane);
 }
 
 // ------------------------------------------------------------------------------------------------ C ABI
-template <int NP>
+template <int NP, bool DROPOUT = false>
 static int attn_fwd_x6_impl(const char* who, const float* q, const float* k, const float* v, float* out, float* lse, int B, int L,
                             int S, int H, int E, long long q_sb, long long q_sl, long long k_sb, long long k_sl, long long v_sb,
-                            long long v_sl, float scale, void* stream, const float* const* bounds = nullptr) {
+                            long long v_sl, float scale, void* stream, const float* const* bounds = nullptr,
+                            unsigned long long seed = 0, unsigned thr = 0, float dscale = 1.f) {
     if (B <= 0 || L <= 0 || S <= 0 || H <= 0 || H > 65535 || B > 65535) {
         ign_set_error("%s: bad dimensions B=%d L=%d S=%d H=%d", who, B, L, S, H);
         return IGN_E_ARG;
@@ -731,6 +786,7 @@ static int attn_fwd_x6_impl(const char* who, const float* q, const float* k, con
     a.q_sb = q_sb; a.q_sl = q_sl; a.k_sb = k_sb; a.k_sl = k_sl; a.v_sb = v_sb; a.v_sl = v_sl;
     a.B = B; a.L = L; a.S = S; a.H = H; a.E = E; a.scale = scale;
     if (NP == 2) { a.bq = bounds[0]; a.bk = bounds[1]; a.bv = bounds[2]; }
+    a.seed = seed; a.thr = thr; a.dscale = dscale;
     const dim3 grid((L + 127) / 128, H, B);
     IgnScopedTimer tm("attn_fwd", s);
 #define IGN_AX(EE)                                                                                                            \
@@ -738,11 +794,11 @@ static int attn_fwd_x6_impl(const char* who, const float* q, const float* k, con
         constexpr size_t lds = (size_t)3 * AxPitch<EE>::KT * (AxPitch<EE>::K + AxPitch<EE>::V) * sizeof(unsigned short) + 256; \
         static bool once = false;                                                                                             \
         if (!once) {                                                                                                          \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_x6_kernel<EE, NP>),                              \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_x6_kernel<EE, NP, DROPOUT>),                     \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                  \
             once = true;                                                                                                      \
         }                                                                                                                     \
-        hipLaunchKernelGGL((attn_fwd_x6_kernel<EE, NP>), grid, dim3(256), lds, s, a);                                         \
+        hipLaunchKernelGGL((attn_fwd_x6_kernel<EE, NP, DROPOUT>), grid, dim3(256), lds, s, a);                                \
     } while (0)
     switch (E) {
         case 16: IGN_AX(16); break;
@@ -754,12 +810,13 @@ static int attn_fwd_x6_impl(const char* who, const float* q, const float* k, con
     return ign_check_launch("attn_fwd_x6_kernel");
 }
 
-template <int NP>
+template <int NP, bool DROPOUT = false>
 static int attn_bwd_x6_impl(const char* who, const float* q, const float* k, const float* v, const float* out, const float* lse,
                             const float* gout, float* gq, float* gk, float* gv, float* delta_ws, int B, int L, int S, int H,
                             int E, long long q_sb, long long q_sl, long long k_sb, long long k_sl, long long v_sb,
                             long long v_sl, float scale, void* stream, long long g_sb = 0, long long g_sl = 0,
-                            const float* const* bounds = nullptr, float* g_amax = nullptr) {
+                            const float* const* bounds = nullptr, float* g_amax = nullptr,
+                            unsigned long long seed = 0, unsigned thr = 0, float dscale = 1.f) {
     if (NP == 2 && (!bounds || !bounds[0] || !bounds[1] || !bounds[2] || !bounds[3])) {
         ign_set_error("%s: null operand bound", who);
         return IGN_E_ARG;
@@ -796,6 +853,7 @@ static int attn_bwd_x6_impl(const char* who, const float* q, const float* k, con
     a.B = B; a.L = L; a.S = S; a.H = H; a.E = E; a.scale = scale;
     if (NP == 2) { a.bq = bounds[0]; a.bk = bounds[1]; a.bv = bounds[2]; a.bg = bounds[3]; }
     a.gmax = g_amax;
+    a.seed = seed; a.thr = thr; a.dscale = dscale;
     a.g_sl = g_sl ? g_sl : (long long)H * E;
     a.gq_sb = g_sb ? g_sb : (long long)L * H * E;
     a.gkv_sb = g_sb ? g_sb : (long long)S * H * E;
@@ -814,10 +872,10 @@ static int attn_bwd_x6_impl(const char* who, const float* q, const float* k, con
     do {                                                                                                                      \
         /* dQ first: it also writes delta = rowsum(dO * O), which the dK kernel reads */                                      \
         { IgnScopedTimer tm("attn_bwd_dq", s);                                                                                \
-          IGN_AB(EE, (attn_bwd_dq_x6_kernel<EE, NP>), gq_grid); }                                                             \
+          IGN_AB(EE, (attn_bwd_dq_x6_kernel<EE, NP, DROPOUT>), gq_grid); }                                                    \
         { IgnScopedTimer tm("attn_bwd_dkdv", s);                                                                              \
-          IGN_AB(EE, (attn_bwd_dkv_x6_kernel<EE, true, NP>), gk_grid);                                                        \
-          IGN_AB(EE, (attn_bwd_dkv_x6_kernel<EE, false, NP>), gk_grid); }                                                     \
+          IGN_AB(EE, (attn_bwd_dkv_x6_kernel<EE, true, NP, DROPOUT>), gk_grid);                                               \
+          IGN_AB(EE, (attn_bwd_dkv_x6_kernel<EE, false, NP, DROPOUT>), gk_grid); }                                            \
     } while (0)
     switch (E) {
         case 16: IGN_AB_ALL(16); break;
@@ -875,4 +933,103 @@ extern "C" int ign_attn_bwd_x6_strided(IGN_ATTN_BWD_ARGS, long long g_sb, long l
                                       q_sl, k_sb, k_sl, v_sb, v_sl, scale, stream, g_sb, g_sl)
                 : attn_bwd_x6_impl<3>("ign_attn_bwd_x6_strided", q, k, v, out, lse, gout, gq, gk, gv, delta_ws, B, L, S, H, E, q_sb,
                                       q_sl, k_sb, k_sl, v_sb, v_sl, scale, stream, g_sb, g_sl);
+}
+
+// ------------------------------------------------------------------------------------------------ dropout (include/ign_abi.h)
+// The DROPOUT instantiations of every attention kernel, one keep mask (ign_dropout.h).  math: IGN_ATTN_MATH_*.
+static int dropout_args(const char* who, float p, int E, int math, unsigned* thr, float* dscale) {
+    if (!(p >= 0.f && p < 1.f)) { ign_set_error("%s: dropout p = %g outside [0, 1)", who, (double)p); return IGN_E_ARG; }
+    *thr = ign_dropout_threshold(p);
+    if (*thr >= 65536u) { ign_set_error("%s: dropout p = %g rounds to a keep rate of 0 (p = thr / 65536)", who, (double)p); return IGN_E_ARG; }
+    *dscale = ign_dropout_scale(*thr);
+    if (math < IGN_ATTN_MATH_F32 || math > IGN_ATTN_MATH_H3) { ign_set_error("%s: unknown arithmetic %d", who, math); return IGN_E_ARG; }
+    if (E != 16 && E != 32 && E != 64 && E != 128) {
+        ign_set_error("%s: head dimension E=%d not instantiated (16, 32, 64, 128)", who, E);
+        return IGN_E_UNSUP;
+    }
+    if ((math == IGN_ATTN_MATH_H3 || math == IGN_ATTN_MATH_BF16) && E > 64) {
+        ign_set_error("%s: E=%d > 64 with the %s arithmetic", who, E, math == IGN_ATTN_MATH_H3 ? "h3" : "bf16");
+        return IGN_E_UNSUP;
+    }
+    return 0;
+}
+
+extern "C" int ign_attn_fwd_dropout(IGN_ATTN_FWD_ARGS, int math, const float* bq, const float* bk, const float* bv, float p,
+                                    unsigned long long seed) {
+    static const char* who = "ign_attn_fwd_dropout";
+    unsigned thr;
+    float ds;
+    int rc;
+    if ((rc = dropout_args(who, p, E, math, &thr, &ds))) return rc;
+    const float* bounds[3] = {bq, bk, bv};
+    switch (math) {
+        case IGN_ATTN_MATH_F32:
+            return ign_attn_f32_dropout_fwd(who, q, k, v, out, lse, B, L, S, H, E, q_sb, q_sl, k_sb, k_sl, v_sb, v_sl, scale, stream,
+                                            seed, thr, ds);
+        case IGN_ATTN_MATH_X6:
+            return attn_fwd_x6_impl<3, true>(who, q, k, v, out, lse, B, L, S, H, E, q_sb, q_sl, k_sb, k_sl, v_sb, v_sl, scale, stream,
+                                             nullptr, seed, thr, ds);
+        case IGN_ATTN_MATH_BF16:
+            return attn_fwd_x6_impl<1, true>(who, q, k, v, out, lse, B, L, S, H, E, q_sb, q_sl, k_sb, k_sl, v_sb, v_sl, scale, stream,
+                                             nullptr, seed, thr, ds);
+        default:
+            return attn_fwd_x6_impl<2, true>(who, q, k, v, out, lse, B, L, S, H, E, q_sb, q_sl, k_sb, k_sl, v_sb, v_sl, scale, stream,
+                                             bounds, seed, thr, ds);
+    }
+}
+
+extern "C" int ign_attn_bwd_dropout(IGN_ATTN_BWD_ARGS, int math, long long g_sb, long long g_sl, const float* bq, const float* bk,
+                                    const float* bv, const float* bgo, float* g_amax, float p, unsigned long long seed) {
+    static const char* who = "ign_attn_bwd_dropout";
+    unsigned thr;
+    float ds;
+    int rc;
+    if ((rc = dropout_args(who, p, E, math, &thr, &ds))) return rc;
+    const float* bounds[4] = {bq, bk, bv, bgo};
+    switch (math) {
+        case IGN_ATTN_MATH_F32:
+            if (g_sb || g_sl) { ign_set_error("%s: strided gradients need a split arithmetic (not f32)", who); return IGN_E_UNSUP; }
+            return ign_attn_f32_dropout_bwd(who, q, k, v, out, lse, gout, gq, gk, gv, delta_ws, B, L, S, H, E, q_sb, q_sl, k_sb, k_sl,
+                                            v_sb, v_sl, scale, stream, seed, thr, ds);
+        case IGN_ATTN_MATH_X6:
+            return attn_bwd_x6_impl<3, true>(who, q, k, v, out, lse, gout, gq, gk, gv, delta_ws, B, L, S, H, E, q_sb, q_sl, k_sb, k_sl,
+                                             v_sb, v_sl, scale, stream, g_sb, g_sl, nullptr, nullptr, seed, thr, ds);
+        case IGN_ATTN_MATH_BF16:
+            return attn_bwd_x6_impl<1, true>(who, q, k, v, out, lse, gout, gq, gk, gv, delta_ws, B, L, S, H, E, q_sb, q_sl, k_sb, k_sl,
+                                             v_sb, v_sl, scale, stream, g_sb, g_sl, nullptr, nullptr, seed, thr, ds);
+        default:
+            return attn_bwd_x6_impl<2, true>(who, q, k, v, out, lse, gout, gq, gk, gv, delta_ws, B, L, S, H, E, q_sb, q_sl, k_sb, k_sl,
+                                             v_sb, v_sl, scale, stream, g_sb, g_sl, bounds, g_amax, seed, thr, ds);
+    }
+}
+
+// keep[((b H + h) L + i) S + j] = 1 / 0: one thread per 4 consecutive keys of a query (ign_drop_row4, as the forward evaluates it)
+__global__ void __launch_bounds__(256) attn_dropout_mask_kernel(unsigned char* __restrict__ keep, int H, int L, int S, int S4,
+                                                                long long n4, unsigned long long seed, unsigned thr) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;       // over (b h, i, j4)
+    if (idx >= n4) return;
+    const int j4 = (int)(idx % S4) * 4;
+    const long long row = idx / S4;                                         // (b h) L + i
+    const int i = (int)(row % L);
+    const unsigned bh = (unsigned)(row / L);
+    const uint32_t kp = ign_drop_row4(seed, bh, (uint32_t)i, (uint32_t)j4, thr);
+    unsigned char* dst = keep + row * S + j4;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+        if (j4 + t < S) dst[t] = (unsigned char)((kp >> t) & 1u);
+}
+
+extern "C" int ign_attn_dropout_mask(unsigned char* keep, int B, int H, int L, int S, float p, unsigned long long seed, void* stream) {
+    static const char* who = "ign_attn_dropout_mask";
+    if (!keep) { ign_set_error("%s: null pointer", who); return IGN_E_ARG; }
+    if (B <= 0 || H <= 0 || L <= 0 || S <= 0) { ign_set_error("%s: bad dimensions B=%d H=%d L=%d S=%d", who, B, H, L, S); return IGN_E_ARG; }
+    unsigned thr;
+    float ds;
+    int rc;
+    if ((rc = dropout_args(who, p, 16, IGN_ATTN_MATH_F32, &thr, &ds))) return rc;
+    const int S4 = (S + 3) / 4;
+    const long long n4 = (long long)B * H * L * S4;
+    hipLaunchKernelGGL(attn_dropout_mask_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, keep, H, L, S,
+                       S4, n4, seed, thr);
+    return ign_check_launch("attn_dropout_mask_kernel");
 }

@@ -15,6 +15,16 @@ __device__ __forceinline__ void ign_atomic_absmax(float* slot, float v) {
 
 #define IGN_WAVE 64
 
+// DROPOUT instantiations of the fp32-MFMA attention kernels (ign_attention.hip), dispatched by ign_attn_*_dropout
+// (ign_attention_x6.hip): seed / thr / dscale as in ign_dropout.h
+int ign_attn_f32_dropout_fwd(const char* who, const float* q, const float* k, const float* v, float* out, float* lse, int B, int L,
+                             int S, int H, int E, long long q_sb, long long q_sl, long long k_sb, long long k_sl, long long v_sb,
+                             long long v_sl, float scale, void* stream, unsigned long long seed, unsigned thr, float dscale);
+int ign_attn_f32_dropout_bwd(const char* who, const float* q, const float* k, const float* v, const float* out, const float* lse,
+                             const float* gout, float* gq, float* gk, float* gv, float* delta_ws, int B, int L, int S, int H, int E,
+                             long long q_sb, long long q_sl, long long k_sb, long long k_sl, long long v_sb, long long v_sl,
+                             float scale, void* stream, unsigned long long seed, unsigned thr, float dscale);
+
 // thread-local error message (ign_abi.cpp owns the storage)
 void ign_set_error(const char* fmt, ...);
 int  ign_check_launch(const char* what);

@@ -240,7 +240,18 @@ class Experiment(object):
         a = self.args
         return (getattr(a, 'hipgraph', False) and self.device.type == 'cuda' and not amp and not self.distributed
                 and a.gradient_accumulation_steps == 1 and a.gradient_clip <= 0 and a.model in ('InterpGN', 'SBM', 'LTS')
-                and isinstance(self.optimizer, FlatAdam))
+                and isinstance(self.optimizer, FlatAdam) and not self._attention_dropout_active())
+
+    def _attention_dropout_active(self):
+        """Attention dropout draws a fresh seed per call on the host; a captured graph would replay one mask (ops.attention refuses
+        to be captured with p > 0), so such a model trains eagerly."""
+        from layers.SelfAttention_Family import FullAttention
+        for m in self.model.modules():
+            if isinstance(m, FullAttention) and m.dropout.p > 0:
+                return True
+            if isinstance(m, nn.MultiheadAttention) and m.dropout > 0:
+                return True
+        return False
 
     def _train_one_epoch_graphed(self, epoch, train_step):
         from ign_hip.graph import GraphedTrainStep

@@ -321,11 +321,47 @@ def _bl_strides(t, name):
     return t.stride(0), t.stride(1)
 
 
+# Attention dropout (include/ign_abi.h, "Attention dropout"): arithmetic selectors of ign_attn_fwd_dropout / ign_attn_bwd_dropout
+ATTN_MATH_F32, ATTN_MATH_X6, ATTN_MATH_BF16, ATTN_MATH_H3 = 0, 1, 2, 3
+
+
+def dropout_threshold(p):
+    """-> (thr, s) of the kernels' keep rule for a dropout rate p (as the fp32 the C ABI receives): keep <=> a 16-bit Philox
+    halfword >= thr, thr = round(p * 65536); kept probabilities are scaled by s = 65536 / (65536 - thr) (fp32)."""
+    p32 = ctypes.c_float(p).value
+    if not (0.0 <= p32 < 1.0):
+        raise ValueError(f"attention dropout p = {p} outside [0, 1)")
+    thr = round(p32 * 65536.0)                  # exact product; round half to even like rintf
+    if thr >= 65536:
+        raise ValueError(f"attention dropout p = {p} rounds to a keep rate of 0")
+    return thr, ctypes.c_float(ctypes.c_float(65536.0).value / float(65536 - thr)).value
+
+
+def _dropout_seed(p):
+    """A fresh 64-bit seed from torch's default generator (torch.manual_seed makes a step reproducible to the bit).  A seed passed
+    by value would be baked into a captured hipGraph and every replay would reuse one mask: refused while capturing."""
+    dropout_threshold(p)
+    if torch.cuda.is_current_stream_capturing():
+        raise _lib.IgnError("attention dropout p > 0 inside a hipGraph capture: the per-call seed would be frozen into the graph "
+                            "(run the step eagerly, or with attention dropout 0)")
+    lo, hi = torch.randint(0, 2 ** 32, (2,), dtype=torch.int64).tolist()
+    return lo | (hi << 32)
+
+
+def _attn_math(ctx, E, bwd):
+    if ctx.h3:
+        return ATTN_MATH_H3
+    if ctx.bf16:
+        return ATTN_MATH_BF16
+    return ATTN_MATH_X6 if (ATTN_MATH == "bf16x6" and (E <= 64 or not bwd)) else ATTN_MATH_F32
+
+
 class AttentionFn(torch.autograd.Function):
-    """softmax(scale * Q K^T) V with q (B,L,H,E), k/v (B,S,H,E) -> (B,L,H,E); IGN/layers/SelfAttention_Family.py:56-75."""
+    """softmax(scale * Q K^T) V with q (B,L,H,E), k/v (B,S,H,E) -> (B,L,H,E); IGN/layers/SelfAttention_Family.py:56-75.
+    dropout_p > 0: dropout on the attention probabilities inside the kernels, mask regenerated in the backward from `seed`."""
 
     @staticmethod
-    def forward(ctx, q, k, v, scale):
+    def forward(ctx, q, k, v, scale, dropout_p=0.0, seed=0):
         _need_gpu("attention", q, k, v)
         B, L, H, E = q.shape
         S = k.shape[1]
@@ -342,8 +378,15 @@ class AttentionFn(torch.autograd.Function):
         # "f16x3": two fp16 planes of power-of-two-scaled operands, three products (ign_attn_fwd_h3); needs the magnitude bounds
         ctx.h3 = (not ctx.bf16) and ATTN_MATH == "bf16x6" and GEMM_MATH == "f16x3" and E <= 64
         ctx.bounds = None
+        ctx.p, ctx.seed = float(dropout_p), int(seed)
         if ctx.h3:
             ctx.bounds = (tensor_bound(q), tensor_bound(k), tensor_bound(v))
+        if ctx.p > 0:
+            bq, bk, bv = ctx.bounds if ctx.h3 else (None, None, None)
+            _lib.check(L_.ign_attn_fwd_dropout(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), B, L, S, H, E, qb, ql, kb, kl, vb, vl,
+                                               float(scale), _stream(), _attn_math(ctx, E, False), _ptr(bq), _ptr(bk), _ptr(bv),
+                                               ctx.p, ctx.seed), "ign_attn_fwd_dropout")
+        elif ctx.h3:
             _lib.check(L_.ign_attn_fwd_h3(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), B, L, S, H, E, qb, ql, kb, kl, vb, vl,
                                           float(scale), _stream(), *[_ptr(t) for t in ctx.bounds]), "ign_attn_fwd_h3")
         else:
@@ -365,6 +408,16 @@ class AttentionFn(torch.autograd.Function):
         gv = torch.empty_like(gk)
         delta = torch.empty(B, H, L, device=q.device, dtype=torch.float32)
         (qb, ql), (kb, kl), (vb, vl) = _bl_strides(q, "q"), _bl_strides(k, "k"), _bl_strides(v, "v")
+        if ctx.p > 0:
+            gmax = _new_slot(q.device) if ctx.h3 else None
+            bnd = (*ctx.bounds, tensor_bound(gout)) if ctx.h3 else (None,) * 4
+            _lib.check(_lib.lib().ign_attn_bwd_dropout(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(gout), _ptr(gq), _ptr(gk),
+                                                       _ptr(gv), _ptr(delta), B, L, S, H, E, qb, ql, kb, kl, vb, vl, ctx.scale,
+                                                       _stream(), _attn_math(ctx, E, True), 0, 0, *[_ptr(t) for t in bnd], _ptr(gmax),
+                                                       ctx.p, ctx.seed), "ign_attn_bwd_dropout")
+            if ctx.h3:
+                return set_bound(gq, gmax), set_bound(gk, gmax), set_bound(gv, gmax), None, None, None
+            return gq, gk, gv, None, None, None
         if ctx.h3:
             gmax = _new_slot(q.device)            # max over |dq|, |dk|, |dv| (taken as they are stored): one bound for the three
             _lib.check(_lib.lib().ign_attn_bwd_h3(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(gout), _ptr(gq), _ptr(gk), _ptr(gv),
@@ -380,10 +433,16 @@ class AttentionFn(torch.autograd.Function):
         return gq, gk, gv, None
 
 
-def attention(q, k, v, scale):
-    out = AttentionFn.apply(q, k, v, scale)
+def attention(q, k, v, scale, dropout_p=0.0):
+    """dropout_p: attention dropout (callers pass p > 0 in training only); 0 takes the dropout-free kernels and draws nothing."""
+    if dropout_p == 0:
+        out = AttentionFn.apply(q, k, v, scale)
+        if GEMM_MATH == "f16x3" and ATTN_MATH == "bf16x6" and not torch.is_autocast_enabled() and q.shape[-1] <= 64:
+            set_bound(out, tensor_bound(v))    # a row of the output is a convex combination of rows of v (cached: no extra pass)
+        return out
+    out = AttentionFn.apply(q, k, v, scale, float(dropout_p), _dropout_seed(dropout_p))
     if GEMM_MATH == "f16x3" and ATTN_MATH == "bf16x6" and not torch.is_autocast_enabled() and q.shape[-1] <= 64:
-        set_bound(out, tensor_bound(v))        # a row of the output is a convex combination of rows of v (cached: no extra pass)
+        set_bound(out, tensor_bound(v) * dropout_threshold(dropout_p)[1])   # s times a convex combination of rows of v
     return out
 
 
@@ -393,7 +452,7 @@ class PackedAttentionFn(torch.autograd.Function):
     its output gradient without a stack / gather pass."""
 
     @staticmethod
-    def forward(ctx, qkv, scale):
+    def forward(ctx, qkv, scale, dropout_p=0.0, seed=0):
         _need_gpu("attention", qkv)
         qkv = qkv.contiguous()
         B, L, three, H, E = qkv.shape
@@ -405,8 +464,15 @@ class PackedAttentionFn(torch.autograd.Function):
         ctx.bf16 = torch.is_autocast_enabled()
         ctx.h3 = (not ctx.bf16) and GEMM_MATH == "f16x3"
         ctx.bound = None
+        ctx.p, ctx.seed = float(dropout_p), int(seed)
         if ctx.h3:
             ctx.bound = tensor_bound(qkv)             # one pass: a bound of the packed tensor bounds q, k and v alike
+        if ctx.p > 0:
+            bp = _ptr(ctx.bound) if ctx.h3 else None
+            _lib.check(L_.ign_attn_fwd_dropout(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), B, L, L, H, E, sb, sl, sb, sl, sb, sl,
+                                               float(scale), _stream(), _attn_math(ctx, E, False), bp, bp, bp, ctx.p, ctx.seed),
+                       "ign_attn_fwd_dropout")
+        elif ctx.h3:
             bp = _ptr(ctx.bound)
             _lib.check(L_.ign_attn_fwd_h3(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), B, L, L, H, E, sb, sl, sb, sl, sb, sl,
                                           float(scale), _stream(), bp, bp, bp), "ign_attn_fwd_h3")
@@ -427,6 +493,15 @@ class PackedAttentionFn(torch.autograd.Function):
         gqkv = torch.empty_like(qkv)
         delta = torch.empty(B, H, L, device=qkv.device, dtype=torch.float32)
         sb, sl = qkv.stride(0), qkv.stride(1)
+        if ctx.p > 0:
+            bp = _ptr(ctx.bound) if ctx.h3 else None
+            gmax = _new_slot(qkv.device) if ctx.h3 else None
+            _lib.check(_lib.lib().ign_attn_bwd_dropout(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(gout), _ptr(gqkv[:, :, 0]),
+                                                       _ptr(gqkv[:, :, 1]), _ptr(gqkv[:, :, 2]), _ptr(delta), B, L, L, H, E, sb, sl, sb,
+                                                       sl, sb, sl, ctx.scale, _stream(), _attn_math(ctx, E, True), sb, sl, bp, bp, bp,
+                                                       _ptr(tensor_bound(gout)) if ctx.h3 else None, _ptr(gmax), ctx.p, ctx.seed),
+                       "ign_attn_bwd_dropout")
+            return (set_bound(gqkv, gmax) if ctx.h3 else gqkv), None, None, None
         if ctx.h3:
             bp = _ptr(ctx.bound)
             gmax = _new_slot(qkv.device)          # max |dq|, |dk|, |dv|, taken by the kernels as they store: the projection's
@@ -442,14 +517,20 @@ class PackedAttentionFn(torch.autograd.Function):
         return gqkv, None
 
 
-def attention_packed(qkv, scale):
-    """softmax(scale q k^T) v for qkv (B, L, 3, H, E); the split-bf16 kernels cover E <= 64 (else the unpacked path)."""
+def attention_packed(qkv, scale, dropout_p=0.0):
+    """softmax(scale q k^T) v for qkv (B, L, 3, H, E); the split-bf16 kernels cover E <= 64 (else the unpacked path).
+    dropout_p as in `attention`."""
     E = qkv.shape[-1]
     if ATTN_MATH != "bf16x6" or E > 64:
-        return attention(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], scale)
-    out = PackedAttentionFn.apply(qkv, scale)
+        return attention(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], scale, dropout_p)
+    if dropout_p == 0:
+        out = PackedAttentionFn.apply(qkv, scale)
+        if GEMM_MATH == "f16x3" and not torch.is_autocast_enabled():
+            set_bound(out, tensor_bound(qkv))  # convex combinations of rows of v: bounded by the packed tensor's bound (cached)
+        return out
+    out = PackedAttentionFn.apply(qkv, scale, float(dropout_p), _dropout_seed(dropout_p))
     if GEMM_MATH == "f16x3" and not torch.is_autocast_enabled():
-        set_bound(out, tensor_bound(qkv))      # convex combinations of rows of v: bounded by the packed tensor's bound (cached)
+        set_bound(out, tensor_bound(qkv) * dropout_threshold(dropout_p)[1])   # s times convex combinations of rows of v
     return out
 
 

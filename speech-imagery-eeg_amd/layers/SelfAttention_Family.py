@@ -1,7 +1,7 @@
 """Attention of the Transformer-encoder baseline (IGN/layers/SelfAttention_Family.py:48-75,179-213).
 
-``FullAttention`` is softmax(scale * Q K^T) V without mask and with dropout 0 on every live path
-(``mask_flag=False``: IGN/model/Transformer.py:30).  The reference materialises the (B,H,L,S) score tensor
+``FullAttention`` is dropout(softmax(scale * Q K^T)) V without mask (``mask_flag=False``: IGN/model/Transformer.py:30); the
+dropout on the probabilities runs inside the fused kernels in training.  The reference materialises the (B,H,L,S) score tensor
 (8.2 GB per layer at the benchmark shape); here the core runs as a fused flash-style fp32-MFMA kernel
 (``ign_attn_fwd/bwd``) that never stores the scores.  The Prob/DS/Reformer/TwoStage variants of the reference file are
 not used by any live path and are not rebuilt.
@@ -24,10 +24,10 @@ class FullAttention(nn.Module):
     def forward(self, queries, keys, values, attn_mask, tau=None, delta=None):
         B, L, H, E = queries.shape
         scale = self.scale or 1. / sqrt(E)
-        if self.mask_flag or self.output_attention or (self.training and self.dropout.p > 0):
-            raise NotImplementedError("causal mask / attention-map output / attention dropout are not on the "
-                                      "classification path (mask_flag=False, dropout 0)")
-        return ops.attention(queries, keys, values, scale), None
+        if self.mask_flag or self.output_attention:
+            raise NotImplementedError("causal mask / attention-map output are not on the classification path (mask_flag=False)")
+        # dropout(softmax(...)) of the reference runs inside the fused kernels (ign_attn_*_dropout)
+        return ops.attention(queries, keys, values, scale, dropout_p=self.dropout.p if self.training else 0.0), None
 
 
 class AttentionLayer(nn.Module):

@@ -203,7 +203,8 @@ def _encoder_layer_forward(layer, x, n_heads):
     B, S, d = x.shape
     sa = layer.self_attn
     qkv = ops.linear(x, sa.in_proj_weight, sa.in_proj_bias).view(B, S, 3, n_heads, d // n_heads)
-    o = ops.attention_packed(qkv, 1.0 / math.sqrt(d // n_heads))      # gradients land in one packed buffer
+    # gradients land in one packed buffer; self_attn's dropout on the probabilities runs inside the kernels in training
+    o = ops.attention_packed(qkv, 1.0 / math.sqrt(d // n_heads), dropout_p=sa.dropout if layer.training else 0.0)
     a = ops.linear(o.reshape(B, S, d), sa.out_proj.weight, sa.out_proj.bias)
     x = ops.layer_norm(x, layer.norm1, residual=layer.dropout1(a))
     u = ops.linear(x, layer.linear1.weight, layer.linear1.bias)
