@@ -235,6 +235,22 @@ int ign_attn_bwd_dropout(const float* q, const float* k, const float* v, const f
  * debugging infrastructure.                                                                                                   */
 int ign_attn_dropout_mask(unsigned char* keep, int B, int H, int L, int S, float p, unsigned long long seed, void* stream);
 
+/* Attention map: A = dropout(softmax(scale Q K^T)), the (B, H, L, S) `attn` of IGN/layers/SelfAttention_Family.py:56-75 with
+ * output_attention=True, recomputed from q, k and the lse a forward call saved:
+ *   attn[((b H + h) L + i) S + j] = exp(scale s_ij - lse[b, h, i]) * keep(b, h, i, j) * s      (fp32, contiguous, 64-bit offsets)
+ * s_ij is the score in the arithmetic `math` (IGN_ATTN_MATH_*, as ign_attn_fwd_dropout; BF16 and H3 need E <= 64; bq / bk are
+ * read for H3 only, and must be the forward's bounds: the h3 operand scales come from them).  Pass the forward's q, k, scale,
+ * math, p and seed: keep and s are the mask and scale of ign_dropout.h above, so the map is the one the forward applied
+ * (p = 0: no mask, s = 1).  With the fp32-accurate arithmetics (F32, X6, H3) a row sums to s * (kept mass) at fp32 rounding;
+ * BF16 rounds q and k to bf16 exactly as the forward does.  q, k: the layouts and strides of ign_attn_fwd (16-byte aligned).
+ * Errors before any launch: a null pointer, bad dimensions or strides, p outside [0, 1), an unknown `math`, H3 without bounds
+ * -> IGN_E_ARG; E not in {16, 32, 64, 128}, or E > 64 with BF16 / H3 -> IGN_E_UNSUP.  No gradient flows through the map.     */
+int ign_attn_probs(const float* q, const float* k, const float* lse, float* attn,
+                   int B, int L, int S, int H, int E,
+                   long long q_sb, long long q_sl, long long k_sb, long long k_sl,
+                   float scale, void* stream, int math, const float* bq, const float* bk,
+                   float p, unsigned long long seed);
+
 /* Skinny expert-head GEMM  out[b,n] = sum_f X[b,f] W[n,f] (+ bias[n]),  N <= 16 classes, F % 4 == 0, row pitch ldx.
  * Replaces nn.Linear at IGN/model/Shapelet.py:171,200 (SBM head), IGN/model/Transformer.py:72,109,
  * IGN/model/FullyConvNet.py:50,58.  Backward: gX (B,ldx) and/or gW (N,F), gbias (N) (any may be NULL); sums over the

@@ -56,6 +56,7 @@ SIGNATURES = {
     "ign_attn_bwd_dropout": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ll, ll, ll, ll, ll, ll, cf, vp, ci, ll,
                                   ll, vp, vp, vp, vp, vp, cf, ctypes.c_ulonglong]),
     "ign_attn_dropout_mask": (ci, [vp, ci, ci, ci, ci, cf, ctypes.c_ulonglong, vp]),
+    "ign_attn_probs": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ll, ll, ll, ll, cf, vp, ci, vp, vp, cf, ctypes.c_ulonglong]),
     "ign_head_fwd": (ci, [vp, vp, vp, vp, ci, ci, ci, ll, vp]),
     "ign_head_bwd": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ll, vp]),
     "ign_gate_fwd": (ci, [vp, vp, vp, vp, ci, ci, cf, ci, vp]),

@@ -358,10 +358,11 @@ def _attn_math(ctx, E, bwd):
 
 class AttentionFn(torch.autograd.Function):
     """softmax(scale * Q K^T) V with q (B,L,H,E), k/v (B,S,H,E) -> (B,L,H,E); IGN/layers/SelfAttention_Family.py:56-75.
-    dropout_p > 0: dropout on the attention probabilities inside the kernels, mask regenerated in the backward from `seed`."""
+    dropout_p > 0: dropout on the attention probabilities inside the kernels, mask regenerated in the backward from `seed`.
+    need_weights: also the (B,H,L,S) map dropout(softmax(scale * Q K^T)) of this call (ign_attn_probs), not differentiable."""
 
     @staticmethod
-    def forward(ctx, q, k, v, scale, dropout_p=0.0, seed=0):
+    def forward(ctx, q, k, v, scale, dropout_p=0.0, seed=0, need_weights=False):
         _need_gpu("attention", q, k, v)
         B, L, H, E = q.shape
         S = k.shape[1]
@@ -395,10 +396,21 @@ class AttentionFn(torch.autograd.Function):
                            _stream()), "ign_attn_fwd")
         ctx.save_for_backward(q, k, v, out, lse)
         ctx.scale = float(scale)
-        return out
+        if not need_weights:
+            return out
+        # the map of this call: same q / k (after `fix`), lse, arithmetic, bounds and seed as the forward above
+        attn = torch.empty(B, H, L, S, device=q.device, dtype=torch.float32)
+        bq, bk = ctx.bounds[:2] if ctx.h3 else (None, None)
+        _lib.check(L_.ign_attn_probs(_ptr(q), _ptr(k), _ptr(lse), _ptr(attn), B, L, S, H, E, qb, ql, kb, kl, float(scale), _stream(),
+                                     _attn_math(ctx, E, False), _ptr(bq), _ptr(bk), ctx.p, ctx.seed), "ign_attn_probs")
+        ctx.mark_non_differentiable(attn)
+        ctx.set_materialize_grads(False)              # (else autograd would hand the backward a zero tensor of the map's size)
+        return out, attn
 
     @staticmethod
-    def backward(ctx, gout):
+    def backward(ctx, gout, gattn=None):
+        if gout is None:                              # need_weights: only `out` carries a gradient
+            return (None,) * 7
         q, k, v, out, lse = ctx.saved_tensors
         B, L, H, E = q.shape
         S = k.shape[1]
@@ -416,34 +428,40 @@ class AttentionFn(torch.autograd.Function):
                                                        _stream(), _attn_math(ctx, E, True), 0, 0, *[_ptr(t) for t in bnd], _ptr(gmax),
                                                        ctx.p, ctx.seed), "ign_attn_bwd_dropout")
             if ctx.h3:
-                return set_bound(gq, gmax), set_bound(gk, gmax), set_bound(gv, gmax), None, None, None
-            return gq, gk, gv, None, None, None
+                return set_bound(gq, gmax), set_bound(gk, gmax), set_bound(gv, gmax), None, None, None, None
+            return gq, gk, gv, None, None, None, None
         if ctx.h3:
             gmax = _new_slot(q.device)            # max over |dq|, |dk|, |dv| (taken as they are stored): one bound for the three
             _lib.check(_lib.lib().ign_attn_bwd_h3(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(gout), _ptr(gq), _ptr(gk), _ptr(gv),
                                                   _ptr(delta), B, L, S, H, E, qb, ql, kb, kl, vb, vl, ctx.scale, _stream(), 0, 0,
                                                   *[_ptr(t) for t in ctx.bounds], _ptr(tensor_bound(gout)), _ptr(gmax)),
                        "ign_attn_bwd_h3")
-            return set_bound(gq, gmax), set_bound(gk, gmax), set_bound(gv, gmax), None
+            return set_bound(gq, gmax), set_bound(gk, gmax), set_bound(gv, gmax), None, None, None, None
         # split-bf16 kernels up to E = 64 (E = 128 exceeds their register budget: the fp32-MFMA backward is faster there)
         bwd = (_lib.lib().ign_attn_bwd_bf16 if ctx.bf16 else
                _lib.lib().ign_attn_bwd_x6 if (ATTN_MATH == "bf16x6" and E <= 64) else _lib.lib().ign_attn_bwd)
         _lib.check(bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(gout), _ptr(gq), _ptr(gk), _ptr(gv), _ptr(delta),
                        B, L, S, H, E, qb, ql, kb, kl, vb, vl, ctx.scale, _stream()), "ign_attn_bwd")
-        return gq, gk, gv, None
+        return gq, gk, gv, None, None, None, None
 
 
-def attention(q, k, v, scale, dropout_p=0.0):
-    """dropout_p: attention dropout (callers pass p > 0 in training only); 0 takes the dropout-free kernels and draws nothing."""
+def attention(q, k, v, scale, dropout_p=0.0, need_weights=False):
+    """dropout_p: attention dropout (callers pass p > 0 in training only); 0 takes the dropout-free kernels and draws nothing.
+    need_weights=True returns (out, attn): attn (B, H, L, S) = dropout(softmax(scale * Q K^T)) of this very call (same operands,
+    arithmetic, lse and dropout seed as `out`; one seed per call).  attn is NOT differentiable: it does not require grad, and the
+    gradients of q, k, v are those of `out` alone.  need_weights=False launches, allocates and draws nothing more."""
     if dropout_p == 0:
-        out = AttentionFn.apply(q, k, v, scale)
+        res = AttentionFn.apply(q, k, v, scale, 0.0, 0, True) if need_weights else AttentionFn.apply(q, k, v, scale)
         if GEMM_MATH == "f16x3" and ATTN_MATH == "bf16x6" and not torch.is_autocast_enabled() and q.shape[-1] <= 64:
-            set_bound(out, tensor_bound(v))    # a row of the output is a convex combination of rows of v (cached: no extra pass)
-        return out
-    out = AttentionFn.apply(q, k, v, scale, float(dropout_p), _dropout_seed(dropout_p))
+            # a row of the output is a convex combination of rows of v (cached: no extra pass)
+            set_bound(res[0] if need_weights else res, tensor_bound(v))
+        return res
+    extra = (True,) if need_weights else ()
+    res = AttentionFn.apply(q, k, v, scale, float(dropout_p), _dropout_seed(dropout_p), *extra)
     if GEMM_MATH == "f16x3" and ATTN_MATH == "bf16x6" and not torch.is_autocast_enabled() and q.shape[-1] <= 64:
-        set_bound(out, tensor_bound(v) * dropout_threshold(dropout_p)[1])   # s times a convex combination of rows of v
-    return out
+        # s times a convex combination of rows of v
+        set_bound(res[0] if need_weights else res, tensor_bound(v) * dropout_threshold(dropout_p)[1])
+    return res
 
 
 class PackedAttentionFn(torch.autograd.Function):

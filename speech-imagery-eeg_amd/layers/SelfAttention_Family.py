@@ -3,7 +3,8 @@
 ``FullAttention`` is dropout(softmax(scale * Q K^T)) V without mask (``mask_flag=False``: IGN/model/Transformer.py:30); the
 dropout on the probabilities runs inside the fused kernels in training.  The reference materialises the (B,H,L,S) score tensor
 (8.2 GB per layer at the benchmark shape); here the core runs as a fused flash-style fp32-MFMA kernel
-(``ign_attn_fwd/bwd``) that never stores the scores.  The Prob/DS/Reformer/TwoStage variants of the reference file are
+(``ign_attn_fwd/bwd``) that never stores the scores.  With ``output_attention=True`` the map A = dropout(softmax(...)) of the same
+call is written by a kernel of its own (``ign_attn_probs``) and returned as the reference returns it; it carries no gradient.  The Prob/DS/Reformer/TwoStage variants of the reference file are
 not used by any live path and are not rebuilt.
 """
 from math import sqrt
@@ -24,10 +25,14 @@ class FullAttention(nn.Module):
     def forward(self, queries, keys, values, attn_mask, tau=None, delta=None):
         B, L, H, E = queries.shape
         scale = self.scale or 1. / sqrt(E)
-        if self.mask_flag or self.output_attention:
-            raise NotImplementedError("causal mask / attention-map output are not on the classification path (mask_flag=False)")
+        if self.mask_flag:
+            raise NotImplementedError("causal mask is not on the classification path (mask_flag=False)")
         # dropout(softmax(...)) of the reference runs inside the fused kernels (ign_attn_*_dropout)
-        return ops.attention(queries, keys, values, scale, dropout_p=self.dropout.p if self.training else 0.0), None
+        p = self.dropout.p if self.training else 0.0
+        if self.output_attention:
+            # (V, A) as the reference returns them; A (B, H, L, S) is recomputed by ign_attn_probs from the call's lse and seed
+            return ops.attention(queries, keys, values, scale, dropout_p=p, need_weights=True)
+        return ops.attention(queries, keys, values, scale, dropout_p=p), None
 
 
 class AttentionLayer(nn.Module):
