@@ -348,12 +348,61 @@ def _dropout_seed(p):
     return lo | (hi << 32)
 
 
-def _attn_math(ctx, E, bwd):
-    if ctx.h3:
-        return ATTN_MATH_H3
-    if ctx.bf16:
-        return ATTN_MATH_BF16
-    return ATTN_MATH_X6 if (ATTN_MATH == "bf16x6" and (E <= 64 or not bwd)) else ATTN_MATH_F32
+def _attn_arith(E, autocast, bwd):
+    """The arithmetic (ATTN_MATH_*) of the attention forward (bwd False) or backward at head width E: the one place that reads
+    ATTN_MATH and GEMM_MATH for attention."""
+    if autocast and E <= 64:
+        return ATTN_MATH_BF16     # inside an autocast region (the reference's default mode): operands rounded to bf16, one product
+    if ATTN_MATH == "bf16x6" and GEMM_MATH == "f16x3" and E <= 64:
+        return ATTN_MATH_H3       # two fp16 planes of power-of-two-scaled operands, three products; needs the magnitude bounds
+    if ATTN_MATH == "bf16x6" and (E <= 64 or not bwd):
+        # split-bf16 products on the bf16 matrix cores (fp32 accuracy); the backward up to E = 64 only (E = 128 exceeds its
+        # register budget: the fp32-MFMA backward is faster there)
+        return ATTN_MATH_X6
+    return ATTN_MATH_F32          # "f32": the fp32-MFMA kernels
+
+
+_ATTN_FWD = {ATTN_MATH_F32: "ign_attn_fwd", ATTN_MATH_X6: "ign_attn_fwd_x6", ATTN_MATH_BF16: "ign_attn_fwd_bf16"}
+_ATTN_BWD = {ATTN_MATH_F32: "ign_attn_bwd", ATTN_MATH_X6: "ign_attn_bwd_x6", ATTN_MATH_BF16: "ign_attn_bwd_bf16"}
+
+
+def _attn_fwd(ctx, q, k, v, out, lse):
+    """The forward launch of AttentionFn / PackedAttentionFn, from what their forward stored on ctx: arith, p, seed, scale, the
+    six batch / sequence strides and the three H3 bounds (None otherwise).  p = 0 keeps to the dropout-free entry points."""
+    B, L, H, E = q.shape
+    bq, bk, bv = (_ptr(b) for b in ctx.bounds)
+    if ctx.p > 0:
+        name, tail = "ign_attn_fwd_dropout", (ctx.arith, bq, bk, bv, ctx.p, ctx.seed)
+    elif ctx.arith == ATTN_MATH_H3:
+        name, tail = "ign_attn_fwd_h3", (bq, bk, bv)
+    else:
+        name, tail = _ATTN_FWD[ctx.arith], ()
+    _lib.check(getattr(_lib.lib(), name)(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), B, L, k.shape[1], H, E, *ctx.strides,
+                                         ctx.scale, _stream(), *tail), name)
+
+
+def _attn_bwd(ctx, q, k, v, out, lse, gout, gq, gk, gv, g_strides):
+    """The backward launch matching _attn_fwd; g_strides (0, 0): contiguous gradients, else the batch / sequence strides of a
+    packed gradient buffer.  -> the H3 gradients' bound (max |gq|, |gk|, |gv| as the kernels store them), else None."""
+    B, L, H, E = q.shape
+    arith = ctx.bwd_arith
+    delta = torch.empty(B, H, L, device=q.device, dtype=torch.float32)
+    gmax = bgo = None
+    if arith == ATTN_MATH_H3:
+        gmax = _new_slot(q.device)
+        bgo = tensor_bound(gout)
+    bounds = (*(_ptr(b) for b in ctx.bounds), _ptr(bgo), _ptr(gmax))
+    if ctx.p > 0:
+        name, tail = "ign_attn_bwd_dropout", (arith, *g_strides, *bounds, ctx.p, ctx.seed)
+    elif arith == ATTN_MATH_H3:
+        name, tail = "ign_attn_bwd_h3", (*g_strides, *bounds)
+    elif g_strides != (0, 0):
+        name, tail = "ign_attn_bwd_x6_strided", (*g_strides, 1 if arith == ATTN_MATH_BF16 else 0)
+    else:
+        name, tail = _ATTN_BWD[arith], ()
+    _lib.check(getattr(_lib.lib(), name)(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(gout), _ptr(gq), _ptr(gk), _ptr(gv),
+                                         _ptr(delta), B, L, k.shape[1], H, E, *ctx.strides, ctx.scale, _stream(), *tail), name)
+    return gmax
 
 
 class AttentionFn(torch.autograd.Function):
@@ -371,38 +420,20 @@ class AttentionFn(torch.autograd.Function):
         q, k, v = fix(q), fix(k), fix(v)
         out = torch.empty(B, L, H, E, device=q.device, dtype=torch.float32)
         lse = torch.empty(B, H, L, device=q.device, dtype=torch.float32)
-        (qb, ql), (kb, kl), (vb, vl) = _bl_strides(q, "q"), _bl_strides(k, "k"), _bl_strides(v, "v")
-        L_ = _lib.lib()
-        # "bf16x6": split-bf16 products on the bf16 matrix cores (fp32 accuracy); "f32": the fp32-MFMA kernel; inside an
-        # autocast region (the reference's default mode): operands rounded to bf16, one product
-        ctx.bf16 = torch.is_autocast_enabled() and E <= 64
-        # "f16x3": two fp16 planes of power-of-two-scaled operands, three products (ign_attn_fwd_h3); needs the magnitude bounds
-        ctx.h3 = (not ctx.bf16) and ATTN_MATH == "bf16x6" and GEMM_MATH == "f16x3" and E <= 64
-        ctx.bounds = None
-        ctx.p, ctx.seed = float(dropout_p), int(seed)
-        if ctx.h3:
-            ctx.bounds = (tensor_bound(q), tensor_bound(k), tensor_bound(v))
-        if ctx.p > 0:
-            bq, bk, bv = ctx.bounds if ctx.h3 else (None, None, None)
-            _lib.check(L_.ign_attn_fwd_dropout(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), B, L, S, H, E, qb, ql, kb, kl, vb, vl,
-                                               float(scale), _stream(), _attn_math(ctx, E, False), _ptr(bq), _ptr(bk), _ptr(bv),
-                                               ctx.p, ctx.seed), "ign_attn_fwd_dropout")
-        elif ctx.h3:
-            _lib.check(L_.ign_attn_fwd_h3(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), B, L, S, H, E, qb, ql, kb, kl, vb, vl,
-                                          float(scale), _stream(), *[_ptr(t) for t in ctx.bounds]), "ign_attn_fwd_h3")
-        else:
-            fwd = L_.ign_attn_fwd_bf16 if ctx.bf16 else (L_.ign_attn_fwd_x6 if ATTN_MATH == "bf16x6" else L_.ign_attn_fwd)
-            _lib.check(fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), B, L, S, H, E, qb, ql, kb, kl, vb, vl, float(scale),
-                           _stream()), "ign_attn_fwd")
+        ctx.strides = (*_bl_strides(q, "q"), *_bl_strides(k, "k"), *_bl_strides(v, "v"))
+        autocast = torch.is_autocast_enabled()
+        ctx.arith, ctx.bwd_arith = _attn_arith(E, autocast, False), _attn_arith(E, autocast, True)
+        ctx.p, ctx.seed, ctx.scale = float(dropout_p), int(seed), float(scale)
+        ctx.bounds = (tensor_bound(q), tensor_bound(k), tensor_bound(v)) if ctx.arith == ATTN_MATH_H3 else (None,) * 3
+        _attn_fwd(ctx, q, k, v, out, lse)
         ctx.save_for_backward(q, k, v, out, lse)
-        ctx.scale = float(scale)
         if not need_weights:
             return out
         # the map of this call: same q / k (after `fix`), lse, arithmetic, bounds and seed as the forward above
         attn = torch.empty(B, H, L, S, device=q.device, dtype=torch.float32)
-        bq, bk = ctx.bounds[:2] if ctx.h3 else (None, None)
-        _lib.check(L_.ign_attn_probs(_ptr(q), _ptr(k), _ptr(lse), _ptr(attn), B, L, S, H, E, qb, ql, kb, kl, float(scale), _stream(),
-                                     _attn_math(ctx, E, False), _ptr(bq), _ptr(bk), ctx.p, ctx.seed), "ign_attn_probs")
+        _lib.check(_lib.lib().ign_attn_probs(_ptr(q), _ptr(k), _ptr(lse), _ptr(attn), B, L, S, H, E, *ctx.strides[:4], ctx.scale,
+                                             _stream(), ctx.arith, _ptr(ctx.bounds[0]), _ptr(ctx.bounds[1]), ctx.p, ctx.seed),
+                   "ign_attn_probs")
         ctx.mark_non_differentiable(attn)
         ctx.set_materialize_grads(False)              # (else autograd would hand the backward a zero tensor of the map's size)
         return out, attn
@@ -412,37 +443,22 @@ class AttentionFn(torch.autograd.Function):
         if gout is None:                              # need_weights: only `out` carries a gradient
             return (None,) * 7
         q, k, v, out, lse = ctx.saved_tensors
-        B, L, H, E = q.shape
-        S = k.shape[1]
         gout = gout.contiguous()
-        gq = torch.empty(B, L, H, E, device=q.device, dtype=torch.float32)
-        gk = torch.empty(B, S, H, E, device=q.device, dtype=torch.float32)
+        gq = torch.empty(q.shape, device=q.device, dtype=torch.float32)
+        gk = torch.empty(k.shape, device=q.device, dtype=torch.float32)
         gv = torch.empty_like(gk)
-        delta = torch.empty(B, H, L, device=q.device, dtype=torch.float32)
-        (qb, ql), (kb, kl), (vb, vl) = _bl_strides(q, "q"), _bl_strides(k, "k"), _bl_strides(v, "v")
-        if ctx.p > 0:
-            gmax = _new_slot(q.device) if ctx.h3 else None
-            bnd = (*ctx.bounds, tensor_bound(gout)) if ctx.h3 else (None,) * 4
-            _lib.check(_lib.lib().ign_attn_bwd_dropout(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(gout), _ptr(gq), _ptr(gk),
-                                                       _ptr(gv), _ptr(delta), B, L, S, H, E, qb, ql, kb, kl, vb, vl, ctx.scale,
-                                                       _stream(), _attn_math(ctx, E, True), 0, 0, *[_ptr(t) for t in bnd], _ptr(gmax),
-                                                       ctx.p, ctx.seed), "ign_attn_bwd_dropout")
-            if ctx.h3:
-                return set_bound(gq, gmax), set_bound(gk, gmax), set_bound(gv, gmax), None, None, None, None
-            return gq, gk, gv, None, None, None, None
-        if ctx.h3:
-            gmax = _new_slot(q.device)            # max over |dq|, |dk|, |dv| (taken as they are stored): one bound for the three
-            _lib.check(_lib.lib().ign_attn_bwd_h3(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(gout), _ptr(gq), _ptr(gk), _ptr(gv),
-                                                  _ptr(delta), B, L, S, H, E, qb, ql, kb, kl, vb, vl, ctx.scale, _stream(), 0, 0,
-                                                  *[_ptr(t) for t in ctx.bounds], _ptr(tensor_bound(gout)), _ptr(gmax)),
-                       "ign_attn_bwd_h3")
-            return set_bound(gq, gmax), set_bound(gk, gmax), set_bound(gv, gmax), None, None, None, None
-        # split-bf16 kernels up to E = 64 (E = 128 exceeds their register budget: the fp32-MFMA backward is faster there)
-        bwd = (_lib.lib().ign_attn_bwd_bf16 if ctx.bf16 else
-               _lib.lib().ign_attn_bwd_x6 if (ATTN_MATH == "bf16x6" and E <= 64) else _lib.lib().ign_attn_bwd)
-        _lib.check(bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(gout), _ptr(gq), _ptr(gk), _ptr(gv), _ptr(delta),
-                       B, L, S, H, E, qb, ql, kb, kl, vb, vl, ctx.scale, _stream()), "ign_attn_bwd")
+        gmax = _attn_bwd(ctx, q, k, v, out, lse, gout, gq, gk, gv, (0, 0))
+        if gmax is not None:                          # one bound for the three
+            gq, gk, gv = set_bound(gq, gmax), set_bound(gk, gmax), set_bound(gv, gmax)
         return gq, gk, gv, None, None, None, None
+
+
+def _attn_out_bound(out, src, dropout_p):
+    """f16x3: attach to `out` the bound of v taken from `src` (v, or the packed qkv whose bound bounds v; cached: no extra pass):
+    a row of the output is a convex combination of rows of v, times the dropout scale s when p > 0."""
+    if _attn_arith(out.shape[-1], torch.is_autocast_enabled(), False) == ATTN_MATH_H3:
+        b = tensor_bound(src)
+        set_bound(out, b if dropout_p == 0 else b * dropout_threshold(dropout_p)[1])
 
 
 def attention(q, k, v, scale, dropout_p=0.0, need_weights=False):
@@ -450,17 +466,9 @@ def attention(q, k, v, scale, dropout_p=0.0, need_weights=False):
     need_weights=True returns (out, attn): attn (B, H, L, S) = dropout(softmax(scale * Q K^T)) of this very call (same operands,
     arithmetic, lse and dropout seed as `out`; one seed per call).  attn is NOT differentiable: it does not require grad, and the
     gradients of q, k, v are those of `out` alone.  need_weights=False launches, allocates and draws nothing more."""
-    if dropout_p == 0:
-        res = AttentionFn.apply(q, k, v, scale, 0.0, 0, True) if need_weights else AttentionFn.apply(q, k, v, scale)
-        if GEMM_MATH == "f16x3" and ATTN_MATH == "bf16x6" and not torch.is_autocast_enabled() and q.shape[-1] <= 64:
-            # a row of the output is a convex combination of rows of v (cached: no extra pass)
-            set_bound(res[0] if need_weights else res, tensor_bound(v))
-        return res
-    extra = (True,) if need_weights else ()
-    res = AttentionFn.apply(q, k, v, scale, float(dropout_p), _dropout_seed(dropout_p), *extra)
-    if GEMM_MATH == "f16x3" and ATTN_MATH == "bf16x6" and not torch.is_autocast_enabled() and q.shape[-1] <= 64:
-        # s times a convex combination of rows of v
-        set_bound(res[0] if need_weights else res, tensor_bound(v) * dropout_threshold(dropout_p)[1])
+    seed = 0 if dropout_p == 0 else _dropout_seed(dropout_p)
+    res = AttentionFn.apply(q, k, v, scale, float(dropout_p), seed, need_weights)
+    _attn_out_bound(res[0] if need_weights else res, v, dropout_p)
     return res
 
 
@@ -474,81 +482,37 @@ class PackedAttentionFn(torch.autograd.Function):
         _need_gpu("attention", qkv)
         qkv = qkv.contiguous()
         B, L, three, H, E = qkv.shape
-        q, k, v = qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2]
         out = torch.empty(B, L, H, E, device=qkv.device, dtype=torch.float32)
         lse = torch.empty(B, H, L, device=qkv.device, dtype=torch.float32)
-        sb, sl = qkv.stride(0), qkv.stride(1)
-        L_ = _lib.lib()
-        ctx.bf16 = torch.is_autocast_enabled()
-        ctx.h3 = (not ctx.bf16) and GEMM_MATH == "f16x3"
-        ctx.bound = None
-        ctx.p, ctx.seed = float(dropout_p), int(seed)
-        if ctx.h3:
-            ctx.bound = tensor_bound(qkv)             # one pass: a bound of the packed tensor bounds q, k and v alike
-        if ctx.p > 0:
-            bp = _ptr(ctx.bound) if ctx.h3 else None
-            _lib.check(L_.ign_attn_fwd_dropout(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), B, L, L, H, E, sb, sl, sb, sl, sb, sl,
-                                               float(scale), _stream(), _attn_math(ctx, E, False), bp, bp, bp, ctx.p, ctx.seed),
-                       "ign_attn_fwd_dropout")
-        elif ctx.h3:
-            bp = _ptr(ctx.bound)
-            _lib.check(L_.ign_attn_fwd_h3(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), B, L, L, H, E, sb, sl, sb, sl, sb, sl,
-                                          float(scale), _stream(), bp, bp, bp), "ign_attn_fwd_h3")
-        else:
-            fwd = L_.ign_attn_fwd_bf16 if ctx.bf16 else L_.ign_attn_fwd_x6
-            _lib.check(fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), B, L, L, H, E, sb, sl, sb, sl, sb, sl, float(scale),
-                           _stream()), "ign_attn_fwd_x6")
+        ctx.strides = (qkv.stride(0), qkv.stride(1)) * 3
+        autocast = torch.is_autocast_enabled()
+        ctx.arith, ctx.bwd_arith = _attn_arith(E, autocast, False), _attn_arith(E, autocast, True)
+        ctx.p, ctx.seed, ctx.scale = float(dropout_p), int(seed), float(scale)
+        bound = tensor_bound(qkv) if ctx.arith == ATTN_MATH_H3 else None   # one pass: it bounds q, k and v alike
+        ctx.bounds = (bound,) * 3
+        _attn_fwd(ctx, qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], out, lse)
         ctx.save_for_backward(qkv, out, lse)
-        ctx.scale = float(scale)
         return out
 
     @staticmethod
     def backward(ctx, gout):
         qkv, out, lse = ctx.saved_tensors
-        B, L, three, H, E = qkv.shape
-        q, k, v = qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2]
         gout = gout.contiguous()
         gqkv = torch.empty_like(qkv)
-        delta = torch.empty(B, H, L, device=qkv.device, dtype=torch.float32)
-        sb, sl = qkv.stride(0), qkv.stride(1)
-        if ctx.p > 0:
-            bp = _ptr(ctx.bound) if ctx.h3 else None
-            gmax = _new_slot(qkv.device) if ctx.h3 else None
-            _lib.check(_lib.lib().ign_attn_bwd_dropout(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(gout), _ptr(gqkv[:, :, 0]),
-                                                       _ptr(gqkv[:, :, 1]), _ptr(gqkv[:, :, 2]), _ptr(delta), B, L, L, H, E, sb, sl, sb,
-                                                       sl, sb, sl, ctx.scale, _stream(), _attn_math(ctx, E, True), sb, sl, bp, bp, bp,
-                                                       _ptr(tensor_bound(gout)) if ctx.h3 else None, _ptr(gmax), ctx.p, ctx.seed),
-                       "ign_attn_bwd_dropout")
-            return (set_bound(gqkv, gmax) if ctx.h3 else gqkv), None, None, None
-        if ctx.h3:
-            bp = _ptr(ctx.bound)
-            gmax = _new_slot(qkv.device)          # max |dq|, |dk|, |dv|, taken by the kernels as they store: the projection's
-            _lib.check(_lib.lib().ign_attn_bwd_h3(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(gout), _ptr(gqkv[:, :, 0]),
-                                                  _ptr(gqkv[:, :, 1]), _ptr(gqkv[:, :, 2]), _ptr(delta), B, L, L, H, E, sb, sl, sb, sl,
-                                                  sb, sl, ctx.scale, _stream(), sb, sl, bp, bp, bp, _ptr(tensor_bound(gout)),
-                                                  _ptr(gmax)), "ign_attn_bwd_h3")
-            return set_bound(gqkv, gmax), None    # backward GEMMs scale their dL/dy operand by it without a pass over it
-        _lib.check(_lib.lib().ign_attn_bwd_x6_strided(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(gout),
-                                                      _ptr(gqkv[:, :, 0]), _ptr(gqkv[:, :, 1]), _ptr(gqkv[:, :, 2]), _ptr(delta),
-                                                      B, L, L, H, E, sb, sl, sb, sl, sb, sl, ctx.scale, _stream(), sb, sl,
-                                                      1 if ctx.bf16 else 0), "ign_attn_bwd_x6_strided")
-        return gqkv, None
+        gmax = _attn_bwd(ctx, qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], out, lse, gout, gqkv[:, :, 0], gqkv[:, :, 1], gqkv[:, :, 2],
+                         ctx.strides[:2])
+        # the projection's backward GEMMs scale their dL/dy operand by the H3 bound without a pass over it
+        return (gqkv if gmax is None else set_bound(gqkv, gmax)), None, None, None
 
 
 def attention_packed(qkv, scale, dropout_p=0.0):
-    """softmax(scale q k^T) v for qkv (B, L, 3, H, E); the split-bf16 kernels cover E <= 64 (else the unpacked path).
-    dropout_p as in `attention`."""
-    E = qkv.shape[-1]
-    if ATTN_MATH != "bf16x6" or E > 64:
+    """softmax(scale q k^T) v for qkv (B, L, 3, H, E); dropout_p as in `attention`.  The packed kernels are the split ones: where
+    the configuration runs the fp32-MFMA backward outside autocast (ATTN_MATH "f32", or E > 64), the unpacked path."""
+    if _attn_arith(qkv.shape[-1], False, True) == ATTN_MATH_F32:
         return attention(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], scale, dropout_p)
-    if dropout_p == 0:
-        out = PackedAttentionFn.apply(qkv, scale)
-        if GEMM_MATH == "f16x3" and not torch.is_autocast_enabled():
-            set_bound(out, tensor_bound(qkv))  # convex combinations of rows of v: bounded by the packed tensor's bound (cached)
-        return out
-    out = PackedAttentionFn.apply(qkv, scale, float(dropout_p), _dropout_seed(dropout_p))
-    if GEMM_MATH == "f16x3" and not torch.is_autocast_enabled():
-        set_bound(out, tensor_bound(qkv) * dropout_threshold(dropout_p)[1])   # s times convex combinations of rows of v
+    seed = 0 if dropout_p == 0 else _dropout_seed(dropout_p)
+    out = PackedAttentionFn.apply(qkv, scale, float(dropout_p), seed)
+    _attn_out_bound(out, qkv, dropout_p)
     return out
 
 

@@ -130,3 +130,40 @@ def test_new_dropout_symbols_are_declared_bound_and_exported():
     h = ctypes.CDLL(_lib.lib_path())
     for n in names:
         assert hasattr(h, n), n
+
+
+# (ATTN_MATH, GEMM_MATH, autocast) -> the attention arithmetic at E = 16, 32, 64, 128: (forward, backward)
+_ARITH_TABLE = {
+    ("bf16x6", "f16x3", False): ("H3 H3 H3 X6", "H3 H3 H3 F32"),
+    ("bf16x6", "f16x3", True): ("BF16 BF16 BF16 X6", "BF16 BF16 BF16 F32"),
+    ("bf16x6", "bf16x6", False): ("X6 X6 X6 X6", "X6 X6 X6 F32"),
+    ("bf16x6", "bf16x6", True): ("BF16 BF16 BF16 X6", "BF16 BF16 BF16 F32"),
+    ("f32", "f16x3", False): ("F32 F32 F32 F32", "F32 F32 F32 F32"),
+    ("f32", "f16x3", True): ("BF16 BF16 BF16 F32", "BF16 BF16 BF16 F32"),
+    ("f32", "bf16x6", False): ("F32 F32 F32 F32", "F32 F32 F32 F32"),
+    ("f32", "bf16x6", True): ("BF16 BF16 BF16 F32", "BF16 BF16 BF16 F32"),
+}
+
+
+def test_attention_arithmetic_rule_and_packed_fallback(monkeypatch):
+    """ops._attn_arith, the one statement of which attention kernels run, against the table above; and attention_packed takes
+    the unpacked path exactly for ATTN_MATH != "bf16x6" or E > 64 (there the CPU tensor reaches the monkeypatched `attention`;
+    the packed path refuses it before any launch)."""
+    import torch
+    import speech_imagery_eeg_amd  # noqa: F401
+    from ign_hip import ops, _lib
+    monkeypatch.setattr(ops, "attention", lambda *a: "unpacked")
+    for (attn_math, gemm_math, autocast), rows in _ARITH_TABLE.items():
+        monkeypatch.setattr(ops, "ATTN_MATH", attn_math)
+        monkeypatch.setattr(ops, "GEMM_MATH", gemm_math)
+        for bwd, row in enumerate(rows):
+            for E, want in zip((16, 32, 64, 128), row.split()):
+                got = ops._attn_arith(E, autocast, bool(bwd))
+                assert got == getattr(ops, "ATTN_MATH_" + want), (attn_math, gemm_math, autocast, E, bwd, want, got)
+        for E in (16, 32, 64, 128):
+            qkv = torch.zeros(1, 4, 3, 1, E)
+            if attn_math != "bf16x6" or E > 64:
+                assert ops.attention_packed(qkv, 1.0) == "unpacked"
+            else:
+                with pytest.raises(_lib.IgnError, match="no CPU fallback"):
+                    ops.attention_packed(qkv, 1.0)
