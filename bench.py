@@ -2,7 +2,7 @@
 """Headline benchmark: epochs/sec of IGN 3-class training on synthetic CHISCO-shaped EEG
 (B=256 per GPU, C=122, T=1000; N_train=8192 samples per epoch) -- BASELINE.json's metric.
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1: one rank per GPU over RCCL.  Either the caller starts the ranks (`python -m torch.distributed.run --nproc-per-node N
 bench.py --gpus N ...`: WORLD_SIZE / RANK / LOCAL_RANK come from the environment) or, when WORLD_SIZE is not set, this
@@ -12,9 +12,11 @@ and exits with the child's code.
 A step = one optimizer step of the training hot path (IGN/exp/experiment_classification.py:313-343) on one batch per
 rank: instance norm -> shapelet bank (HIP) -> SBM head || FCN expert (implicit-GEMM conv kernels, second HIP stream) ->
 gini gate -> 3-term loss -> backward (HIP shapelet / conv backward) -> gradient all-reduce over RCCL (N>1) -> Adam.
-Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.  At N = 1 the default run also times
-the two baselines of BASELINE.json configs 3 / 4 on the same tensors (`baselines` object) and the CPU oracle of each
-workload on the host cores (`cpu_baseline`).
+Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.  A plain run does only what the headline
+needs: set-up, warm-up, the K timed steps, --dump-outputs, the result line (with the `roofline` of the timed region).
+`--full` adds the passes that take runs of their own: the fp32-MFMA convolution leg, the serial pass behind
+`roofline.isolated`, and at N = 1 the two baselines of BASELINE.json configs 3 / 4 on the same tensors (`baselines` object),
+the harness leg (`harness`) and the CPU oracle of each workload on the host cores (`cpu_baseline`).
 """
 import argparse
 import json
@@ -542,17 +544,21 @@ def main():
     ap.add_argument("--steps", type=int, default=32)
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--batch", type=int, default=256, help="per-GPU batch (weak scaling)")
-    ap.add_argument("--alt-steps", type=int, default=16, help="steps of the second timed region that runs the FCN convolution "
-                    "GEMMs on the fp32-MFMA kernels instead of the split-bf16 ones (0 = skip)")
-    ap.add_argument("--iso-steps", type=int, default=8, help="steps of the serial (one-stream) pass that measures isolated "
-                    "kernel durations for the roofline object")
-    ap.add_argument("--cpu-sample", type=int, default=8, help="samples per step of the IGN CPU baseline (1 warm-up + 3 timed "
-                    "steps; 0 = skip every CPU baseline)")
-    ap.add_argument("--baseline-steps", type=int, default=6, help="timed steps of each baseline (configs 3 / 4) appended to the "
-                    "default single-GPU IGN run as the `baselines` object (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the passes sized by the five options below (the fp32-MFMA convolution "
+                         "leg, the serial pass of roofline.isolated, the baselines of configs 3 / 4, the harness leg, the CPU "
+                         "baselines); without it, those options do nothing")
+    ap.add_argument("--alt-steps", type=int, default=16, help="--full: steps of the second timed region that runs the FCN "
+                    "convolution GEMMs on the fp32-MFMA kernels instead of the split-bf16 ones (0 = skip)")
+    ap.add_argument("--iso-steps", type=int, default=8, help="--full: steps of the serial (one-stream) pass that measures "
+                    "isolated kernel durations for the roofline object")
+    ap.add_argument("--cpu-sample", type=int, default=8, help="--full: samples per step of the IGN CPU baseline (1 warm-up + 3 "
+                    "timed steps; 0 = skip every CPU baseline)")
+    ap.add_argument("--baseline-steps", type=int, default=6, help="--full: timed steps of each baseline (configs 3 / 4) "
+                    "appended to the single-GPU IGN run as the `baselines` object (0 = skip)")
     ap.add_argument("--harness-epochs", type=int, default=2,
-                    help="timed epochs of the harness leg (Experiment.train_one_epoch on --data SYNTH with per-step H2D copies; "
-                         "single GPU, default config only; 0 = skip)")
+                    help="--full: timed epochs of the harness leg (Experiment.train_one_epoch on --data SYNTH with per-step H2D "
+                         "copies; single GPU, default config only; 0 = skip)")
     ap.add_argument("--graph", action="store_true",
                     help="replay the whole step (fwd + loss + bwd + Adam) as one captured hipGraph (single GPU; pays off in "
                          "launch-bound regimes such as --batch 32, the UEA setting of run_uea.sh)")
@@ -659,12 +665,12 @@ def main():
         dumped = dump_outputs(b, last, args.dump_outputs)
 
     if args.config != "ign":
-        res_b = baseline_result(b, _lib, args.steps, dt, last, args.cpu_sample)
+        res_b = baseline_result(b, _lib, args.steps, dt, last, args.cpu_sample if args.full else 0)
 
     # The same K steps with the convolution GEMMs on the fp32-MFMA kernels (v_mfma_f32_32x32x2_f32), reported next to the
     # headline so that both arithmetic choices are measured in one run (results agree to ~1e-6).
     alt = None
-    if args.config == "ign" and args.alt_steps > 0 and not args.planted:
+    if args.full and args.config == "ign" and args.alt_steps > 0 and not args.planted:
         from ign_hip import fcn as _fcn_alt
         if _fcn_alt.CONV_MATH in ("bf16x6", "f16x3"):
             _was_math = _fcn_alt.CONV_MATH
@@ -683,7 +689,7 @@ def main():
     # a kernel's event bracket also contains the time it shared the CUs with the other expert.  A short serial pass
     # (same step, one stream) right after the timed region gives the isolated durations the roofline fractions refer to.
     iso = {}
-    if args.config == "ign":
+    if args.full and args.config == "ign":
         from models.InterpGN import InterpGN as _IGN
         was = _IGN.expert_streams
         _IGN.expert_streams = False
@@ -723,7 +729,7 @@ def main():
             res["metric"] += f" [deep expert {args.dnn}]"
         common = {"per_gpu_batch": B, "global_batch": B * world, "samples_per_epoch": N_TRAIN,
                   "data": "resident in HBM (no H2D copy in the timed region; the harness path with the per-step copy is the "
-                          "`harness` object)",
+                          "`harness` object of --full)",
                   "parallelism": f"dp{world}", "final_loss": float(last), "hipgraph": bool(b.use_graph)}
         if world > 1 or solo_pg:
             common["collective"] = {"backend": "gloo (rehearsal)" if rehearsal else "nccl (RCCL over xGMI)", "ranks": world,
@@ -821,8 +827,8 @@ def main():
             if "cpu_baseline" in res_b:
                 res["cpu_baseline"] = res_b["cpu_baseline"]
 
-    # ---- configs 3 / 4 in the same run (single GPU, default invocation): a few timed steps each, own roofline + CPU oracle
-    if world == 1 and args.config == "ign" and args.baseline_steps > 0 and not args.planted and args.dnn == "FCN" \
+    # ---- configs 3 / 4 in the same run (single GPU, --full): a few timed steps each, own roofline + CPU oracle
+    if args.full and world == 1 and args.config == "ign" and args.baseline_steps > 0 and not args.planted and args.dnn == "FCN" \
             and args.groups == "4x5" and not b.amp:
         del b
         torch.cuda.empty_cache()
@@ -840,8 +846,8 @@ def main():
             torch.cuda.empty_cache()
         res["baselines"] = baselines
 
-    if rank == 0 and world == 1 and args.config == "ign" and args.harness_epochs > 0 and args.shape == "ch" and B == 256 \
-            and args.groups == "4x5" and args.dnn == "FCN" and not args.planted and args.precision == "fp32":
+    if args.full and rank == 0 and world == 1 and args.config == "ign" and args.harness_epochs > 0 and args.shape == "ch" \
+            and B == 256 and args.groups == "4x5" and args.dnn == "FCN" and not args.planted and args.precision == "fp32":
         log("harness leg ...")
         torch.cuda.empty_cache()
         try:
@@ -849,7 +855,7 @@ def main():
         except Exception as e:                               # the headline must not die with the side leg
             res["harness"] = {"error": repr(e)[:300]}
     if rank == 0:
-        if world == 1 and args.cpu_sample > 0 and args.config == "ign":
+        if args.full and world == 1 and args.cpu_sample > 0 and args.config == "ign":
             log("cpu baseline (ign) ...")
             res["cpu_baseline"] = cpu_baseline_ign(cfg, args.cpu_sample, host_cores())
         print(json.dumps(res), flush=True)

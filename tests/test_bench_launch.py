@@ -104,6 +104,26 @@ def test_dump_outputs_holds_the_last_timed_step(tmp_path):
 
 
 @pytest.mark.gpu
+def test_side_passes_run_only_with_full():
+    """A plain run prints the headline and the roofline of its timed steps and runs nothing else, whatever the side passes'
+    sizes default to; `--full` adds the fp32-MFMA convolution leg, the isolated roofline and the two baselines."""
+    if not has_gpu():
+        pytest.skip("needs a GPU")
+    small = ("--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "8")
+    r = _run({}, *small)
+    assert r.returncode == 0, r.stderr[-3000:]
+    plain = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert plain["steps"] == 2 and plain["ms_per_step"] > 0 and plain["roofline"]["launches"] > 0
+    assert "isolated" not in plain["roofline"] and not {"fp32_mfma_conv", "baselines", "harness", "cpu_baseline"} & set(plain)
+    assert "harness leg" not in r.stderr and "cpu baseline" not in r.stderr
+    r = _run({}, *small, "--full", "--alt-steps", "2", "--iso-steps", "1", "--cpu-sample", "0", "--baseline-steps", "1")
+    assert r.returncode == 0, r.stderr[-3000:]
+    full = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert full["fp32_mfma_conv"]["steps"] == 2 and full["roofline"]["isolated"]["steps"] == 1
+    assert set(full["baselines"]) == {"eegcnn", "transformer"} and "cpu_baseline" not in full
+
+
+@pytest.mark.gpu
 def test_two_rank_rehearsal_end_to_end():
     if not has_gpu():
         pytest.skip("needs a GPU")
@@ -142,7 +162,7 @@ def test_one_rank_rccl_rendezvous_emits_the_collective_fields():
 
 
 def test_committed_bench_line_carries_the_contract_fields():
-    """The driver-facing JSON line (profiles/r3_bench_line.json = the default `python bench.py` run of the round-end measurement
+    """The driver-facing JSON line (profiles/r3_bench_line.json = the `python bench.py --full` run of the round-end measurement
     pass, profiles/collect_round.sh): metric / value / unit / n_gpus / steps / warmup / ms_per_step / higher_is_better / scaling /
     vs_baseline / dtype / data / config.workload, the roofline object of the dominant kernel, the CPU baseline, configs 3 / 4 --
     and the round-3 additions: config.data says the inputs are resident, the `harness` leg (Experiment.train_one_epoch with
