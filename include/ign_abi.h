@@ -300,6 +300,20 @@ int ign_sbm_reg_fwd_bwd(const float* W, float* gW_reg, long long nW, float lambd
                         float* const* gw_kcl, const int* K, const int* L, int C, float lambda_div, float eps, float* loss_out,
                         void* workspace, void* stream);
 
+/* SBM attention head (sbm_cls='attention'; IGN/model/Shapelet.py:117-131, 201-205) without its (B,F,F) scores:
+ *   q_i = x_i wq + bq + pos_i,  k_j = x_j wk + bk + pos_j,  out_i = sum_j softmax_j(scale q_i.k_j) x_j   (D = 16 wide q / k)
+ * x (B,F) with row pitch ldx >= F; wq / wk the (D,1) projection weights, bq / bk (D), pos (>= F, D); out (B,F) contiguous.
+ * lse (B,F): base-2 log-sum-exp of the scaled scores, written when not NULL and read only by ign_sbm_attn_bwd.
+ * Backward: gout (B,F) contiguous; writes gx (B,F) and the parameter gradients gwq / gbq / gwk / gbk (D) and gpos (F,D) (rows
+ * of pos past F are not touched).  workspace: ign_sbm_attn_workspace_bytes(B, F) bytes, no initialisation needed.
+ * Any B, F >= 1; fp32 only; fixed-order reductions, no float atomics: bitwise reproducible.  D must be 16.                */
+size_t ign_sbm_attn_workspace_bytes(int B, int F);
+int ign_sbm_attn_fwd(const float* x, long long ldx, const float* wq, const float* bq, const float* wk, const float* bk,
+                     const float* pos, float* out, float* lse, int B, int F, int D, float scale, void* stream);
+int ign_sbm_attn_bwd(const float* x, long long ldx, const float* wq, const float* bq, const float* wk, const float* bk,
+                     const float* pos, const float* out, const float* lse, const float* gout, float* gx, float* gwq, float* gbq,
+                     float* gwk, float* gbk, float* gpos, void* workspace, int B, int F, int D, float scale, void* stream);
+
 /* One Adam step over flat buffers (torch.optim.Adam semantics, no weight decay / amsgrad): replaces the per-tensor
  * optimizer.step() of IGN/exp/experiment_classification.py:338.  `step` is the 1-based step count.               */
 int ign_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, float lr,

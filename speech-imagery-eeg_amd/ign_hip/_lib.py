@@ -129,6 +129,9 @@ SIGNATURES = {
     "ign_loss_fwd_bwd_reg": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, cf, vp]),
     "ign_sbm_reg_workspace_bytes": (sz, [ci, ci, ll]),
     "ign_sbm_reg_fwd_bwd": (ci, [vp, vp, ll, cf, ci, vp, vp, vp, vp, ci, cf, cf, vp, vp, vp]),
+    "ign_sbm_attn_workspace_bytes": (sz, [ci, ci]),
+    "ign_sbm_attn_fwd": (ci, [vp, ll, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, cf, vp]),
+    "ign_sbm_attn_bwd": (ci, [vp, ll, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, cf, vp]),
     "ign_shapelet_bwd_bank_workspace_bytes": (sz, [ci, ci, ci, ci, vp, vp, vp, ci]),
     "ign_shapelet_bwd_bank": (ci, [vp, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, cf, ci,
                                    vp]),

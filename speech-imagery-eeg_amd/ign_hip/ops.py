@@ -1549,3 +1549,67 @@ def diversity(w):
     if not w.is_cuda or w.dtype != torch.float32 or w.shape[0] > 16:
         return None
     return DiversityFn.apply(w)
+
+
+def _sbm_attn_forward(x, wq, bq, wk, bk, pos, want_lse):
+    B, F_ = x.shape
+    D = wq.shape[0]
+    out = torch.empty(B, F_, device=x.device, dtype=torch.float32)
+    lse = torch.empty(B, F_, device=x.device, dtype=torch.float32) if want_lse else None
+    _lib.check(_lib.lib().ign_sbm_attn_fwd(_ptr(x), x.stride(0), _ptr(wq), _ptr(bq), _ptr(wk), _ptr(bk), _ptr(pos), _ptr(out),
+                                           _ptr(lse), B, F_, D, D ** -0.5, _stream()), "ign_sbm_attn_fwd")
+    return out, lse
+
+
+def _sbm_attn_inputs(x, wq, bq, wk, bk, pos):
+    _need_gpu("sbm_attention", x, wq, bq, wk, bk, pos)
+    if x.dim() != 2 or x.stride(1) != 1:
+        x = x.reshape(x.shape[0], -1).contiguous()
+    D = wq.shape[0]
+    if wq.numel() != D or wk.shape[0] != D or wk.numel() != D or bq.numel() != D or bk.numel() != D or pos.dim() != 2 \
+            or pos.shape[1] != D or pos.shape[0] < x.shape[1]:
+        raise _lib.IgnError(f"sbm_attention: shapes x {tuple(x.shape)}, wq {tuple(wq.shape)}, wk {tuple(wk.shape)}, "
+                            f"pos {tuple(pos.shape)} do not form a (B,F) x (D,1) x (>=F,D) head")
+    return (x,) + tuple(t.contiguous() for t in (wq, bq, wk, bk, pos))
+
+
+class SbmAttentionFn(torch.autograd.Function):
+    """The SBM attention head (models/Shapelet.py SelfAttention) on ign_sbm_attn_fwd / ign_sbm_attn_bwd: the (B,F,F) scores are
+    never stored.  Saves x, the parameters, the output and its base-2 log-sum-exp; the backward is four launches that produce
+    dx and all five parameter gradients.  No host synchronisation and no state kept across calls: capturable."""
+
+    @staticmethod
+    def forward(ctx, x, wq, bq, wk, bk, pos):
+        x, wq, bq, wk, bk, pos = _sbm_attn_inputs(x, wq, bq, wk, bk, pos)
+        out, lse = _sbm_attn_forward(x, wq, bq, wk, bk, pos, True)
+        ctx.save_for_backward(x, wq, bq, wk, bk, pos, out, lse)
+        ctx.pos_rows = pos.shape[0]
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, wq, bq, wk, bk, pos, out, lse = ctx.saved_tensors
+        B, F_ = x.shape
+        D = wq.shape[0]
+        L = _lib.lib()
+        g = g.contiguous()
+        gx = torch.empty(B, F_, device=x.device, dtype=torch.float32)
+        gwq, gwk = torch.empty_like(wq), torch.empty_like(wk)
+        gbq, gbk = torch.empty_like(bq), torch.empty_like(bk)
+        gpos = torch.empty_like(pos) if ctx.pos_rows == F_ else torch.zeros_like(pos)   # rows past F get no gradient
+        ws = torch.empty(L.ign_sbm_attn_workspace_bytes(B, F_) // 4, device=x.device, dtype=torch.float32)
+        _lib.check(L.ign_sbm_attn_bwd(_ptr(x), x.stride(0), _ptr(wq), _ptr(bq), _ptr(wk), _ptr(bk), _ptr(pos), _ptr(out), _ptr(lse),
+                                      _ptr(g), _ptr(gx), _ptr(gwq), _ptr(gbq), _ptr(gwk), _ptr(gbk), _ptr(gpos), _ptr(ws), B, F_, D,
+                                      D ** -0.5, _stream()), "ign_sbm_attn_bwd")
+        need = ctx.needs_input_grad
+        return tuple(t if n else None for t, n in zip((gx, gwq, gbq, gwk, gbk, gpos), need))
+
+
+def sbm_attention(x, wq, bq, wk, bk, pos):
+    """o_i = sum_j softmax_j(q_i.k_j / sqrt(D)) x_j with q_i = x_i wq + bq + pos_i, k_j = x_j wk + bk + pos_j, over the F features
+    of each row of x (B,F): F.scaled_dot_product_attention(q, k, x[..., None]) of IGN/model/Shapelet.py:126-131 in fp32, also
+    inside an autocast region.  x (B,F) fp32 on the GPU; wq / wk (D,1), bq / bk (D), pos (>=F, D) with D = 16.  Without
+    autograd (no_grad, eval with frozen inputs) only the forward runs and no log-sum-exp is written."""
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (x, wq, bq, wk, bk, pos)):
+        return SbmAttentionFn.apply(x, wq, bq, wk, bk, pos)
+    return _sbm_attn_forward(*_sbm_attn_inputs(x, wq, bq, wk, bk, pos), False)[0]

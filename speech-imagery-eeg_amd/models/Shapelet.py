@@ -84,6 +84,10 @@ class SelfAttention(nn.Module):
         self.pos_embed = nn.Embedding(num_embeddings=dim_feature, embedding_dim=dim_attn)
 
     def forward(self, x):
+        if x.is_cuda and x.dtype == torch.float32:
+            # fused kernels (ops.sbm_attention): no (B,F,F) scores; fp32 inside an autocast region too, like the EEG-CNN block
+            return ops.sbm_attention(x, self.q_proj.weight, self.q_proj.bias, self.k_proj.weight, self.k_proj.bias,
+                                     self.pos_embed.weight)
         pos = self.pos_embed(torch.arange(x.shape[1], device=x.device))
         q = self.q_proj(x.unsqueeze(-1)) + pos
         k = self.k_proj(x.unsqueeze(-1)) + pos
