@@ -314,6 +314,21 @@ int ign_sbm_attn_bwd(const float* x, long long ldx, const float* wq, const float
                      const float* pos, const float* out, const float* lse, const float* gout, float* gx, float* gwq, float* gbq,
                      float* gwk, float* gbk, float* gpos, void* workspace, int B, int F, int D, float scale, void* stream);
 
+/* SBM bilinear head (sbm_cls='bilinear'; IGN/model/Shapelet.py:170-177, 199-205): the nn.Bilinear term, no bias,
+ *   out[b,n] = sum_{i,j} u[b,i] w[n,i,j] v[b,j]
+ * as exact-fp32 matrix-core GEMMs.  u, v (B,F), w (N,F,F), out (B,N), all contiguous.  Forward: T_n = u w_n and the row
+ * dot with v; t_save (B,N,F) receives T when not NULL (the backward's gv needs it).  Backward with gout (B,N):
+ * gu = sum_n (gout_n . v) w_n^T, gv = sum_n gout_n . T_n (needs t_save), gw_n = (gout_n . u)^T v; each of gu / gv / gw may
+ * be NULL and is then not computed.  workspace: ign_sbm_bilinear_workspace_bytes(B, F, N) bytes, no initialisation needed:
+ * B*N floats per 128 columns of F (forward row-dot partials), or B*N*F (the backward's per-class partials of gu) if more;
+ * the backward needs it only for gu with N > 1.
+ * Any B, F, N >= 1; fixed-order reductions, no float atomics: bitwise reproducible.  No F*F or B*F*F temporary.        */
+size_t ign_sbm_bilinear_workspace_bytes(int B, int F, int N);
+int ign_sbm_bilinear_fwd(const float* u, const float* v, const float* w, float* out, float* t_save, void* workspace, int B, int F,
+                         int N, void* stream);
+int ign_sbm_bilinear_bwd(const float* u, const float* v, const float* w, const float* t_save, const float* gout, float* gu,
+                         float* gv, float* gw, void* workspace, int B, int F, int N, void* stream);
+
 /* One Adam step over flat buffers (torch.optim.Adam semantics, no weight decay / amsgrad): replaces the per-tensor
  * optimizer.step() of IGN/exp/experiment_classification.py:338.  `step` is the 1-based step count.               */
 int ign_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, float lr,

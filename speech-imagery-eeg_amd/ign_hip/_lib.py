@@ -132,6 +132,9 @@ SIGNATURES = {
     "ign_sbm_attn_workspace_bytes": (sz, [ci, ci]),
     "ign_sbm_attn_fwd": (ci, [vp, ll, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, cf, vp]),
     "ign_sbm_attn_bwd": (ci, [vp, ll, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, cf, vp]),
+    "ign_sbm_bilinear_workspace_bytes": (sz, [ci, ci, ci]),
+    "ign_sbm_bilinear_fwd": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, vp]),
+    "ign_sbm_bilinear_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp]),
     "ign_shapelet_bwd_bank_workspace_bytes": (sz, [ci, ci, ci, ci, vp, vp, vp, ci]),
     "ign_shapelet_bwd_bank": (ci, [vp, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, cf, ci,
                                    vp]),

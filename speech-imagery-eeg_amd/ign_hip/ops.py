@@ -1613,3 +1613,63 @@ def sbm_attention(x, wq, bq, wk, bk, pos):
     if torch.is_grad_enabled() and any(t.requires_grad for t in (x, wq, bq, wk, bk, pos)):
         return SbmAttentionFn.apply(x, wq, bq, wk, bk, pos)
     return _sbm_attn_forward(*_sbm_attn_inputs(x, wq, bq, wk, bk, pos), False)[0]
+
+
+def _sbm_bilinear_inputs(u, v, weight):
+    _need_gpu("sbm_bilinear", u, v, weight)
+    if u.dim() != 2 or tuple(v.shape) != tuple(u.shape) or weight.dim() != 3 or weight.shape[1] != u.shape[1] \
+            or weight.shape[2] != u.shape[1]:
+        raise _lib.IgnError(f"sbm_bilinear: shapes u {tuple(u.shape)}, v {tuple(v.shape)}, weight {tuple(weight.shape)} do not "
+                            f"form a (B,F) x (B,F) x (N,F,F) bilinear head")
+    return u.contiguous(), v.contiguous(), weight.contiguous()
+
+
+def _sbm_bilinear_forward(u, v, w, want_t):
+    B, F_ = u.shape
+    N = w.shape[0]
+    L = _lib.lib()
+    out = torch.empty(B, N, device=u.device, dtype=torch.float32)
+    t = torch.empty(B, N, F_, device=u.device, dtype=torch.float32) if want_t else None
+    ws = torch.empty(L.ign_sbm_bilinear_workspace_bytes(B, F_, N) // 4, device=u.device, dtype=torch.float32)
+    _lib.check(L.ign_sbm_bilinear_fwd(_ptr(u), _ptr(v), _ptr(w), _ptr(out), _ptr(t), _ptr(ws), B, F_, N, _stream()),
+               "ign_sbm_bilinear_fwd")
+    return out, t
+
+
+class SbmBilinearFn(torch.autograd.Function):
+    """The bilinear term of the SBM head (nn.Bilinear without bias, models/Shapelet.py) on ign_sbm_bilinear_fwd / _bwd: three
+    fp32 matrix-core GEMMs and no (B,F,F) temporary.  Saves u, v, the weight and, when v needs a gradient, T = (u W_n) (B,N,F);
+    the backward computes only the gradients asked for (W frozen: no dW GEMM).  No host synchronisation: capturable."""
+
+    @staticmethod
+    def forward(ctx, u, v, weight):
+        u, v, weight = _sbm_bilinear_inputs(u, v, weight)
+        out, t = _sbm_bilinear_forward(u, v, weight, ctx.needs_input_grad[1])
+        ctx.save_for_backward(u, v, weight, t)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        u, v, w, t = ctx.saved_tensors
+        B, F_ = u.shape
+        N = w.shape[0]
+        need_u, need_v, need_w = ctx.needs_input_grad
+        g = g.contiguous()
+        gu = torch.empty_like(u) if need_u else None
+        gv = torch.empty_like(v) if need_v else None
+        gw = torch.empty_like(w) if need_w else None
+        L = _lib.lib()
+        ws = torch.empty(L.ign_sbm_bilinear_workspace_bytes(B, F_, N) // 4, device=u.device, dtype=torch.float32) \
+            if need_u and N > 1 else None                     # the per-class partials of gu
+        _lib.check(L.ign_sbm_bilinear_bwd(_ptr(u), _ptr(v), _ptr(w), _ptr(t), _ptr(g), _ptr(gu), _ptr(gv), _ptr(gw), _ptr(ws), B, F_,
+                                          N, _stream()), "ign_sbm_bilinear_bwd")
+        return gu, gv, gw
+
+
+def sbm_bilinear(u, v, weight):
+    """out[b,n] = sum_{i,j} u[b,i] weight[n,i,j] v[b,j]: nn.Bilinear(F, F, N, bias=False)(u, v) of IGN/model/Shapelet.py:199-205
+    in exact fp32, also inside an autocast region.  u, v (B,F) and weight (N,F,F) fp32 on the GPU.  Without autograd (no_grad,
+    or nothing requires grad) only the forward runs and T is not written."""
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (u, v, weight)):
+        return SbmBilinearFn.apply(u, v, weight)
+    return _sbm_bilinear_forward(*_sbm_bilinear_inputs(u, v, weight), False)[0]

@@ -150,7 +150,14 @@ class ShapeBottleneckModel(nn.Module):
         if cls == 'linear':
             return ops.head_linear(self.dropout(p), self.output_layer.weight)
         if cls == 'bilinear':
-            return self.output_layer(self.dropout(p)) + self.output_bilinear(self.dropout(p), self.dropout(p))
+            lin = self.output_layer(self.dropout(p))
+            a, b = self.dropout(p), self.dropout(p)            # three dropout draws in the reference's order
+            W = self.output_bilinear.weight
+            if a.is_cuda and a.dtype == torch.float32 and b.dtype == torch.float32 and W.dtype == torch.float32:
+                # ops.sbm_bilinear: fp32 matrix-core GEMMs, no (B,F,F) autograd temporary.  nn.Bilinear is on autocast's
+                # promote list, so with fp32 operands it returns fp32 inside an autocast region too, as the op does
+                return lin + ops.sbm_bilinear(a, b, W)
+            return lin + self.output_bilinear(a, b)
         return self.output_layer(self.dropout(self.attention(p)))
 
     def _fused_forward(self, x, xn):
