@@ -29,6 +29,10 @@ extern "C" {
 #define IGN_E_UNSUP    (-1002)  /* combination not implemented (see message)              */
 #define IGN_E_TOOBIG   (-1003)  /* a row does not fit the LDS staging budget              */
 
+/* Largest class count N of the class-head GEMMs (ign_head_*) and the fused loss tail (ign_loss_*); above it they return
+ * IGN_E_UNSUP.  N <= 16 runs the single-pass kernels; wider heads run in 16-class chunks with the same launch count.      */
+#define IGN_HEAD_NMAX  256
+
 /* distance / gate selectors: `mode` = IGN_DIST_* | IGN_GATE_*                                           */
 #define IGN_DIST_L1    0   /* mean |x-w|      IGN/model/Shapelet.py:74 ("euclidean", the default)        */
 #define IGN_DIST_MSE   1   /* mean (x-w)^2    IGN/model/Shapelet.py:24-40 (memory_efficient branch)      */
@@ -251,10 +255,11 @@ int ign_attn_probs(const float* q, const float* k, const float* lse, float* attn
                    float scale, void* stream, int math, const float* bq, const float* bk,
                    float p, unsigned long long seed);
 
-/* Skinny expert-head GEMM  out[b,n] = sum_f X[b,f] W[n,f] (+ bias[n]),  N <= 16 classes, F % 4 == 0, row pitch ldx.
+/* Skinny expert-head GEMM  out[b,n] = sum_f X[b,f] W[n,f] (+ bias[n]),  N <= IGN_HEAD_NMAX classes, F % 4 == 0, row pitch ldx.
  * Replaces nn.Linear at IGN/model/Shapelet.py:171,200 (SBM head), IGN/model/Transformer.py:72,109,
  * IGN/model/FullyConvNet.py:50,58.  Backward: gX (B,ldx) and/or gW (N,F), gbias (N) (any may be NULL); sums over the
- * batch run in ascending order (deterministic).                                                                    */
+ * batch run in ascending order, gX sums the classes in ascending order (deterministic).  One launch per call at any N
+ * (N > 16: 16-class chunks as an extra grid dimension).  gW stages g in LDS: B*N <= 10240 for N <= 16, B <= 640 above.  */
 int ign_head_fwd(const float* X, const float* W, const float* bias, float* out, int B, int F, int N, long long ldx,
                  void* stream);
 int ign_head_bwd(const float* g_out, const float* X, const float* W, float* gX, float* gW, float* gbias,
@@ -275,7 +280,8 @@ int ign_gate_bwd(const float* sbm, const float* dnn, const float* gout, const fl
 /* IGN's training-loss tail in one launch: gini gate + CE(mixture, y) + beta*CE(sbm, y) (batch means) and the gradients of
  * that sum w.r.t. both experts' logits.  Replaces IGN/exp/experiment_classification.py:320-329 (the two F.cross_entropy
  * terms) together with IGN/model/InterpGN.py:44-52 and their autograd.  labels: int64 (B), values in [0, N).
- * out (B,N), eta (B), loss2 = {CE(out,y), CE(sbm,y), their beta-weighted sum}, gsbm / gdnn (B,N) = d(CE(out,y) + beta*CE(sbm,y)) / d logits.  N <= 16. */
+ * out (B,N), eta (B), loss2 = {CE(out,y), CE(sbm,y), their beta-weighted sum}, gsbm / gdnn (B,N) = d(CE(out,y) + beta*CE(sbm,y)) / d logits.
+ * 2 <= N <= IGN_HEAD_NMAX; one block, one launch at any N (N > 16: one wave per row, per-row losses summed in row order).   */
 int ign_loss_fwd_bwd(const float* sbm, const float* dnn, const long long* labels, float* out, float* eta, float* loss2,
                      float* gsbm, float* gdnn, int B, int N, float beta, void* stream);
 /* The same with the model's regulariser value added to loss2[2] on the device (`reg`: one float, nullable): the whole training

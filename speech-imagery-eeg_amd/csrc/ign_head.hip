@@ -1,11 +1,13 @@
 // Expert-head GEMMs, the gini gate and the flat Adam update: the small HBM-bound pieces of the training step.
 //
-//  * head GEMM  out[b,n] = sum_f X[b,f] W[n,f] (+ bias[n])  with N = number of classes (3..16) -- "skinny":
+//  * head GEMM  out[b,n] = sum_f X[b,f] W[n,f] (+ bias[n])  with N = number of classes (2..IGN_HEAD_NMAX = 256; above 16 in
+//    16-class chunks, one extra grid dimension, same launch count) -- "skinny":
 //    IGN/model/Shapelet.py:171,200 (SBM head, F = G*K*C = 2440), IGN/model/Transformer.py:72,109 (F = T*d = 512000),
 //    IGN/model/FullyConvNet.py:50,58.  N is far too small for an MFMA tile to pay (a 32x32 tile would be >90 % padding)
 //    and the op moves 4*(B*F + N*F) bytes for 2*B*F*N flops (intensity ~N/2 flop/byte): HBM/L2 bound, so it is a
 //    coalesced float4 streaming kernel with N accumulators per thread and a block reduction.
-//  * gini gate  eta = (N*sum softmax(s)^2 - 1)/(N-1); out = eta*s + (1-eta)*d   IGN/model/InterpGN.py:44-52, fwd + bwd.
+//  * gini gate  eta = (N*sum softmax(s)^2 - 1)/(N-1); out = eta*s + (1-eta)*d   IGN/model/InterpGN.py:44-52, fwd + bwd; and the
+//    fused loss tail (gate + both cross-entropies + their logit gradients): one thread per row up to 16 classes, one wave per row above.
 //  * Adam       one launch over the flat parameter / gradient / moment buffers (torch.optim.Adam semantics,
 //    IGN/exp/experiment_classification.py:136,338).
 #include "ign_common.h"
@@ -15,12 +17,18 @@ constexpr int HEAD_NMAX = 16;
 // ------------------------------------------------------------------------------------------------ head forward
 // One block per row; 256 threads, or 1024 for long rows (the Transformer's 512 000-feature head: one 256-thread block per CU
 // kept four loads per lane in flight and ran at 0.7 TB/s).
+// WIDE (N > 16): blockIdx.y = 16-class chunk; each chunk runs the N <= 16 arithmetic on its classes n0 .. n0 + 15 (the row of X
+// is re-read per chunk, from L2).  The N <= 16 instantiation is the single-chunk kernel (n0 = 0, one grid row).
+template <bool WIDE>
 __global__ void __launch_bounds__(1024) head_fwd_kernel(const float* __restrict__ X, const float* __restrict__ W,
                                                         const float* __restrict__ bias, float* __restrict__ out,
                                                         int B, int F, int N, long long ldx) {
     __shared__ float red[16][HEAD_NMAX];
     const int b = blockIdx.x;
+    const int n0 = WIDE ? blockIdx.y * HEAD_NMAX : 0;
+    const int nc = WIDE ? min(N - n0, HEAD_NMAX) : N;         // classes of this chunk
     const float* x = X + (long long)b * ldx;
+    const float* Wc = W + (long long)n0 * F;
     float acc[HEAD_NMAX];
 #pragma unroll
     for (int n = 0; n < HEAD_NMAX; ++n) acc[n] = 0.f;
@@ -30,15 +38,15 @@ __global__ void __launch_bounds__(1024) head_fwd_kernel(const float* __restrict_
         const float4 xv = *reinterpret_cast<const float4*>(x + f);
 #pragma unroll
         for (int n = 0; n < HEAD_NMAX; ++n)
-            if (n < N) {
-                const float4 wv = *reinterpret_cast<const float4*>(W + (long long)n * F + f);
+            if (n < nc) {
+                const float4 wv = *reinterpret_cast<const float4*>(Wc + (long long)n * F + f);
                 acc[n] += xv.x * wv.x + xv.y * wv.y + xv.z * wv.z + xv.w * wv.w;
             }
     }
     for (int f = F4 + threadIdx.x; f < F; f += nthr)
 #pragma unroll
         for (int n = 0; n < HEAD_NMAX; ++n)
-            if (n < N) acc[n] += x[f] * W[(long long)n * F + f];
+            if (n < nc) acc[n] += x[f] * Wc[(long long)n * F + f];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int n = 0; n < HEAD_NMAX; ++n) {
@@ -48,43 +56,56 @@ __global__ void __launch_bounds__(1024) head_fwd_kernel(const float* __restrict_
         if (lane == 0) red[wave][n] = v;
     }
     __syncthreads();
-    if (threadIdx.x < N) {
+    if (threadIdx.x < nc) {
         const int n = threadIdx.x;
         float t = 0.f;
         for (int w = 0; w < (nthr >> 6); ++w) t += red[w][n];          // fixed order
-        out[(long long)b * N + n] = t + (bias ? bias[n] : 0.f);
+        out[(long long)b * N + n0 + n] = t + (bias ? bias[n0 + n] : 0.f);
     }
 }
 
-// gX[b,f] = sum_n g[b,n] W[n,f]
+// gX[b,f] = sum_n g[b,n] W[n,f].  WIDE: the thread walks the 16-class chunks in ascending order into one accumulator -- the
+// order of a single N-loop, so the sum does not depend on the chunking.
+template <bool WIDE>
 __device__ __forceinline__ void head_bwd_x_body(const float* __restrict__ g, const float* __restrict__ W,
                                                 float* __restrict__ gX, int B, int F, int N, long long ldx, int bx, int b) {
     const int f = (bx * 256 + threadIdx.x) * 4;
     if (f >= F) return;
     float gn[HEAD_NMAX];
+    if constexpr (!WIDE) {
 #pragma unroll
-    for (int n = 0; n < HEAD_NMAX; ++n) gn[n] = n < N ? g[(long long)b * N + n] : 0.f;
+        for (int n = 0; n < HEAD_NMAX; ++n) gn[n] = n < N ? g[(long long)b * N + n] : 0.f;
+    }
     if (f + 3 < F) {
         float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+        const int nch = WIDE ? (N + HEAD_NMAX - 1) / HEAD_NMAX : 1;
+        for (int c = 0; c < nch; ++c) {
+            const int n0 = c * HEAD_NMAX, nc = WIDE ? min(N - n0, HEAD_NMAX) : N;
+            if constexpr (WIDE) {
 #pragma unroll
-        for (int n = 0; n < HEAD_NMAX; ++n)
-            if (n < N) {
-                const float4 wv = *reinterpret_cast<const float4*>(W + (long long)n * F + f);
-                r.x += gn[n] * wv.x; r.y += gn[n] * wv.y; r.z += gn[n] * wv.z; r.w += gn[n] * wv.w;
+                for (int n = 0; n < HEAD_NMAX; ++n) gn[n] = n < nc ? g[(long long)b * N + n0 + n] : 0.f;
             }
+#pragma unroll
+            for (int n = 0; n < HEAD_NMAX; ++n)
+                if (n < nc) {
+                    const float4 wv = *reinterpret_cast<const float4*>(W + (long long)(n0 + n) * F + f);
+                    r.x += gn[n] * wv.x; r.y += gn[n] * wv.y; r.z += gn[n] * wv.z; r.w += gn[n] * wv.w;
+                }
+        }
         *reinterpret_cast<float4*>(gX + (long long)b * ldx + f) = r;
-    } else {
+    } else {                                         // (unreachable while F % 4 == 0 is required)
         for (int ff = f; ff < F; ++ff) {
             float r = 0.f;
-            for (int n = 0; n < N; ++n) r += gn[n] * W[(long long)n * F + ff];
+            for (int n = 0; n < N; ++n) r += (WIDE ? g[(long long)b * N + n] : gn[n]) * W[(long long)n * F + ff];
             gX[(long long)b * ldx + ff] = r;
         }
     }
 }
 
+template <bool WIDE>
 __global__ void __launch_bounds__(256) head_bwd_x_kernel(const float* __restrict__ g, const float* __restrict__ W,
                                                          float* __restrict__ gX, int B, int F, int N, long long ldx) {
-    head_bwd_x_body(g, W, gX, B, F, N, ldx, blockIdx.x, blockIdx.y);
+    head_bwd_x_body<WIDE>(g, W, gX, B, F, N, ldx, blockIdx.x, blockIdx.y);
 }
 
 // gW[n,f] = sum_b g[b,n] X[b,f];  gbias[n] = sum_b g[b,n].
@@ -93,19 +114,31 @@ __global__ void __launch_bounds__(256) head_bwd_x_kernel(const float* __restrict
 // a 256-f-per-block version ran 10 blocks and took 125 us of a 17.9 ms step).
 // `add` / `add_scale` (both nullable): gW += add_scale[0] * add -- a gradient of the same tensor that does not depend on the batch
 // (the L1 regulariser of the SBM head, IGN/model/Shapelet.py:219) rides on this store instead of an accumulate kernel.
+// `bx` = the block's 32-f slice, `n0` = its first class.  WIDE: the block covers classes n0 .. n0 + 15 and stages only those
+// columns of g (B x 16 floats, whatever N), so the LDS budget does not grow with N; f-slice 0 of each chunk writes its gbias.
+template <bool WIDE>
 __device__ __forceinline__ void head_bwd_w_body(const float* __restrict__ g, const float* __restrict__ X,
                                                 float* __restrict__ gW, float* __restrict__ gbias, int B, int F,
                                                 int N, long long ldx, const float* __restrict__ add,
-                                                const float* __restrict__ add_scale, const int bx) {
-    extern __shared__ float sm[];               // g copy [B*N], then partials [8][HEAD_NMAX][32]
+                                                const float* __restrict__ add_scale, const int bx, const int n0) {
+    extern __shared__ float sm[];               // g copy [B*gsn], then partials [8][HEAD_NMAX][32]
+    const int gsn = WIDE ? HEAD_NMAX : N;       // row pitch of the g copy
+    const int nc = WIDE ? min(N - n0, HEAD_NMAX) : N;
     float* gs = sm;
-    float* part = sm + B * N;
-    for (int i = threadIdx.x; i < B * N; i += 256) gs[i] = g[i];
+    float* part = sm + B * gsn;
+    if (WIDE) {
+        for (int i = threadIdx.x; i < B * HEAD_NMAX; i += 256) {
+            const int b = i / HEAD_NMAX, n = i % HEAD_NMAX;
+            gs[i] = n < nc ? g[(long long)b * N + n0 + n] : 0.f;
+        }
+    } else {
+        for (int i = threadIdx.x; i < B * N; i += 256) gs[i] = g[i];
+    }
     __syncthreads();
-    if (gbias && bx == 0 && threadIdx.x < N) {
+    if (gbias && bx == 0 && threadIdx.x < nc) {
         float s = 0.f;
-        for (int b = 0; b < B; ++b) s += gs[b * N + threadIdx.x];
-        gbias[threadIdx.x] = s;
+        for (int b = 0; b < B; ++b) s += gs[b * gsn + threadIdx.x];
+        gbias[n0 + threadIdx.x] = s;
     }
     const int fl = threadIdx.x & 31, grp = threadIdx.x >> 5;
     const int f = bx * 32 + fl;
@@ -119,34 +152,38 @@ __device__ __forceinline__ void head_bwd_w_body(const float* __restrict__ g, con
             const float xv = X[(long long)b * ldx + f];
 #pragma unroll
             for (int n = 0; n < HEAD_NMAX; ++n)
-                if (n < N) acc[n] = fmaf(gs[b * N + n], xv, acc[n]);
+                if (n < nc) acc[n] = fmaf(gs[b * gsn + n], xv, acc[n]);
         }
 #pragma unroll
     for (int n = 0; n < HEAD_NMAX; ++n)
-        if (n < N) part[(grp * HEAD_NMAX + n) * 32 + fl] = acc[n];
+        if (n < nc) part[(grp * HEAD_NMAX + n) * 32 + fl] = acc[n];
     __syncthreads();
-    for (int i = threadIdx.x; i < N * 32; i += 256) {
+    for (int i = threadIdx.x; i < nc * 32; i += 256) {
         const int n = i >> 5, ff = i & 31;
         if (bx * 32 + ff < F) {
             float s = 0.f;
 #pragma unroll
             for (int q = 0; q < 8; ++q) s += part[(q * HEAD_NMAX + n) * 32 + ff];
-            const long long o = (long long)n * F + bx * 32 + ff;
+            const long long o = (long long)(n0 + n) * F + bx * 32 + ff;
             if (add) s += (add_scale ? add_scale[0] : 1.f) * add[o];
             gW[o] = s;
         }
     }
 }
 
+// grid (F/32 slices[, 16-class chunks])
+template <bool WIDE>
 __global__ void __launch_bounds__(256) head_bwd_w_kernel(const float* __restrict__ g, const float* __restrict__ X,
                                                          float* __restrict__ gW, float* __restrict__ gbias, int B, int F,
                                                          int N, long long ldx, const float* __restrict__ add,
                                                          const float* __restrict__ add_scale) {
-    head_bwd_w_body(g, X, gW, gbias, B, F, N, ldx, add, add_scale, blockIdx.x);
+    head_bwd_w_body<WIDE>(g, X, gW, gbias, B, F, N, ldx, add, add_scale, blockIdx.x, WIDE ? blockIdx.y * HEAD_NMAX : 0);
 }
 
 // both gradients in ONE launch: blocks [0, nwb) play head_bwd_w_kernel's role, the rest head_bwd_x_kernel's ((nxb, B) grid
-// flattened) -- block-uniform branch, the two halves touch disjoint outputs
+// flattened) -- block-uniform branch, the two halves touch disjoint outputs.  WIDE: nwb = (F/32 slices) x (16-class chunks),
+// slice-fastest.
+template <bool WIDE>
 __global__ void __launch_bounds__(256) head_bwd_xw_kernel(const float* __restrict__ g, const float* __restrict__ X,
                                                           const float* __restrict__ W, float* __restrict__ gX,
                                                           float* __restrict__ gW, float* __restrict__ gbias, int B, int F, int N,
@@ -154,10 +191,12 @@ __global__ void __launch_bounds__(256) head_bwd_xw_kernel(const float* __restric
                                                           const float* __restrict__ add_scale, int nwb, int nxb) {
     const int blk = blockIdx.x;
     if (blk < nwb) {
-        head_bwd_w_body(g, X, gW, gbias, B, F, N, ldx, add, add_scale, blk);
+        const int nfb = WIDE ? (F + 31) / 32 : nwb;
+        const int c = WIDE ? blk / nfb : 0;
+        head_bwd_w_body<WIDE>(g, X, gW, gbias, B, F, N, ldx, add, add_scale, blk - c * nfb, c * HEAD_NMAX);
     } else {
         const int r = blk - nwb;
-        head_bwd_x_body(g, W, gX, B, F, N, ldx, r % nxb, r / nxb);
+        head_bwd_x_body<WIDE>(g, W, gX, B, F, N, ldx, r % nxb, r / nxb);
     }
 }
 
@@ -277,11 +316,129 @@ __global__ void __launch_bounds__(256) ign_loss_kernel(const float* __restrict__
     }
 }
 
+// The same loss tail for 16 < N <= IGN_HEAD_NMAX: one block of 16 waves, one wave per row (rows w, w + 16, ...), the lanes cover
+// the classes in chunks of 64 and every row-wide max / sum is a butterfly over the wave (each lane ends with the same value).
+// The arithmetic per row is ign_loss_kernel's.  Each row's two CE terms go to LDS at their row index; one thread adds them in
+// ascending row order (LOSS_TILE rows at a time), so the batch mean does not depend on how the waves were scheduled.
+constexpr int LOSS_WAVES = 16, LOSS_TILE = 1024, LOSS_KMAX = IGN_HEAD_NMAX / 64;
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__global__ void __launch_bounds__(LOSS_WAVES * 64) ign_loss_wide_kernel(const float* __restrict__ s, const float* __restrict__ d,
+                                                                        const long long* __restrict__ y, float* __restrict__ out,
+                                                                        float* __restrict__ eta_out, float* __restrict__ loss2,
+                                                                        float* __restrict__ gs, float* __restrict__ gd, int B, int N,
+                                                                        float beta, const float* __restrict__ reg) {
+    __shared__ float ce[2][LOSS_TILE];
+    __shared__ float tot[2];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float invB = 1.f / (float)B;
+    if (threadIdx.x == 0) { tot[0] = 0.f; tot[1] = 0.f; }
+    for (int base = 0; base < B; base += LOSS_TILE) {
+        const int rows = min(LOSS_TILE, B - base);
+        for (int r = wave; r < rows; r += LOSS_WAVES) {
+            const int b = base + r;
+            const float* sr = s + (long long)b * N;
+            const float* dr = d + (long long)b * N;
+            const int yb = (int)y[b];
+            float sv[LOSS_KMAX], dv[LOSS_KMAX], q[LOSS_KMAX], ov[LOSS_KMAX], eo[LOSS_KMAX];
+            float mx = -INFINITY;
+#pragma unroll
+            for (int k = 0; k < LOSS_KMAX; ++k) {
+                const int n = k * 64 + lane;
+                sv[k] = n < N ? sr[n] : -INFINITY;
+                dv[k] = n < N ? dr[n] : 0.f;
+                mx = fmaxf(mx, sv[k]);
+            }
+            mx = wave_max(mx);
+            float z = 0.f, z2 = 0.f;
+#pragma unroll
+            for (int k = 0; k < LOSS_KMAX; ++k) {
+                q[k] = k * 64 + lane < N ? expf(sv[k] - mx) : 0.f;
+                z += q[k];
+                z2 += q[k] * q[k];
+            }
+            z = wave_sum(z);
+            z2 = wave_sum(z2);
+            const float G = z2 / (z * z);
+            const float eta = ((float)N * G - 1.f) / (float)(N - 1);
+            if (lane == 0) eta_out[b] = eta;
+            float mo = -INFINITY, s_y = 0.f, o_y = 0.f;
+#pragma unroll
+            for (int k = 0; k < LOSS_KMAX; ++k) {
+                const int n = k * 64 + lane;
+                ov[k] = eta * sv[k] + (1.f - eta) * dv[k];
+                if (n < N) {
+                    out[(long long)b * N + n] = ov[k];
+                    mo = fmaxf(mo, ov[k]);
+                }
+                if (n == yb) { s_y = sv[k]; o_y = ov[k]; }
+            }
+            mo = wave_max(mo);
+            s_y = wave_sum(s_y);                  // exactly one lane holds the label's logits, the others add zeros
+            o_y = wave_sum(o_y);
+            float zo = 0.f;
+#pragma unroll
+            for (int k = 0; k < LOSS_KMAX; ++k) {
+                eo[k] = k * 64 + lane < N ? expf(ov[k] - mo) : 0.f;
+                zo += eo[k];
+            }
+            zo = wave_sum(zo);
+            // gradients: g_out = (softmax(out) - onehot)/B ; through the gate (see gate_bwd_kernel) ; + beta*(softmax(s) - onehot)/B
+            float dot = 0.f;
+#pragma unroll
+            for (int k = 0; k < LOSS_KMAX; ++k) {
+                const int n = k * 64 + lane;
+                eo[k] = (eo[k] / zo - (n == yb ? 1.f : 0.f)) * invB;          // go
+                if (n < N) dot += eo[k] * (sv[k] - dv[k]);
+            }
+            dot = wave_sum(dot);
+            const float c = 2.f * (float)N / (float)(N - 1) * dot;
+#pragma unroll
+            for (int k = 0; k < LOSS_KMAX; ++k) {
+                const int n = k * 64 + lane;
+                if (n < N) {
+                    const float qn = q[k] / z;
+                    gs[(long long)b * N + n] = eta * eo[k] + c * qn * (qn - G) + beta * (qn - (n == yb ? 1.f : 0.f)) * invB;
+                    gd[(long long)b * N + n] = (1.f - eta) * eo[k];
+                }
+            }
+            if (lane == 0) {
+                ce[0][r] = mo + logf(zo) - o_y;
+                ce[1][r] = mx + logf(z) - s_y;
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int i = 0; i < rows; ++i) { tot[0] += ce[0][i]; tot[1] += ce[1][i]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float a = tot[0], b2 = tot[1];
+        loss2[0] = a * invB;
+        loss2[1] = b2 * invB;
+        loss2[2] = a * invB + beta * (b2 * invB) + (reg ? reg[0] : 0.f);        // + info.loss.mean() (exp:325-329)
+    }
+}
+
 extern "C" int ign_loss_fwd_bwd_reg(const float* sbm, const float* dnn, const long long* labels, const float* reg, float* out,
                                     float* eta, float* loss2, float* gsbm, float* gdnn, int B, int N, float beta, void* stream) {
-    if (!sbm || !dnn || !labels || !out || !eta || !loss2 || !gsbm || !gdnn || B <= 0 || N < 2 || N > LOSS_NMAX) {
-        ign_set_error("ign_loss_fwd_bwd: null pointer or bad dimension (B=%d N=%d, N <= %d)", B, N, LOSS_NMAX);
+    if (!sbm || !dnn || !labels || !out || !eta || !loss2 || !gsbm || !gdnn || B <= 0 || N < 2) {
+        ign_set_error("ign_loss_fwd_bwd: null pointer or bad dimension (B=%d N=%d, N <= %d)", B, N, IGN_HEAD_NMAX);
         return IGN_E_ARG;
+    }
+    if (N > IGN_HEAD_NMAX) { ign_set_error("ign_loss_fwd_bwd: N=%d classes > %d", N, IGN_HEAD_NMAX); return IGN_E_UNSUP; }
+    if (N > LOSS_NMAX) {
+        hipLaunchKernelGGL(ign_loss_wide_kernel, dim3(1), dim3(LOSS_WAVES * 64), 0, (hipStream_t)stream, sbm, dnn, labels, out, eta,
+                           loss2, gsbm, gdnn, B, N, beta, reg);
+        return ign_check_launch("ign_loss_wide_kernel");
     }
     hipLaunchKernelGGL(ign_loss_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, sbm, dnn, labels, out, eta, loss2, gsbm, gdnn, B, N,
                        beta, reg);
@@ -366,13 +523,18 @@ extern "C" int ign_head_fwd(const float* X, const float* W, const float* bias, f
         ign_set_error("ign_head_fwd: null pointer or bad dimension (B=%d F=%d N=%d ldx=%lld)", B, F, N, ldx);
         return IGN_E_ARG;
     }
-    if (N > HEAD_NMAX) { ign_set_error("ign_head_fwd: N=%d classes > %d", N, HEAD_NMAX); return IGN_E_UNSUP; }
+    if (N > IGN_HEAD_NMAX) { ign_set_error("ign_head_fwd: N=%d classes > %d", N, IGN_HEAD_NMAX); return IGN_E_UNSUP; }
     if ((ldx & 3) || ((uintptr_t)X & 15) || ((uintptr_t)W & 15) || (F & 3)) {
         ign_set_error("ign_head_fwd: X/W must be 16-byte aligned with F and ldx multiples of 4 (F=%d ldx=%lld)", F, ldx);
         return IGN_E_ARG;
     }
     IgnScopedTimer tm("head_fwd", (hipStream_t)stream);
-    hipLaunchKernelGGL(head_fwd_kernel, dim3(B), dim3(F >= 32768 ? 1024 : 256), 0, (hipStream_t)stream, X, W, bias, out, B, F, N, ldx);
+    const dim3 blk(F >= 32768 ? 1024 : 256);
+    if (N <= HEAD_NMAX)
+        hipLaunchKernelGGL(head_fwd_kernel<false>, dim3(B), blk, 0, (hipStream_t)stream, X, W, bias, out, B, F, N, ldx);
+    else
+        hipLaunchKernelGGL(head_fwd_kernel<true>, dim3(B, (N + HEAD_NMAX - 1) / HEAD_NMAX), blk, 0, (hipStream_t)stream, X, W, bias,
+                           out, B, F, N, ldx);
     return ign_check_launch("head_fwd_kernel");
 }
 
@@ -387,30 +549,45 @@ extern "C" int ign_head_bwd_acc(const float* g, const float* X, const float* W, 
         ign_set_error("ign_head_bwd: null pointer or bad dimension");
         return IGN_E_ARG;
     }
-    if (N > HEAD_NMAX) { ign_set_error("ign_head_bwd: N=%d classes > %d", N, HEAD_NMAX); return IGN_E_UNSUP; }
+    if (N > IGN_HEAD_NMAX) { ign_set_error("ign_head_bwd: N=%d classes > %d", N, IGN_HEAD_NMAX); return IGN_E_UNSUP; }
     if ((ldx & 3) || (F & 3) || ((uintptr_t)W & 15) || (gX && ((uintptr_t)gX & 15))) {
         ign_set_error("ign_head_bwd: W/gX must be 16-byte aligned with F and ldx multiples of 4");
         return IGN_E_ARG;
     }
-    if ((size_t)B * N * 4 > 40 * 1024) { ign_set_error("ign_head_bwd: B*N=%d too large for the LDS copy of g", B * N); return IGN_E_TOOBIG; }
+    // the weight gradient stages g in LDS: all of it for N <= 16, one 16-class chunk of it (B x 16) above
+    const bool wide = N > HEAD_NMAX;
+    const int gsn = wide ? HEAD_NMAX : N, nch = (N + HEAD_NMAX - 1) / HEAD_NMAX;
+    if ((size_t)B * gsn * 4 > 40 * 1024) { ign_set_error("ign_head_bwd: B*N=%d too large for the LDS copy of g", B * gsn); return IGN_E_TOOBIG; }
+    const size_t lds = ((size_t)B * gsn + 8 * HEAD_NMAX * 32) * 4;
     hipStream_t s = (hipStream_t)stream;
     int rc;
     if (gX && gW) {
-        const int nwb = (F + 31) / 32, nxb = (F / 4 + 255) / 256;
+        const int nfb = (F + 31) / 32, nxb = (F / 4 + 255) / 256;
         IgnScopedTimer tm("head_bwd_xw", s);
-        hipLaunchKernelGGL(head_bwd_xw_kernel, dim3((unsigned)(nwb + nxb * B)), dim3(256), ((size_t)B * N + 8 * HEAD_NMAX * 32) * 4, s, g, X,
-                           W, gX, gW, gbias, B, F, N, ldx, gW_add, add_scale_dev, nwb, nxb);
+        if (!wide)
+            hipLaunchKernelGGL(head_bwd_xw_kernel<false>, dim3((unsigned)(nfb + nxb * B)), dim3(256), lds, s, g, X, W, gX, gW, gbias, B,
+                               F, N, ldx, gW_add, add_scale_dev, nfb, nxb);
+        else
+            hipLaunchKernelGGL(head_bwd_xw_kernel<true>, dim3((unsigned)(nfb * nch + nxb * B)), dim3(256), lds, s, g, X, W, gX, gW,
+                               gbias, B, F, N, ldx, gW_add, add_scale_dev, nfb * nch, nxb);
         return ign_check_launch("head_bwd_xw_kernel");
     }
     if (gX) {
         IgnScopedTimer tm("head_bwd_x", s);
-        hipLaunchKernelGGL(head_bwd_x_kernel, dim3((F / 4 + 255) / 256, B), dim3(256), 0, s, g, W, gX, B, F, N, ldx);
+        if (!wide)
+            hipLaunchKernelGGL(head_bwd_x_kernel<false>, dim3((F / 4 + 255) / 256, B), dim3(256), 0, s, g, W, gX, B, F, N, ldx);
+        else
+            hipLaunchKernelGGL(head_bwd_x_kernel<true>, dim3((F / 4 + 255) / 256, B), dim3(256), 0, s, g, W, gX, B, F, N, ldx);
         if ((rc = ign_check_launch("head_bwd_x_kernel"))) return rc;
     }
     if (gW) {
         IgnScopedTimer tm("head_bwd_w", s);
-        hipLaunchKernelGGL(head_bwd_w_kernel, dim3((F + 31) / 32), dim3(256), ((size_t)B * N + 8 * HEAD_NMAX * 32) * 4, s, g, X, gW, gbias, B, F, N, ldx,
-                           gW_add, add_scale_dev);
+        if (!wide)
+            hipLaunchKernelGGL(head_bwd_w_kernel<false>, dim3((F + 31) / 32), dim3(256), lds, s, g, X, gW, gbias, B, F, N, ldx, gW_add,
+                               add_scale_dev);
+        else
+            hipLaunchKernelGGL(head_bwd_w_kernel<true>, dim3((F + 31) / 32, nch), dim3(256), lds, s, g, X, gW, gbias, B, F, N, ldx,
+                               gW_add, add_scale_dev);
         if ((rc = ign_check_launch("head_bwd_w_kernel"))) return rc;
     }
     return 0;

@@ -14,7 +14,7 @@ import os
 
 import torch
 
-from . import _lib
+from . import _lib, ops
 
 
 # Arithmetic of the forward / data-gradient GEMMs (the weight gradient is fp32 MFMA in both):
@@ -340,7 +340,7 @@ class FcnBodyFn(torch.autograd.Function):
 def fcn_body(x, blocks, math=None, head=None):
     """x (B,T,C) float32 on the GPU; blocks = [(conv1d, batchnorm1d), ...] -> pooled (B, C_last).
     `math`: arithmetic of the GEMMs (see CONV_MATH); default = "bf16" inside an autocast region, else CONV_MATH.
-    `head`: an nn.Linear over the pooled channels (<= 16 outputs) -> its logits (B, N) are returned instead, computed by the
+    `head`: an nn.Linear over the pooled channels (<= ops.HEAD_NMAX outputs) -> its logits (B, N) are returned instead, computed by the
     pooling launch."""
     if math is None:
         math = "bf16" if torch.is_autocast_enabled() else CONV_MATH
@@ -353,8 +353,8 @@ def fcn_body(x, blocks, math=None, head=None):
             raise _lib.IgnError("fcn_body: only stride-1, unpadded, undilated, ungrouped Conv1d is implemented")
         params += [conv.weight, conv.bias, bn.weight, bn.bias]
     if head is not None:
-        if head.weight.shape[0] > 16:
-            raise _lib.IgnError("fcn_body: the fused head covers up to 16 outputs")
+        if head.weight.shape[0] > ops.HEAD_NMAX:
+            raise _lib.IgnError(f"fcn_body: the fused head covers up to {ops.HEAD_NMAX} outputs")
         # (a head without bias passes a None placeholder: autograd.Function accepts non-tensor inputs)
         return FcnBodyFn.apply(x, (states, math, True), *params, head.weight, head.bias)
     return FcnBodyFn.apply(x, (states, math, False), *params)

@@ -13,6 +13,18 @@ ATTN_MATH = os.environ.get("IGN_ATTN_MATH", "bf16x6")          # "f32": attentio
 LAYERNORM_MIN_ROWS = 0        # round 1 kept torch below 64k rows; with the row-count-aware grid and the parallel reduce the HIP kernels win everywhere
 LINEAR_WGRAD = "bf16x6"       # weight gradient of ops.linear on the split kernels; "f32" (set by tests / diag scripts): the fp32-MFMA TN kernel
 GATE_RBF, GATE_LTS = 0x00, 0x10
+HEAD_NMAX = 256               # IGN_HEAD_NMAX (include/ign_abi.h): widest class head of ign_head_* / ign_loss_*
+HEAD_WIDE_BMAX = 640          # batch bound of ign_head_bwd above 16 classes (one 16-class chunk of the logit gradient in 40 KB of LDS)
+
+
+def head_fits(B, N):
+    """Whether ign_head_fwd / ign_head_bwd take a (B, N) head.  N <= 16 keeps its own rule (checked by the kernel)."""
+    return N <= 16 or (N <= HEAD_NMAX and B <= HEAD_WIDE_BMAX)
+
+
+def _check_classes(name, n):
+    if n > HEAD_NMAX:
+        raise _lib.IgnError(f"{name}: N={n} classes > {HEAD_NMAX}, the widest class head the HIP kernels take (IGN_HEAD_NMAX)")
 
 
 def _ptr(t):
@@ -271,6 +283,7 @@ class SbmFn(torch.autograd.Function):
         out = None
         if fuse_head:
             N, F_ = W.shape
+            _check_classes("sbm head", N)
             out = torch.empty(B, N, device=xn.device, dtype=torch.float32)
             _lib.check(L.ign_head_fwd(_ptr(P), _ptr(W), None, _ptr(out), B, F_, N, P.stride(0), _stream()), "ign_head_fwd")
         ctx.set_materialize_grads(False)
@@ -557,7 +570,7 @@ def head_linear(x, w, bias=None):
     (still on the GPU; CPU tensors are refused)."""
     if not x.is_cuda:
         raise _lib.IgnError(f"head_linear: tensor on {x.device}; the product path runs on the MI355X only (no CPU fallback)")
-    if x.dim() != 2 or x.shape[1] % 4 or w.shape[0] > 16 or x.dtype != torch.float32 \
+    if x.dim() != 2 or x.shape[1] % 4 or not head_fits(x.shape[0], w.shape[0]) or x.dtype != torch.float32 \
             or w.dtype != torch.float32 or torch.is_autocast_enabled():
         return torch.nn.functional.linear(x, w, bias)
     return HeadLinearFn.apply(x, w, bias)
@@ -1154,6 +1167,7 @@ class IgnLossFn(torch.autograd.Function):
         sbm, dnn = sbm.contiguous(), dnn.contiguous()
         y = y.contiguous().long()
         B, N = sbm.shape
+        _check_classes("ign_loss", N)
         out = torch.empty_like(sbm)
         gsd = torch.empty(2, B, N, device=sbm.device, dtype=torch.float32)       # (d loss / d sbm, d loss / d dnn), one buffer
         eta = torch.empty(B, 1, device=sbm.device, dtype=torch.float32)

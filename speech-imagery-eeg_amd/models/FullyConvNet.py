@@ -32,6 +32,6 @@ class FullyConvNetwork(nn.Module):
         # handed to a library convolution
         x = x if x.dtype == torch.float32 else x.float()
         blocks = [(b[0], b[1]) for b in (self.block1, self.block2, self.block3)]
-        if self.fc.weight.shape[0] <= 16 and not torch.is_autocast_enabled():
+        if ops.head_fits(x.shape[0], self.fc.weight.shape[0]) and not torch.is_autocast_enabled():
             return fcn.fcn_body(x, blocks, head=self.fc)            # class head inside the pooling launch
         return ops.head_linear(fcn.fcn_body(x, blocks), self.fc.weight, self.fc.bias)
