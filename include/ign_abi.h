@@ -289,6 +289,19 @@ int ign_loss_fwd_bwd(const float* sbm, const float* dnn, const long long* labels
 int ign_loss_fwd_bwd_reg(const float* sbm, const float* dnn, const long long* labels, const float* reg, float* out, float* eta,
                          float* loss2, float* gsbm, float* gdnn, int B, int N, float beta, void* stream);
 
+/* Regression loss tail (IGN/exp/experiment_regression.py:59-76): CRPS of the softmax CDF over N bins against the step CDF
+ * H_j = [edges[j] >= target] (compared in float64; edges may hold +-inf, a target on an edge counts as >=), batch mean, and
+ * its gradient w.r.t. the logits, in one launch.  logits / grad (B,N) fp32, target (B) fp32, edges (N) fp64, loss_out (1).
+ * 2 <= N <= IGN_HEAD_NMAX, any B >= 1; one block, per-row losses summed in row order (bitwise repeatable); no allocation.  */
+int ign_crps_fwd_bwd(const float* logits, const float* target, const double* edges, float* loss_out, float* grad,
+                     int B, int N, void* stream);
+/* InterpGN's regression tail in one launch (IGN/exp/experiment_regression.py:159-169): out / eta = the gini gate of
+ * ign_gate_fwd (bitwise the same), loss3 = {CRPS(out), CRPS(sbm), CRPS(out) + beta*CRPS(sbm) + reg[0]} (`reg` nullable),
+ * gsbm / gdnn = d(CRPS(out) + beta*CRPS(sbm)) / d logits through the gate.  Limits and order as ign_crps_fwd_bwd.          */
+int ign_loss_crps_fwd_bwd_reg(const float* sbm, const float* dnn, const float* target, const double* edges, const float* reg,
+                              float* out, float* eta, float* loss3, float* gsbm, float* gdnn, int B, int N, float beta,
+                              void* stream);
+
 /* Shapelet diversity regulariser of one length group, forward and gradient in one launch.
  * Replaces IGN/model/Shapelet.py:223-230:  mean_{c,i,j} exp(-||w[i,c,:] - w[j,c,:] + eps||_2) (1 - delta_ij), eps = 1e-6.
  * loss_part_c (C): per-channel partial sums (their sum is the group's loss); gw_kcl (K,C,L): d loss / d w.  K <= 16.  */

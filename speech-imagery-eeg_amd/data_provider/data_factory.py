@@ -1,24 +1,27 @@
-"""``data_provider(args, flag) -> (Dataset, DataLoader)`` -- the loader contract of
-IGN/data_factory/data_factory.py:29-121 for the classification task.
+"""``data_provider(args, flag, bin_edges=None) -> (Dataset, DataLoader)`` -- the loader contract of
+IGN/data_factory/data_factory.py:29-137 for the classification and regression tasks.
 
 Batches are ``(X[B, T, C] float32, y[B, 1], mask[B, T] bool)``.  Registry keys follow the reference
-(``UEA``, ``EEG``, ``EEG3``); ``SYNTH`` is the synthetic benchmark provider.  Under ``torch.distributed`` each
+(``UEA``, ``EEG``, ``EEG3``, ``Monash``); ``SYNTH`` is the synthetic benchmark provider.  Under ``torch.distributed`` each
 rank iterates a disjoint, equally sized slice of a shared permutation (ign_hip.ddp.shard_indices).
 """
 import torch
 import torch.distributed as dist
 from torch.utils.data import DataLoader, Sampler
 
-from data_provider.data_loader import UEAloader
+import functools
+
+from data_provider.data_loader import Monashloader, UEAloader
 from data_provider.eeg_npy import EEGNpyDataset, EEGNpyDataset3Class, collate_raw
 from data_provider.synthetic import SyntheticEEG
-from data_provider.uea import collate_fn
+from data_provider.uea import collate_fn, collate_subsampled
 
 data_dict = {
     'UEA': UEAloader,
     'EEG': EEGNpyDataset,           # 39 classes
     'EEG3': EEGNpyDataset3Class,    # 3 classes
     'SYNTH': SyntheticEEG,
+    'Monash': Monashloader,         # regression (float targets)
 }
 
 
@@ -42,9 +45,11 @@ class RankShardSampler(Sampler):
 
 def data_provider(args, flag, bin_edges=None):
     flag = flag.lower()
+    if args.task_name == 'regression':
+        return _regression_provider(args, flag, bin_edges)
     if args.task_name != 'classification':
-        raise NotImplementedError(f"task_name={args.task_name!r}: only the classification path is rebuilt "
-                                  f"(SURVEY section 2 marks forecasting / anomaly / regression out of scope)")
+        raise NotImplementedError(f"task_name={args.task_name!r}: only the classification and regression paths are rebuilt "
+                                  f"(SURVEY section 2 marks forecasting / anomaly out of scope)")
     if args.data not in data_dict:
         raise KeyError(f"--data {args.data!r} not in {sorted(data_dict)}")
     Data = data_dict[args.data]
@@ -77,4 +82,24 @@ def data_provider(args, flag, bin_edges=None):
                         num_workers=args.num_workers, drop_last=False, pin_memory=torch.cuda.is_available(),
                         collate_fn=collate_raw if raw else (lambda b: collate_fn(b, max_len=max_len)))
     loader.device_transform = 'standardise_raw' if raw else None
+    return data_set, loader
+
+
+def _regression_provider(args, flag, bin_edges):
+    """IGN/data_factory/data_factory.py:123-137.  `bin_edges`: None for the train split (the loader derives them), the train
+    split's edges for val / test.  Every batch is padded / clipped to the dataset's max_seq_len and subsampled with the
+    dataset's one stride (repair R2: the reference clips later batches to the first batch's subsampled length).  --batch_size
+    also for test (the reference evaluates one series at a time; eval-mode outputs do not depend on the batch here)."""
+    if args.data != 'Monash':
+        raise KeyError(f"--data {args.data!r}: the regression task reads the Monash archive (--data Monash)")
+    data_set = Monashloader(root_path=args.root_path, flag=flag, bin_edges=bin_edges)
+    sampler = None
+    shuffle = flag == 'train'
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 and flag == 'train':
+        sampler = RankShardSampler(len(data_set), dist.get_rank(), dist.get_world_size(), shuffle,
+                                   seed=max(0, getattr(args, 'seed', 0)))
+    loader = DataLoader(data_set, batch_size=args.batch_size, shuffle=(shuffle and sampler is None), sampler=sampler,
+                        num_workers=args.num_workers, drop_last=False, pin_memory=torch.cuda.is_available(),
+                        collate_fn=functools.partial(collate_subsampled, max_len=data_set.max_seq_len, stride=data_set.stride))
+    loader.device_transform = None
     return data_set, loader

@@ -3,9 +3,10 @@
 installed here -- SURVEY D13).
 
 Format: ``#`` comments; ``@key value`` header lines (``@problemName``, ``@timeStamps``, ``@missing``,
-``@univariate``, ``@dimensions``, ``@equalLength``, ``@seriesLength``, ``@classLabel true a b c``); ``@data``;
-then one case per line: ``dim_1:dim_2:...:dim_D:label`` where each ``dim_i`` is a comma-separated series and
-``?`` marks a missing value.  Only the un-timestamped form used by the UEA multivariate archive is supported.
+``@univariate``, ``@dimensions``, ``@equalLength``, ``@seriesLength``, ``@classLabel true a b c``, or
+``@targetLabel true`` for the Monash regression archive); ``@data``; then one case per line:
+``dim_1:dim_2:...:dim_D:label`` where each ``dim_i`` is a comma-separated series and ``?`` marks a missing value.
+Only the un-timestamped form used by the UEA multivariate archive is supported.
 """
 import numpy as np
 
@@ -16,11 +17,13 @@ class TsFormatError(ValueError):
 
 def load_ts(path, missing="NaN"):
     """-> (cases, labels, meta): cases = list over samples of list over dimensions of float64 arrays,
-    labels = list of str (or None when the file has no class label)."""
+    labels = list of str class labels, or -- for a ``@targetLabel true`` file without class labels -- list of float
+    regression targets (None when the file has neither).  A file that carries both tags is read as classification."""
     meta = {}
     cases, labels = [], []
     in_data = False
     has_label = False
+    has_target = False
     with open(path, "r", encoding="utf-8") as f:
         for lineno, raw in enumerate(f, 1):
             line = raw.strip()
@@ -34,6 +37,7 @@ def load_ts(path, missing="NaN"):
                 if key == "data":
                     in_data = True
                     has_label = bool(meta.get("classlabel", [False])[0])
+                    has_target = not has_label and str(meta.get("targetlabel", "false")).lower() == "true"
                     continue
                 if key == "classlabel":
                     flag = len(parts) > 1 and parts[1].lower() == "true"
@@ -49,6 +53,12 @@ def load_ts(path, missing="NaN"):
             if has_label:
                 labels.append(fields[-1].strip())
                 fields = fields[:-1]
+            elif has_target:
+                try:
+                    labels.append(float(fields[-1]))
+                except ValueError:
+                    raise TsFormatError(f"{path}:{lineno}: target {fields[-1].strip()[:40]!r} is not a number") from None
+                fields = fields[:-1]
             dims = []
             for fld in fields:
                 vals = [v.strip() for v in fld.split(",")]
@@ -62,14 +72,15 @@ def load_ts(path, missing="NaN"):
     ndim = {len(c) for c in cases}
     if len(ndim) > 1:
         raise TsFormatError(f"{path}: inconsistent number of dimensions per case {sorted(ndim)}")
-    return cases, (labels if has_label else None), meta
+    return cases, (labels if has_label or has_target else None), meta
 
 
-def write_ts(path, X, y, problem="synthetic", class_labels=None):
+def write_ts(path, X, y, problem="synthetic", class_labels=None, regression=False):
     """Write (n, C, T) data (or a list of (C, T_i) arrays for ragged series) in UEA ``.ts`` format -- used to
-    build BasicMotions-shaped fixtures for tests (the real archive cannot be fetched: no network)."""
-    labels = [str(v) for v in y]
-    classes = class_labels or sorted(set(labels))
+    build BasicMotions-shaped fixtures for tests (the real archive cannot be fetched: no network).  `regression`: `y`
+    are real-valued targets, written under ``@targetLabel true`` as the Monash archive does."""
+    labels = [repr(float(v)) for v in y] if regression else [str(v) for v in y]
+    classes = None if regression else (class_labels or sorted(set(labels)))
     lens = {np.asarray(x).shape[-1] for x in X}
     with open(path, "w", encoding="utf-8") as f:
         f.write(f"@problemName {problem}\n@timeStamps false\n@missing false\n")
@@ -77,7 +88,7 @@ def write_ts(path, X, y, problem="synthetic", class_labels=None):
         f.write(f"@dimensions {np.asarray(X[0]).shape[0]}\n@equalLength {'true' if len(lens) == 1 else 'false'}\n")
         if len(lens) == 1:
             f.write(f"@seriesLength {lens.pop()}\n")
-        f.write("@classLabel true " + " ".join(classes) + "\n@data\n")
+        f.write("@targetLabel true\n@data\n" if regression else "@classLabel true " + " ".join(classes) + "\n@data\n")
         for x, lab in zip(X, labels):
             x = np.asarray(x)
             f.write(":".join(",".join(repr(float(v)) for v in row) for row in x) + ":" + lab + "\n")

@@ -25,6 +25,20 @@ def collate_fn(data, max_len=None):
     return X, targets, padding_mask(torch.tensor(lengths), max_len)
 
 
+def subsample_stride(T, limit=1000):
+    """The one subsampling stride of a regression dataset whose series pad to T samples: ceil(T / limit) from T >= limit on
+    (the rule of IGN/exp/experiment_regression.py:32-37, applied with a fixed T -- repair R2)."""
+    return -(-int(T) // limit) if T >= limit else 1
+
+
+def collate_subsampled(data, max_len, stride):
+    """collate_fn to exactly max_len samples, then every `stride`-th time step of the batch and of its padding mask."""
+    X, targets, mask = collate_fn(data, max_len=max_len)
+    if stride > 1:
+        X, mask = X[:, ::stride].contiguous(), mask[:, ::stride].contiguous()
+    return X, targets, mask
+
+
 class Normalizer:
     """Feature normalisation over ALL time steps of ALL samples ('standardization', 'minmax') or per sample
     ('per_sample_std', 'per_sample_minmax') -- IGN/data_factory/uea.py:58-107, on numpy instead of pandas.

@@ -82,9 +82,7 @@ class Experiment(object):
         else:
             self.device = torch.device('cpu')
 
-        self.train_data, self.train_loader = data_provider(args, flag="train")
-        self.val_data, self.val_loader = data_provider(args, flag="val")
-        self.test_data, self.test_loader = data_provider(args, flag="test")
+        self._load_data()
         self._get_params_from_data()
         # host -> device double buffering (and, for raw CHISCO shards, the on-GPU standardise + transpose)
         self.train_loader, self.val_loader, self.test_loader = (self._prefetch(l) for l in
@@ -112,6 +110,11 @@ class Experiment(object):
         print(f"Experiment: model={args.model} dnn={getattr(args, 'dnn_type', None)} device={self.device} "
               f"world={self.world} seq_len={args.seq_len} enc_in={args.enc_in} num_class={args.num_class} "
               f"train/val/test={len(self.train_data)}/{len(self.val_data)}/{len(self.test_data)}")
+
+    def _load_data(self):
+        self.train_data, self.train_loader = data_provider(self.args, flag="train")
+        self.val_data, self.val_loader = data_provider(self.args, flag="val")
+        self.test_data, self.test_loader = data_provider(self.args, flag="test")
 
     def _sync_buffers(self, src=0):
         """floating-point buffers (BatchNorm running mean / variance) of rank `src` -> every rank"""
@@ -205,18 +208,7 @@ class Experiment(object):
             batch_x, label, padding_mask = self._to_device(batch_x, label, padding_mask)
             with torch.autocast(device_type=self.device.type, dtype=torch.bfloat16, enabled=amp):
                 logits, info = self._forward(batch_x, padding_mask)
-                if a.model == 'InterpGN' and logits.is_cuda and not amp:
-                    # CE(mixture) + info.loss.mean() + beta*CE(sbm) and both logit gradients in one launch (ops.ign_loss)
-                    # instead of ~40 softmax / nll / mean kernels between the forward and the backward pass
-                    beta = compute_beta(epoch, a.train_epochs, a.beta_schedule)
-                    loss = ign_ops.ign_loss(info.shapelet_preds, info.dnn_preds, label, beta, reg=info.loss)[0]
-                else:
-                    loss = F.cross_entropy(logits, label)
-                    if a.model != 'DNN':
-                        loss = loss + info.loss.mean()
-                    if a.model == 'InterpGN':
-                        beta = compute_beta(epoch, a.train_epochs, a.beta_schedule)
-                        loss = loss + beta * F.cross_entropy(info.shapelet_preds, label)
+                loss = self._train_loss(logits, info, label, compute_beta(epoch, a.train_epochs, a.beta_schedule), amp)
             if a.gradient_accumulation_steps > 1:
                 loss = loss / a.gradient_accumulation_steps
             ign_ops.backward(loss)                 # = loss.backward() (a cached unit root gradient on the GPU)
@@ -234,6 +226,20 @@ class Experiment(object):
                     self.optimizer.zero_grad()
             losses.append(loss.detach())
         return losses, train_step
+
+    def _train_loss(self, logits, info, label, beta, amp):
+        """The training loss of one step (IGN/exp/experiment_classification.py:319-329); `beta` weighs InterpGN's SBM term."""
+        a = self.args
+        if a.model == 'InterpGN' and logits.is_cuda and not amp:
+            # CE(mixture) + info.loss.mean() + beta*CE(sbm) and both logit gradients in one launch (ops.ign_loss)
+            # instead of ~40 softmax / nll / mean kernels between the forward and the backward pass
+            return ign_ops.ign_loss(info.shapelet_preds, info.dnn_preds, label, beta, reg=info.loss)[0]
+        loss = F.cross_entropy(logits, label)
+        if a.model != 'DNN':
+            loss = loss + info.loss.mean()
+        if a.model == 'InterpGN':
+            loss = loss + beta * F.cross_entropy(info.shapelet_preds, label)
+        return loss
 
     # -- `--hipgraph`: the same step as above, captured once per (beta, lr) and replayed per batch ---------------------------------
     def _graph_eligible(self, amp):
@@ -263,10 +269,7 @@ class Experiment(object):
 
         def step_fn(batch_x, label, padding_mask):
             logits, info = self._forward(batch_x, padding_mask)
-            if a.model == 'InterpGN':
-                loss = ign_ops.ign_loss(info.shapelet_preds, info.dnn_preds, label, beta, reg=info.loss)[0]
-            else:
-                loss = F.cross_entropy(logits, label) + info.loss.mean()
+            loss = self._train_loss(logits, info, label, beta, False)
             ign_ops.backward(loss)
             self.bucket.allreduce()
             self.optimizer.step()
@@ -309,25 +312,27 @@ class Experiment(object):
                 # BatchNorm running statistics are per rank (each rank saw its own shards); the model that is validated,
                 # early-stopped on and checkpointed is rank 0's, so every rank evaluates THAT one ...
                 self._sync_buffers(0)
-            val_loss, val_acc = self.validation()
+            val_loss, val_acc = self._val_metrics()
             if self.distributed:
                 # ... and the stopping decision is taken from one (val_loss, val_acc) pair: ranks that disagreed by one
                 # flipped argmax would leave the epoch loop at different times and dead-lock in the next all-reduce
-                t = torch.tensor([val_loss, val_acc], dtype=torch.float64, device=self.device)
+                t = torch.tensor([val_loss, 0.0 if val_acc is None else val_acc], dtype=torch.float64, device=self.device)
                 dist.broadcast(t, src=0)
-                val_loss, val_acc = float(t[0]), float(t[1])
+                val_loss, val_acc = float(t[0]), (None if val_acc is None else float(t[1]))
             remain = (time.time() - t_start) * (a.train_epochs - epoch) / (epoch + 1)
             if (epoch + 1) % a.log_interval == 0 and self.rank == 0:
-                print(f"Epoch {epoch + 1}/{a.train_epochs} | Train Loss {train_loss:.4f} | Val Loss {val_loss:.4f} | "
-                      f"Val Acc {val_acc:.4f} | Time Rem {convert_to_hms(remain)}")
+                acc = "" if val_acc is None else f" | Val Acc {val_acc:.4f}"
+                print(f"Epoch {epoch + 1}/{a.train_epochs} | Train Loss {train_loss:.4f} | Val Loss {val_loss:.4f}{acc} | "
+                      f"Time Rem {convert_to_hms(remain)}")
             if a.lr_decay:
                 self.scheduler.step()
             if epoch >= a.min_epochs:
+                score = val_loss if val_acc is None else -val_acc        # early stopping on -val_accuracy; no accuracy: val loss
                 if self.rank == 0:
-                    early_stopping(-val_acc, self.model, self.checkpoint_dir)
+                    early_stopping(score, self.model, self.checkpoint_dir)
                 else:                                           # same decision on every rank, only rank 0 writes
                     early_stopping.save_checkpoint = lambda *_: None
-                    early_stopping(-val_acc, self.model, self.checkpoint_dir)
+                    early_stopping(score, self.model, self.checkpoint_dir)
             self.epoch_stop = epoch
             if early_stopping.early_stop:
                 if self.rank == 0:
@@ -340,6 +345,10 @@ class Experiment(object):
         if os.path.exists(best):
             self.model.load_state_dict(torch.load(best, map_location=self.device, weights_only=True))
         return self.model
+
+    def _val_metrics(self):
+        """-> (val_loss, val_accuracy or None) for the epoch loop of train()."""
+        return self.validation()
 
     def validation(self):
         if len(self.val_loader) == 0:

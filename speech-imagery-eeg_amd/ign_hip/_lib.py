@@ -127,6 +127,8 @@ SIGNATURES = {
     "ign_bn_bwd_apply_amax": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]),
     "ign_head_bwd_acc": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ll, vp]),
     "ign_loss_fwd_bwd_reg": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, cf, vp]),
+    "ign_crps_fwd_bwd": (ci, [vp, vp, vp, vp, vp, ci, ci, vp]),
+    "ign_loss_crps_fwd_bwd_reg": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, cf, vp]),
     "ign_sbm_reg_workspace_bytes": (sz, [ci, ci, ll]),
     "ign_sbm_reg_fwd_bwd": (ci, [vp, vp, ll, cf, ci, vp, vp, vp, vp, ci, cf, cf, vp, vp, vp]),
     "ign_sbm_attn_workspace_bytes": (sz, [ci, ci]),

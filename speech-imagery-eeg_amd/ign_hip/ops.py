@@ -1202,6 +1202,97 @@ def ign_loss(sbm_out, dnn_out, y, beta=1.0, reg=None):
     return IgnLossFn.apply(sbm_out.float(), dnn_out.float(), y, beta, reg)
 
 
+def _crps_inputs(name, logits, target, edges):
+    """-> (fp32 target (B,), fp64 edges (N,)) on the logits' device, checked against the (B, N) logits."""
+    B, N = logits.shape
+    _check_classes(name, N)
+    target = target.reshape(-1).to(device=logits.device, dtype=torch.float32).contiguous()
+    edges = edges.reshape(-1).to(device=logits.device, dtype=torch.float64).contiguous()
+    if target.numel() != B or edges.numel() != N:
+        raise _lib.IgnError(f"{name}: logits {tuple(logits.shape)} need {B} targets and {N} bin edges, "
+                            f"got {target.numel()} and {edges.numel()}")
+    return target, edges
+
+
+def _unit_or_scaled(gl, g):
+    """The saved logit gradient(s) handed out unscaled for the cached unit root of ops.backward(), else scaled by gl."""
+    unit = _UNIT.get(gl.device)
+    return g if (unit is not None and gl.data_ptr() == unit.data_ptr()) else gl * g
+
+
+class CrpsLossFn(torch.autograd.Function):
+    """CRPS(softmax(logits), step CDF of target) (batch mean) with its logit gradient from one launch (ign_crps_fwd_bwd)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, edges):
+        _need_gpu("crps_loss", logits)
+        logits = logits.contiguous()
+        B, N = logits.shape
+        target, edges = _crps_inputs("crps_loss", logits, target, edges)
+        grad = torch.empty_like(logits)
+        loss = torch.empty((), device=logits.device, dtype=torch.float32)
+        _lib.check(_lib.lib().ign_crps_fwd_bwd(_ptr(logits), _ptr(target), _ptr(edges), _ptr(loss), _ptr(grad), B, N, _stream()),
+                   "ign_crps_fwd_bwd")
+        ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gl):
+        (grad,) = ctx.saved_tensors
+        return _unit_or_scaled(gl, grad), None, None
+
+
+def crps_loss(logits, target, edges):
+    """CRPSLoss of IGN/exp/experiment_regression.py:59-76: mean_b sum_j (cumsum(softmax(logits))_bj - [edges_j >= target_b])^2.
+    target (B,) or (B, 1), real-valued (compared in float64, not truncated); edges (N,) with the last one +inf.  Under bf16
+    autocast the logits are cast to fp32 first, as autocast does for softmax / cumsum."""
+    return CrpsLossFn.apply(logits.float(), target, edges)
+
+
+class IgnCrpsLossFn(torch.autograd.Function):
+    """CRPS(gate(sbm, dnn)) + beta * CRPS(sbm) [+ reg] with both logit gradients from one launch (ign_loss_crps_fwd_bwd_reg)."""
+
+    @staticmethod
+    def forward(ctx, sbm, dnn, target, edges, beta, reg):
+        _need_gpu("ign_crps_loss", sbm, dnn, reg)
+        sbm, dnn = sbm.contiguous(), dnn.contiguous()
+        if dnn.shape != sbm.shape:
+            raise _lib.IgnError(f"ign_crps_loss: expert logits {tuple(sbm.shape)} vs {tuple(dnn.shape)}")
+        B, N = sbm.shape
+        target, edges = _crps_inputs("ign_crps_loss", sbm, target, edges)
+        out = torch.empty_like(sbm)
+        gsd = torch.empty(2, B, N, device=sbm.device, dtype=torch.float32)       # (d loss / d sbm, d loss / d dnn), one buffer
+        eta = torch.empty(B, 1, device=sbm.device, dtype=torch.float32)
+        loss3 = torch.empty(3, device=sbm.device, dtype=torch.float32)
+        if reg is not None:
+            reg = reg.contiguous().reshape(-1)
+            if reg.numel() != 1:
+                raise _lib.IgnError(f"ign_crps_loss: the regulariser must be one value, got {tuple(reg.shape)}")
+        _lib.check(_lib.lib().ign_loss_crps_fwd_bwd_reg(_ptr(sbm), _ptr(dnn), _ptr(target), _ptr(edges), _ptr(reg), _ptr(out),
+                                                        _ptr(eta), _ptr(loss3), _ptr(gsd[0]), _ptr(gsd[1]), B, N, float(beta),
+                                                        _stream()), "ign_loss_crps_fwd_bwd_reg")
+        ctx.save_for_backward(gsd)
+        ctx.reg_shape = None if reg is None else tuple(reg.shape)
+        ctx.mark_non_differentiable(out, eta)
+        ctx.set_materialize_grads(False)
+        return loss3[2], out, eta
+
+    @staticmethod
+    def backward(ctx, gl, gout, geta):
+        if gl is None:
+            return None, None, None, None, None, None
+        (gsd,) = ctx.saved_tensors
+        g = _unit_or_scaled(gl, gsd)
+        return g[0], g[1], None, None, None, (gl.reshape(ctx.reg_shape) if ctx.reg_shape is not None else None)
+
+
+def ign_crps_loss(sbm_out, dnn_out, target, edges, beta=1.0, reg=None):
+    """-> (CRPS(mix) + beta*CRPS(sbm) [+ reg], mix, eta): InterpGN's regression training loss
+    (IGN/exp/experiment_regression.py:159-169) in one launch; mix / eta equal ops.gini_gate's bitwise and carry no gradient.
+    `reg`: the model's regulariser value (ModelInfo.loss, one element), added on the device."""
+    return IgnCrpsLossFn.apply(sbm_out.float(), dnn_out.float(), target, edges, beta, reg)
+
+
 class Conv1SumSqFn(torch.autograd.Function):
     """m2[f] = sum_{rows,t} ((w1[f] (*) x_row)[t] - mu[f])^2 without storing the convolution (ign_conv1_sumsq_*).
     d m2 / d mu = -2 sum (y1 - mu) = 0 when mu is the batch mean, which is the only use (BatchNorm-1 of EEG-CNN)."""

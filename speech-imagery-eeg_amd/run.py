@@ -7,6 +7,8 @@ Differences, all repairs of fork defects listed in SURVEY section 0:
   * ``--data`` defaults to ``UEA`` and ``--data_root`` to ``./data/UEA_multivariate`` (the upstream defaults that
     survive as comments in IGN/run.py:68-69), so ``run_uea.sh`` -- which passes neither -- works (D2);
   * ``--data SYNTH`` (+ ``--synthetic n,C,T,classes``) is the synthetic CHISCO-shaped provider of the benchmark;
+  * ``--task_name regression --data Monash`` is the reference's regression twin (exp/experiment_regression.py), with the
+    repairs R1-R3 of DESIGN 2.3;
   * multi-GPU is one process per GPU: ``python -m torch.distributed.run --nproc-per-node N run.py ...``.
 """
 import argparse
@@ -23,17 +25,18 @@ import numpy as np
 import torch
 
 from exp.experiment_classification import Experiment as ClassificationExperiment
+from exp.experiment_regression import Experiment as RegressionExperiment
 
 exp_dict = {
     "classification": ClassificationExperiment,
-    "regression": None,      # Monash regression twin: out of scope; key kept for the registry
+    "regression": RegressionExperiment,      # Monash TSER targets, binned, CRPS loss
 }
 
 
 def build_parser():
     p = argparse.ArgumentParser()
     # data
-    p.add_argument("--data", type=str, default="UEA", choices=['EEG', 'EEG3', 'UEA', 'SYNTH'])
+    p.add_argument("--data", type=str, default="UEA", choices=['EEG', 'EEG3', 'UEA', 'SYNTH', 'Monash'])
     p.add_argument("--data_root", type=str, default="./data/UEA_multivariate")
     p.add_argument("--json_path", type=str, default="./json/textmaps.json")
     p.add_argument("--hipgraph", action="store_true",
@@ -153,11 +156,11 @@ def init_distributed():
 
 def main(argv=None):
     args = get_args(argv)
-    exp_cls = exp_dict[args.task_name]
+    exp_cls = exp_dict.get(args.task_name)
     if exp_cls is None:
-        raise SystemExit(f"task_name={args.task_name!r} is not part of this build (classification only)")
+        raise SystemExit(f"task_name={args.task_name!r} is not part of this build")
     rank = init_distributed()
-    if args.data in ('EEG', 'EEG3', 'UEA') and not os.path.exists(args.root_path):
+    if args.data in ('EEG', 'EEG3', 'UEA', 'Monash') and not os.path.exists(args.root_path):
         raise SystemExit(f"data path does not exist: {args.root_path}")
     seeds = [0, 42, 1234, 8237, 2023] if args.seed == -1 else [args.seed]
     for i, seed in enumerate(seeds):
@@ -182,7 +185,11 @@ def main(argv=None):
         else:
             print("warning: testing a randomly initialised model")
         test_loss, test_metrics, test_df = experiment.test(save_csv=True, result_dir=f"./result/{args.model}")
-        if rank == 0 and test_metrics is not None:
+        if rank == 0 and args.task_name == 'regression':
+            with open(f"{os.path.dirname(ckpt)}/test_results.pkl", 'wb') as f:
+                pickle.dump({'test_loss': test_loss, 'test_df': test_df, 'args': vars(args)}, f)
+            print(f"CRPS: {test_loss:.6f}")
+        elif rank == 0 and test_metrics is not None:
             with open(f"{os.path.dirname(ckpt)}/test_results.pkl", 'wb') as f:
                 pickle.dump({'test_loss': test_loss, 'test_metrics': test_metrics, 'test_df': test_df,
                              'args': vars(args)}, f)
