@@ -32,21 +32,26 @@ CONV_MATH = os.environ.get("IGN_CONV_MATH", "f16x3")
 DEBUG = None       # set to a dict to capture the backward intermediates (tests/diag_fcn.py)
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+_ptr, _stream = ops._ptr, _lib.stream
 
 
-_stream = _lib.stream
+def _slot(slots, off):
+    """Address of float `off` of the float32 tensor `slots` (the operand bounds of the fp16 path); None without one."""
+    return ctypes.c_void_p(slots.data_ptr() + 4 * off) if slots is not None else None
 
 
-def _attached_bound(t):
-    """ops.cached_bound without importing ops (which imports this module)."""
-    cb = getattr(t, "_ign_bound", None)
-    if cb is None or cb[1] != t._version or cb[2] != t.data_ptr():
-        return None
-    if torch.cuda.is_current_stream_capturing() and not (len(cb) > 3 and cb[3]):
-        return None
-    return cb[0]
+def _fcn_arith(math, autocast, states):
+    """The arithmetic (ops.GEMM_*) of the body's GEMMs from fcn_body's `math` argument: the one place that reads CONV_MATH."""
+    if math is None:
+        math = ops.GEMM_BF16 if autocast else CONV_MATH
+    if math == ops.GEMM_H3 and not (all(st.use_batch_stats for st in states) and len(states) <= 8):
+        return ops.GEMM_X6          # running statistics: no hard bound on the normalised activations
+    return math if math in (ops.GEMM_H3, ops.GEMM_X6, ops.GEMM_BF16) else ops.GEMM_F32
+
+
+def _wgrad_arith(arith, k):
+    """The arithmetic of a block's weight gradient: the split kernels where the tap count is instantiated, else fp32 MFMA."""
+    return arith if arith != ops.GEMM_F32 and k in ops.WGRAD_TAPS else ops.GEMM_F32
 
 
 class BnState:
@@ -77,9 +82,9 @@ class FcnBodyFn(torch.autograd.Function):
     """forward(x (B,T,C), states, w1, b1, gamma1, beta1, w2, ..., beta3) -> pooled (B, C3)."""
 
     @staticmethod
-    def forward(ctx, x, states_math, *params):
+    def forward(ctx, x, states_arith, *params):
         L = _lib.lib()
-        states, math, has_head = states_math
+        states, arith, has_head = states_arith
         head_w, head_b = (params[-2], params[-1]) if has_head else (None, None)
         if has_head:
             params = params[:-2]
@@ -91,17 +96,11 @@ class FcnBodyFn(torch.autograd.Function):
         dev = x.device
         f32 = dict(device=dev, dtype=torch.float32)
         need_grad = any(ctx.needs_input_grad[2:2 + len(params)])
-        if math == "f16x3" and not (all(st.use_batch_stats for st in states) and nl <= 8):
-            math = "bf16x6"           # running statistics: no hard bound on the normalised activations
-        h3 = math == "f16x3"
-        x6 = math in ("bf16x6", "bf16", "f16x3")
-        conv_fwd = L.ign_clconv_fwd_bf16 if math == "bf16" else L.ign_clconv_fwd_x6
         slots = zbuf = xbound = None
-        fp = lambda t, off: ctypes.c_void_p(t.data_ptr() + 4 * off)        # address of float `off` of a float32 tensor
         inputs, affine, wds, shapes = [x], [], [], []
         pa = pb = None
         packed = None
-        if x6 and nl <= 8:
+        if arith != ops.GEMM_F32 and nl <= 8:
             # prologue: the weights of every block packed (split into bf16 planes) in ONE launch, which also bumps the
             # BatchNorm step counters of the blocks that track running statistics
             ws_ = [params[4 * l].contiguous() for l in range(nl)]
@@ -114,7 +113,7 @@ class FcnBodyFn(torch.autograd.Function):
             bumps = [st.bump for st in states]
             bump_tab = pv(bumps) if any(b is not None for b in bumps) else None
             dims = (ia(*[w.shape[0] for w in ws_]), ia(*[w.shape[1] for w in ws_]), ia(*[w.shape[2] for w in ws_]))
-            if h3:
+            if arith == ops.GEMM_H3:
                 # operand bounds (4 floats per block: |W|, |block input|, |dL/dy|, spare): weights and the BatchNorm-derived
                 # activation bounds from the parameters in one launch, the raw input's from one pass over x
                 slots = torch.empty(4 * nl, **f32)
@@ -133,9 +132,9 @@ class FcnBodyFn(torch.autograd.Function):
                                           zbuf.numel() if zbuf is not None else 0, _stream()), "ign_fcn_scan")
                 # max |x|: attached to the tensor by a producer that had the batch in its hands (ops.instance_norm when both
                 # experts share a stream), else one pass over x
-                xbound = _attached_bound(x)
+                xbound = ops.cached_bound(x)
                 if xbound is None:
-                    _lib.check(L.ign_absmax(_ptr(x), x.numel(), fp(slots, 1), _stream()), "ign_absmax")
+                    _lib.check(L.ign_absmax(_ptr(x), x.numel(), _slot(slots, 1), _stream()), "ign_absmax")
                     xbound = slots[1:2]
                 _lib.check(L.ign_clconv_pack_weights_h2_multi(nl, pv(ws_), pv(wts), pv(wds_), *dims, bump_tab,
                                                               vpa(*[slots.data_ptr() + 16 * l for l in range(nl)]), _stream()),
@@ -158,30 +157,11 @@ class FcnBodyFn(torch.autograd.Function):
                 raise _lib.IgnError(f"fcn_body block {l + 1}: input {tuple(h.shape)} vs weight {tuple(w.shape)}")
             st = states[l]
             y = torch.empty(B, Tout, Co, **f32)
-            nparts = int(L.ign_clconv_x6_mtiles(B, Tout) if x6 else L.ign_clconv_mtiles(B * Tout))
+            nparts = int(L.ign_clconv_mtiles(B * Tout) if arith == ops.GEMM_F32 else L.ign_clconv_x6_mtiles(B, Tout))
             part = torch.empty(nparts, 2, Co, **f32) if st.use_batch_stats else None
-            want_wd = l > 0 and need_grad
-            if x6:
-                if packed is not None:
-                    wt, wd = packed[0][l], packed[1][l]
-                else:
-                    wt = torch.empty(int(L.ign_clconv_x3_elems(Co, Ci, k)), device=dev, dtype=torch.bfloat16)
-                    wd = torch.empty(int(L.ign_clconv_x3_elems(Ci, Co, k)), device=dev, dtype=torch.bfloat16) if want_wd else None
-                    _lib.check(L.ign_clconv_pack_weights_x3(_ptr(w), _ptr(wt), _ptr(wd), Co, Ci, k, _stream()),
-                               "ign_clconv_pack_weights_x3")
-                if h3:
-                    _lib.check(L.ign_clconv_fwd_h3(_ptr(h), _ptr(wt), _ptr(b), _ptr(pa), _ptr(pb), _ptr(y), _ptr(part),
-                                                   fp(slots, 4 * l + 1) if l else _ptr(xbound), fp(slots, 4 * l), B, Tin, Ci, Co, k,
-                                                   _stream()), "ign_clconv_fwd_h3")
-                else:
-                    _lib.check(conv_fwd(_ptr(h), _ptr(wt), _ptr(b), _ptr(pa), _ptr(pb), _ptr(y), _ptr(part), B, Tin, Ci, Co, k,
-                                        _stream()), "ign_clconv_fwd_x6")
-            else:
-                wt = torch.empty(Co, k * Ci, **f32)
-                wd = torch.empty(Ci, k * Co, **f32) if want_wd else None
-                _lib.check(L.ign_clconv_pack_weights(_ptr(w), _ptr(wt), _ptr(wd), Co, Ci, k, _stream()), "ign_clconv_pack_weights")
-                _lib.check(L.ign_clconv_fwd(_ptr(h), _ptr(wt), _ptr(b), _ptr(pa), _ptr(pb), _ptr(y), _ptr(part), B, Tin, Ci, Co, k,
-                                            _stream()), "ign_clconv_fwd")
+            wt, wd = (packed[0][l], packed[1][l]) if packed is not None else ops._pack_weights(arith, w, l > 0 and need_grad)
+            ops._clconv_fwd(arith, h, wt, b, pa, pb, y, part, (B, Tin, Ci, Co, k), _slot(slots, 4 * l + 1) if l else _ptr(xbound),
+                            _slot(slots, 4 * l))
             a, bb, mean, invstd = (torch.empty(Co, **f32) for _ in range(4))
             if st.use_batch_stats:
                 _lib.check(L.ign_bn_finalize_fwd(_ptr(part), nparts, B * Tout, Co, _ptr(gamma), _ptr(beta), st.eps, st.momentum,
@@ -216,7 +196,7 @@ class FcnBodyFn(torch.autograd.Function):
                        "ign_bn_relu_pool_fwd")
         ctx.head = head
         ctx.head_needs = tuple(ctx.needs_input_grad[-2:]) if has_head else None
-        ctx.saved = (inputs, affine, wds, shapes, [st.use_batch_stats for st in states], math, slots, zbuf, xbound) \
+        ctx.saved = (inputs, affine, wds, shapes, [st.use_batch_stats for st in states], arith, slots, zbuf, xbound) \
             if (need_grad or (has_head and any(ctx.head_needs))) else None
         ctx.body_grad = need_grad
         return out
@@ -228,10 +208,7 @@ class FcnBodyFn(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             raise _lib.IgnError("fcn_body: gradient w.r.t. the input series is not implemented (inputs are data)")
         L = _lib.lib()
-        inputs, affine, wds, shapes, batch_stats, math, slots, zbuf, xbound = ctx.saved
-        h3 = math == "f16x3"
-        x6 = math in ("bf16x6", "bf16", "f16x3")
-        fp = lambda t, off: ctypes.c_void_p(t.data_ptr() + 4 * off)
+        inputs, affine, wds, shapes, batch_stats, arith, slots, zbuf, xbound = ctx.saved
         nl = len(shapes)
         B = inputs[0].shape[0]
         dev = gpool.device
@@ -272,7 +249,7 @@ class FcnBodyFn(torch.autograd.Function):
         _lib.check(L.ign_bn_relu_pool_bwd(_ptr(y), _ptr(gpool), _ptr(a), _ptr(bb), _ptr(mean), _ptr(invstd), _ptr(g), _ptr(part),
                                           B, Tout, Co, _stream()), "ign_bn_relu_pool_bwd")
         # weight-gradient partials of every block are reduced by ONE launch at the end (split-bf16 kernels with k in 2,3,5,8)
-        defer = x6 and all(sh[2] in (2, 3, 5, 8) for sh in shapes) and nl <= 8
+        defer = all(_wgrad_arith(arith, sh[2]) != ops.GEMM_F32 for sh in shapes) and nl <= 8
         deferred = []
         for l in range(nl - 1, -1, -1):
             Co, Ci, k, Tin, Tout = shapes[l]
@@ -285,25 +262,16 @@ class FcnBodyFn(torch.autograd.Function):
             training = 1 if batch_stats[l] else 0
             # (fp16 path: the kernel also takes max |dL/dy| as it writes the tensor -- the bound its two consumers scale by)
             _lib.check(L.ign_bn_bwd_apply_amax(_ptr(g), _ptr(y), _ptr(a), _ptr(mean), _ptr(invstd), _ptr(dbeta), _ptr(dgamma), _ptr(dyp),
-                                               fp(slots, 4 * l + 2) if h3 else None, B, Tout, Co, pad, training, _stream()),
-                       "ign_bn_bwd_apply")
+                                               _slot(slots, 4 * l + 2), B, Tout, Co, pad, training, _stream()),
+                       "ign_bn_bwd_apply_amax")
             if DEBUG is not None:
                 DEBUG[f"g{l}"], DEBUG[f"dyp{l}"], DEBUG[f"dbeta{l}"], DEBUG[f"dgamma{l}"] = g.clone(), dyp.clone(), dbeta.clone(), dgamma.clone()
             del g
             # weight gradient; the operand below is relu(bn(y_{l-1})) recomputed on the fly (raw x for the first block)
             pa, pb = (affine[l - 1][0], affine[l - 1][1]) if l > 0 else (None, None)
-            wx6 = x6 and k in (2, 3, 5, 8)
-            ws_bytes = (L.ign_clconv_wgrad_x6_workspace_bytes if wx6 else L.ign_clconv_wgrad_workspace_bytes)(B, Tin, Ci, Co, k)
-            ws = torch.empty(int(ws_bytes) // 4, **f32)
             dw = torch.empty(Co, Ci, k, **f32)
-            wgrad = (L.ign_clconv_wgrad_bf16 if math == "bf16" else L.ign_clconv_wgrad_x6) if wx6 else L.ign_clconv_wgrad
-            if h3 and wx6:
-                _lib.check(L.ign_clconv_wgrad_h3(_ptr(dyp), pad, _ptr(inputs[l]), _ptr(pa), _ptr(pb), None if defer else _ptr(dw), _ptr(ws),
-                                                 fp(slots, 4 * l + 2), fp(slots, 4 * l + 1) if l else _ptr(xbound), B, Tin, Ci, Co, k, _stream()),
-                           "ign_clconv_wgrad_h3")
-            else:
-                _lib.check(wgrad(_ptr(dyp), pad, _ptr(inputs[l]), _ptr(pa), _ptr(pb), None if defer else _ptr(dw), _ptr(ws), B, Tin,
-                                 Ci, Co, k, _stream()), "ign_clconv_wgrad")
+            ws = ops._clconv_wgrad(_wgrad_arith(arith, k), dyp, pad, inputs[l], pa, pb, None if defer else dw, (B, Tin, Ci, Co, k),
+                                   _slot(slots, 4 * l + 2), _slot(slots, 4 * l + 1) if l else _ptr(xbound))
             if defer:
                 deferred.append((ws, dw, int(L.ign_clconv_wgrad_x6_nsplit(B, Tin, Ci, Co, k)), Co, Ci, k))
             del ws
@@ -315,16 +283,10 @@ class FcnBodyFn(torch.autograd.Function):
             if l > 0:
                 pa_, pb_, pm_, pi_ = affine[l - 1]
                 g = torch.empty(B, Tin, Ci, **f32)
-                nparts = int(L.ign_clconv_x6_mtiles(B, Tin) if x6 else L.ign_clconv_mtiles(B * Tin))
+                nparts = int(L.ign_clconv_mtiles(B * Tin) if arith == ops.GEMM_F32 else L.ign_clconv_x6_mtiles(B, Tin))
                 part = torch.empty(nparts, 2, Ci, **f32)
-                dgrad = (L.ign_clconv_dgrad_bf16 if math == "bf16" else L.ign_clconv_dgrad_x6) if x6 else L.ign_clconv_dgrad
-                if h3:
-                    _lib.check(L.ign_clconv_dgrad_h3(_ptr(dyp), _ptr(wds[l]), _ptr(inputs[l]), _ptr(pa_), _ptr(pb_), _ptr(pm_), _ptr(pi_),
-                                                     _ptr(g), _ptr(part), fp(slots, 4 * l + 2), fp(slots, 4 * l), B, Tin, Ci, Co, k,
-                                                     _stream()), "ign_clconv_dgrad_h3")
-                else:
-                    _lib.check(dgrad(_ptr(dyp), _ptr(wds[l]), _ptr(inputs[l]), _ptr(pa_), _ptr(pb_), _ptr(pm_), _ptr(pi_),
-                                     _ptr(g), _ptr(part), B, Tin, Ci, Co, k, _stream()), "ign_clconv_dgrad")
+                ops._clconv_dgrad(arith, dyp, wds[l], inputs[l], pa_, pb_, pm_, pi_, g, part, (B, Tin, Ci, Co, k),
+                                  _slot(slots, 4 * l + 2), _slot(slots, 4 * l))
             del dyp
         if deferred:
             n = len(deferred)
@@ -339,12 +301,11 @@ class FcnBodyFn(torch.autograd.Function):
 
 def fcn_body(x, blocks, math=None, head=None):
     """x (B,T,C) float32 on the GPU; blocks = [(conv1d, batchnorm1d), ...] -> pooled (B, C_last).
-    `math`: arithmetic of the GEMMs (see CONV_MATH); default = "bf16" inside an autocast region, else CONV_MATH.
+    `math`: arithmetic of the GEMMs (see CONV_MATH, _fcn_arith); default = "bf16" inside an autocast region, else CONV_MATH.
     `head`: an nn.Linear over the pooled channels (<= ops.HEAD_NMAX outputs) -> its logits (B, N) are returned instead, computed by the
     pooling launch."""
-    if math is None:
-        math = "bf16" if torch.is_autocast_enabled() else CONV_MATH
     states = [BnState(bn) for _, bn in blocks]            # (the step counters are bumped by the node's prologue launch)
+    arith = _fcn_arith(math, torch.is_autocast_enabled(), states)
     params = []
     for conv, bn in blocks:
         if conv.bias is None or bn.weight is None or bn.bias is None:
@@ -356,5 +317,5 @@ def fcn_body(x, blocks, math=None, head=None):
         if head.weight.shape[0] > ops.HEAD_NMAX:
             raise _lib.IgnError(f"fcn_body: the fused head covers up to {ops.HEAD_NMAX} outputs")
         # (a head without bias passes a None placeholder: autograd.Function accepts non-tensor inputs)
-        return FcnBodyFn.apply(x, (states, math, True), *params, head.weight, head.bias)
-    return FcnBodyFn.apply(x, (states, math, False), *params)
+        return FcnBodyFn.apply(x, (states, arith, True), *params, head.weight, head.bias)
+    return FcnBodyFn.apply(x, (states, arith, False), *params)

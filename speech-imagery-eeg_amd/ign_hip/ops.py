@@ -363,10 +363,10 @@ def _dropout_seed(p):
 
 def _attn_arith(E, autocast, bwd):
     """The arithmetic (ATTN_MATH_*) of the attention forward (bwd False) or backward at head width E: the one place that reads
-    ATTN_MATH and GEMM_MATH for attention."""
+    ATTN_MATH; the split kernels follow the dense layers (_dense_arith) onto the fp16 planes."""
     if autocast and E <= 64:
         return ATTN_MATH_BF16     # inside an autocast region (the reference's default mode): operands rounded to bf16, one product
-    if ATTN_MATH == "bf16x6" and GEMM_MATH == "f16x3" and E <= 64:
+    if ATTN_MATH == "bf16x6" and _dense_arith(False) == GEMM_H3 and E <= 64:
         return ATTN_MATH_H3       # two fp16 planes of power-of-two-scaled operands, three products; needs the magnitude bounds
     if ATTN_MATH == "bf16x6" and (E <= 64 or not bwd):
         # split-bf16 products on the bf16 matrix cores (fp32 accuracy); the backward up to E = 64 only (E = 128 exceeds its
@@ -695,11 +695,110 @@ def gelu(u):
     return keep_bound(_ActFn.apply(u, True), u)
 
 
-def _gemm(L, bf16):
-    """(forward / input-gradient GEMM, weight-gradient GEMM) entry points: the split-bf16 kernels (fp32 accuracy), or inside a
-    torch.autocast(bfloat16) region -- the reference's default mode -- the same kernels with their operands rounded to bf16 and
-    ONE product per MFMA step (what autocast computes for a matmul; accumulation and outputs stay fp32)."""
-    return (L.ign_clconv_fwd_bf16, L.ign_clconv_wgrad_bf16) if bf16 else (L.ign_clconv_fwd_x6, L.ign_clconv_wgrad_x6)
+# The arithmetics of a dense-layer / convolution GEMM, by the names the knobs use (GEMM_MATH, fcn.CONV_MATH): fp32 MFMA (ign_clconv_*);
+# "bf16x6" (*_x6); the x6 kernels with operands rounded to bf16 and ONE product per MFMA step -- what torch.autocast(bfloat16), the
+# reference's default mode, computes for a matmul; accumulation and outputs stay fp32 (*_bf16); "f16x3", which takes operand bounds (*_h3)
+GEMM_F32, GEMM_X6, GEMM_BF16, GEMM_H3 = "f32", "bf16x6", "bf16", "f16x3"
+WGRAD_TAPS = (2, 3, 5, 8)     # tap counts the multi-tap split weight-gradient kernels (ign_clconv_wgrad_x6 / _bf16 / _h3) exist for
+
+
+def _dense_arith(autocast):
+    """The arithmetic of linear / gelu_linear / conv1d_cl, of the LayerNorm bound hooks and of prepare_linear_weights: the one place
+    that reads GEMM_MATH.  (The FCN body has its own knob and rule: fcn._fcn_arith.)"""
+    if autocast:
+        return GEMM_BF16
+    return GEMM_H3 if GEMM_MATH == "f16x3" else GEMM_X6
+
+
+def _linear_wgrad_split(Ci):
+    """Whether a Linear layer's weight gradient runs on the split kernel (ign_linear_wgrad_*), else fp32 ign_clconv_wgrad, k = 1."""
+    return Ci % 4 == 0 and LINEAR_WGRAD == "bf16x6"
+
+
+def _conv_wgrad_route(k, Ci):
+    """conv1d_cl's weight gradient: "split" (the multi-tap split kernel), "taps" (one Linear-layer weight gradient per tap) or
+    "f32" (ign_clconv_wgrad; k = 1 goes there too)."""
+    if LINEAR_WGRAD != "bf16x6":
+        return "f32"
+    if k in WGRAD_TAPS:
+        return "split"
+    return "taps" if k > 1 and Ci % 4 == 0 else "f32"
+
+
+# One launcher per GEMM kind and its entry point per arithmetic.  `dims` = (B, Tin, Ci, Co, k) as the entry point takes them; the two
+# operand bounds are device pointers (ctypes.c_void_p) and reach the kernel under GEMM_H3 only: otherwise callers pass None.
+_CLCONV_FWD = {GEMM_F32: "ign_clconv_fwd", GEMM_X6: "ign_clconv_fwd_x6", GEMM_BF16: "ign_clconv_fwd_bf16", GEMM_H3: "ign_clconv_fwd_h3"}
+_CLCONV_DGRAD = {GEMM_F32: "ign_clconv_dgrad", GEMM_X6: "ign_clconv_dgrad_x6", GEMM_BF16: "ign_clconv_dgrad_bf16",
+                 GEMM_H3: "ign_clconv_dgrad_h3"}
+_CLCONV_WGRAD = {GEMM_F32: "ign_clconv_wgrad", GEMM_X6: "ign_clconv_wgrad_x6", GEMM_BF16: "ign_clconv_wgrad_bf16",
+                 GEMM_H3: "ign_clconv_wgrad_h3"}
+_LINEAR_WGRAD = {GEMM_X6: "ign_linear_wgrad_x6", GEMM_BF16: "ign_linear_wgrad_bf16", GEMM_H3: "ign_linear_wgrad_h3"}
+
+
+def _clconv_fwd(arith, x, wt, bias, pro_a, pro_b, y, part, dims, b_in=None, b_w=None, amax=None):
+    """y = conv(relu(pro_a x + pro_b), packed weights wt) + bias, BatchNorm partial sums into `part`: the forward of a convolution
+    / dense layer, and every input gradient computed as a forward GEMM on the transposed weights.  `amax` (GEMM_H3): a slot the
+    epilogue maxes max |y| into."""
+    name, tail = _CLCONV_FWD[arith], ()
+    if arith == GEMM_H3:
+        name, tail = (name, (b_in, b_w)) if amax is None else ("ign_clconv_fwd_h3_amax", (b_in, b_w, _ptr(amax)))
+    _lib.check(getattr(_lib.lib(), name)(_ptr(x), _ptr(wt), _ptr(bias), _ptr(pro_a), _ptr(pro_b), _ptr(y), _ptr(part), *tail, *dims,
+                                         _stream()), name)
+
+
+def _clconv_dgrad(arith, dyp, wd, y_in, a_in, b_in, mean_in, invstd_in, g_in, part, dims, b_dy=None, b_w=None):
+    """The FCN body's data gradient with the BatchNorm-backward epilogue of the block below."""
+    name, tail = _CLCONV_DGRAD[arith], ((b_dy, b_w) if arith == GEMM_H3 else ())
+    _lib.check(getattr(_lib.lib(), name)(_ptr(dyp), _ptr(wd), _ptr(y_in), _ptr(a_in), _ptr(b_in), _ptr(mean_in), _ptr(invstd_in),
+                                         _ptr(g_in), _ptr(part), *tail, *dims, _stream()), name)
+
+
+def _wgrad_workspace(arith, dims, device):
+    """The workspace of a weight-gradient launch (_clconv_wgrad, or _linear_wgrad with dims (1, M, Ci, Co, 1))."""
+    size = "ign_clconv_wgrad_workspace_bytes" if arith == GEMM_F32 else "ign_clconv_wgrad_x6_workspace_bytes"
+    return torch.empty(max(1, int(getattr(_lib.lib(), size)(*dims)) // 4), device=device, dtype=torch.float32)
+
+
+def _clconv_wgrad(arith, dyp, dy_pad, x, pro_a, pro_b, dw, dims, b_dy=None, b_x=None):
+    """dW of a convolution from dy (zero-padded by dy_pad rows per side) and relu(pro_a x + pro_b).  dw None (split kernels): the
+    partial slabs stay in the workspace for ign_clconv_wgrad_reduce_multi.  -> the workspace."""
+    name, tail = _CLCONV_WGRAD[arith], ((b_dy, b_x) if arith == GEMM_H3 else ())
+    ws = _wgrad_workspace(arith, dims, dyp.device)
+    _lib.check(getattr(_lib.lib(), name)(_ptr(dyp), dy_pad, _ptr(x), _ptr(pro_a), _ptr(pro_b), _ptr(dw), _ptr(ws), *tail, *dims,
+                                         _stream()), name)
+    return ws
+
+
+def _linear_wgrad(arith, dy, x, dw, db, M, Ci, Co, b_dy=None, b_x=None, ws=None):
+    """dW = dy^T x and (db not None) the bias gradient in one pass over dy (M, Co) and x (M, Ci), on the split kernels.  `ws`: a
+    workspace of (1, M', Ci, Co, 1), M' >= M, to reuse (the per-tap route of conv1d_cl)."""
+    name, tail = _LINEAR_WGRAD[arith], ((b_dy, b_x) if arith == GEMM_H3 else ())
+    if ws is None:
+        ws = _wgrad_workspace(arith, (1, M, Ci, Co, 1), dy.device)
+    _lib.check(getattr(_lib.lib(), name)(_ptr(dy), _ptr(x), _ptr(dw), _ptr(db), _ptr(ws), *tail, M, Ci, Co, _stream()), name)
+
+
+def _pack_weights(arith, w, need_dx, b_w=None):
+    """One layer's weights w (Co, Ci[, k]) in the layout the GEMMs of `arith` read: -> (forward form, transposed tap-reversed form
+    for the input gradient or None).  b_w (GEMM_H3): the weight's magnitude bound, a one-element device tensor."""
+    L = _lib.lib()
+    Co, Ci = w.shape[:2]
+    k = w.shape[2] if w.dim() == 3 else 1
+    if arith == GEMM_F32:
+        wt = torch.empty(Co, k * Ci, device=w.device, dtype=torch.float32)
+        wd = torch.empty(Ci, k * Co, device=w.device, dtype=torch.float32) if need_dx else None
+    else:
+        wt = torch.empty(int(L.ign_clconv_x3_elems(Co, Ci, k)), device=w.device, dtype=torch.bfloat16)
+        wd = torch.empty(int(L.ign_clconv_x3_elems(Ci, Co, k)), device=w.device, dtype=torch.bfloat16) if need_dx else None
+    if arith == GEMM_H3:
+        (v1, i1), name = _tables(1), "ign_clconv_pack_weights_h2_multi"
+        rc = L.ign_clconv_pack_weights_h2_multi(1, v1(w.data_ptr()), v1(wt.data_ptr()), v1(wd.data_ptr()) if need_dx else None,
+                                                i1(Co), i1(Ci), i1(k), None, v1(b_w.data_ptr()), _stream())
+    else:
+        name = "ign_clconv_pack_weights" if arith == GEMM_F32 else "ign_clconv_pack_weights_x3"
+        rc = getattr(L, name)(_ptr(w), _ptr(wt), _ptr(wd), Co, Ci, k, _stream())
+    _lib.check(rc, name)
+    return wt, wd
 
 
 _PREPARED = {}          # (data_ptr, shape) -> (w, version, generation, bound slot, packed forward planes, packed transposed planes)
@@ -711,7 +810,7 @@ def prepare_linear_weights(weights, need_dx=True):
     scan + one packing launch per layer.  `ops.linear` consumes the entry of its weight (once; an entry is valid only for the
     parameter values it was made from: tensor version and _lib.PARAM_GENERATION).  No-op outside the f16x3 arithmetic."""
     _PREPARED.clear()
-    if GEMM_MATH != "f16x3" or torch.is_autocast_enabled():
+    if _dense_arith(torch.is_autocast_enabled()) != GEMM_H3:
         return
     ws = []
     for w in weights:
@@ -754,7 +853,6 @@ def _take_prepared(w, need_dx):
 
 def _linear_forward(ctx, x, w, bias, extra=()):
     """LinearFn.forward; `extra`: tensors saved behind x2 (GeluLinearFn: the pre-activation)."""
-    L = _lib.lib()
     Co, Ci = w.shape
     x2 = x.reshape(-1, Ci)
     x2 = x2 if x2.is_contiguous() else x2.contiguous()
@@ -762,36 +860,19 @@ def _linear_forward(ctx, x, w, bias, extra=()):
     w = w.contiguous()
     dev = x.device
     need_dx = ctx.needs_input_grad[0]
-    ctx.bf16 = torch.is_autocast_enabled()          # autocast region: operands rounded to bf16, one product (see _gemm)
-    ctx.h3 = (not ctx.bf16) and GEMM_MATH == "f16x3"
-    prepared = _take_prepared(w, need_dx) if ctx.h3 else None       # bound + packed planes from the model's prologue launch
-    if prepared is not None:
-        wt3, wd3 = prepared[4], (prepared[5] if need_dx else None)
-    else:
-        wt3 = torch.empty(int(L.ign_clconv_x3_elems(Co, Ci, 1)), device=dev, dtype=torch.bfloat16)
-        wd3 = torch.empty(int(L.ign_clconv_x3_elems(Ci, Co, 1)), device=dev, dtype=torch.bfloat16) if need_dx else None
+    arith = ctx.arith = _dense_arith(torch.is_autocast_enabled())
     y = torch.empty(*x.shape[:-1], Co, device=dev, dtype=torch.float32)    # final shape (not a view: its reshaped views find its bound)
-    ctx.bx = ctx.bw = None
-    if ctx.h3:
-        # two fp16 planes, three products: operand bounds on the device (the input's is inherited from x when x2 is a view)
+    ctx.bx = ctx.bw = prepared = None
+    if arith == GEMM_H3:
+        # operand bounds on the device (the input's is inherited from x when x2 is a view); the weight's bound and packed planes
+        # come from the model's prologue launch (prepare_linear_weights) where there was one
         ctx.bx = tensor_bound(x) if x2.data_ptr() == x.data_ptr() and x.is_contiguous() else tensor_bound(x2)
-        if prepared is not None:
-            ctx.bw = prepared[3]
-        else:
-            ctx.bw = tensor_bound(w)
-            v1, i1 = _tables(1)
-            _lib.check(L.ign_clconv_pack_weights_h2_multi(1, v1(w.data_ptr()), v1(wt3.data_ptr()),
-                                                          v1(wd3.data_ptr()) if need_dx else None, i1(Co), i1(Ci), i1(1), None,
-                                                          v1(ctx.bw.data_ptr()), _stream()), "ign_clconv_pack_weights_h2_multi")
-        # the epilogue also takes max |y|: the operand bound of whatever dense layer / attention core consumes y
-        yb = _new_slot(dev)
-        _lib.check(L.ign_clconv_fwd_h3_amax(_ptr(x2), _ptr(wt3), _ptr(bias), None, None, _ptr(y), None, _ptr(ctx.bx), _ptr(ctx.bw),
-                                            _ptr(yb), 1, M, Ci, Co, 1, _stream()), "ign_clconv_fwd_h3")
-    else:
-        yb = None
-        _lib.check(L.ign_clconv_pack_weights_x3(_ptr(w), _ptr(wt3), _ptr(wd3), Co, Ci, 1, _stream()), "ign_clconv_pack_weights_x3")
-        _lib.check(_gemm(L, ctx.bf16)[0](_ptr(x2), _ptr(wt3), _ptr(bias), None, None, _ptr(y), None, 1, M, Ci, Co, 1, _stream()),
-                   "ign_clconv_fwd_x6")
+        prepared = _take_prepared(w, need_dx)
+        ctx.bw = prepared[3] if prepared is not None else tensor_bound(w)
+    wt3, wd3 = (prepared[4], prepared[5] if need_dx else None) if prepared is not None else _pack_weights(arith, w, need_dx, ctx.bw)
+    # the epilogue also takes max |y|: the operand bound of whatever dense layer / attention core consumes y
+    yb = _new_slot(dev) if arith == GEMM_H3 else None
+    _clconv_fwd(arith, x2, wt3, bias, None, None, y, None, (1, M, Ci, Co, 1), _ptr(ctx.bx), _ptr(ctx.bw), yb)
     ctx.save_for_backward(x2, *extra)
     ctx.wd3, ctx.dims, ctx.has_bias, ctx.xshape = wd3, (M, Ci, Co), bias is not None, x.shape
     ctx.mark_non_differentiable(*([yb] if yb is not None else []))
@@ -804,29 +885,23 @@ def _linear_backward(ctx, gy, gelu=False):
     activation's derivative applied in the epilogue of the input-gradient GEMM (ign_linear_dgrad_gelu_h3) where the shape allows."""
     if gy is None:
         return None, None, None
-    L = _lib.lib()
     x2 = ctx.saved_tensors[0]
     u2 = ctx.saved_tensors[1].reshape(x2.shape) if gelu else None
     M, Ci, Co = ctx.dims
     g2 = gy.reshape(M, Co)
     g2 = g2 if g2.is_contiguous() else g2.contiguous()
     dx = dw = db = None
-    bg = tensor_bound(g2) if ctx.h3 else None
+    arith = ctx.arith
+    bg = tensor_bound(g2) if arith == GEMM_H3 else None
     if ctx.needs_input_grad[0]:
         dx = torch.empty(M, Ci, device=g2.device, dtype=torch.float32)
-        dxb = None
-        fused = gelu and ctx.h3 and Ci % 256 == 0 and Co % 4 == 0 and u2.is_contiguous()
-        if fused:
-            dxb = _new_slot(g2.device)           # dL/du = (g W) * gelu'(u) in one GEMM; its epilogue also takes max |dL/du|
-            _lib.check(L.ign_linear_dgrad_gelu_h3(_ptr(g2), _ptr(ctx.wd3), _ptr(u2), _ptr(dx), _ptr(bg), _ptr(ctx.bw), _ptr(dxb), M, Co, Ci,
-                                                  _stream()), "ign_linear_dgrad_gelu_h3")
-        elif ctx.h3:
-            dxb = _new_slot(g2.device)           # the epilogue takes max |dx|: the next backward GEMM's operand bound
-            _lib.check(L.ign_clconv_fwd_h3_amax(_ptr(g2), _ptr(ctx.wd3), None, None, None, _ptr(dx), None, _ptr(bg), _ptr(ctx.bw),
-                                                _ptr(dxb), 1, M, Co, Ci, 1, _stream()), "ign_clconv_fwd_h3_amax(dx)")
+        dxb = _new_slot(g2.device) if arith == GEMM_H3 else None     # the epilogue takes max |dx|: the next backward GEMM's bound
+        fused = gelu and arith == GEMM_H3 and Ci % 256 == 0 and Co % 4 == 0 and u2.is_contiguous()
+        if fused:                                # dL/du = (g W) * gelu'(u) in one GEMM
+            _lib.check(_lib.lib().ign_linear_dgrad_gelu_h3(_ptr(g2), _ptr(ctx.wd3), _ptr(u2), _ptr(dx), _ptr(bg), _ptr(ctx.bw),
+                                                           _ptr(dxb), M, Co, Ci, _stream()), "ign_linear_dgrad_gelu_h3")
         else:
-            _lib.check(_gemm(L, ctx.bf16)[0](_ptr(g2), _ptr(ctx.wd3), None, None, None, _ptr(dx), None, 1, M, Co, Ci, 1, _stream()),
-                       "ign_clconv_fwd_x6(dx)")
+            _clconv_fwd(arith, g2, ctx.wd3, None, None, None, dx, None, (1, M, Co, Ci, 1), _ptr(bg), _ptr(ctx.bw), dxb)
         if gelu and not fused:                   # shapes / arithmetics outside the fused kernel: torch's element-wise backward
             dx = torch.ops.aten.gelu_backward(dx, u2)     # (|gelu'| <= 1.13: dxb stays a usable bound, see keep_bound)
         dx = dx.view(ctx.xshape)
@@ -835,23 +910,13 @@ def _linear_backward(ctx, gy, gelu=False):
     want_db = ctx.has_bias and ctx.needs_input_grad[2]
     if ctx.needs_input_grad[1]:
         dw = torch.empty(Co, Ci, device=g2.device, dtype=torch.float32)
-        if Ci % 4 == 0 and LINEAR_WGRAD == "bf16x6":
+        if _linear_wgrad_split(Ci):
             # weight and bias gradient in one pass over dy (the bias gradient rides on the tiles that stage dy anyway)
-            ws = torch.empty(int(L.ign_clconv_wgrad_x6_workspace_bytes(1, M, Ci, Co, 1)) // 4, device=g2.device,
-                             dtype=torch.float32)
             if want_db:
                 db = torch.empty(Co, device=g2.device, dtype=torch.float32)
-            if ctx.h3:
-                _lib.check(L.ign_linear_wgrad_h3(_ptr(g2), _ptr(x2), _ptr(dw), _ptr(db), _ptr(ws), _ptr(bg), _ptr(ctx.bx), M, Ci, Co,
-                                                 _stream()), "ign_linear_wgrad_h3")
-            else:
-                fn = L.ign_linear_wgrad_bf16 if ctx.bf16 else L.ign_linear_wgrad_x6
-                _lib.check(fn(_ptr(g2), _ptr(x2), _ptr(dw), _ptr(db), _ptr(ws), M, Ci, Co, _stream()), "ign_linear_wgrad_x6")
+            _linear_wgrad(arith, g2, x2, dw, db, M, Ci, Co, _ptr(bg), _ptr(ctx.bx))
         else:
-            ws = torch.empty(int(L.ign_clconv_wgrad_workspace_bytes(1, M, Ci, Co, 1)) // 4, device=g2.device,
-                             dtype=torch.float32)
-            _lib.check(L.ign_clconv_wgrad(_ptr(g2), 0, _ptr(x2), None, None, _ptr(dw), _ptr(ws), 1, M, Ci, Co, 1, _stream()),
-                       "ign_clconv_wgrad")
+            _clconv_wgrad(GEMM_F32, g2, 0, x2, None, None, dw, (1, M, Ci, Co, 1))
     if want_db and db is None:
         db = g2.sum(dim=0)
     return dx, dw, db
@@ -964,7 +1029,7 @@ class LayerNormFn(torch.autograd.Function):
         dbeta = torch.empty(D, device=x2.device, dtype=torch.float32) if need_w and ctx.has_bias else None
         part = torch.empty(int(L.ign_layernorm_parts(R, D)) * 2 * D, device=x2.device, dtype=torch.float32)
         gxv = gx.view(gy.shape)
-        if GEMM_MATH == "f16x3" and not torch.is_autocast_enabled():
+        if _dense_arith(torch.is_autocast_enabled()) == GEMM_H3:
             # dL/dx usually feeds the backward GEMMs of a dense layer: its magnitude bound is taken here, as it is written
             slot = _new_slot(x2.device)
             _lib.check(L.ign_layernorm_bwd_amax(_ptr(x2), _ptr(g2), _ptr(weight), _ptr(mean), _ptr(rstd), _ptr(gx), _ptr(dgamma),
@@ -988,7 +1053,7 @@ def layer_norm(x, norm, residual=None):
             or (residual is not None and (residual.shape != x.shape or residual.dtype != x.dtype or not residual.is_cuda))):
         return norm(x if residual is None else x + residual)
     out = LayerNormFn.apply(x, residual, norm.weight, norm.bias, norm.eps)
-    if GEMM_MATH == "f16x3" and norm.bias is not None and not torch.is_autocast_enabled():
+    if norm.bias is not None and _dense_arith(torch.is_autocast_enabled()) == GEMM_H3:
         # a row standardised with its own mean and (biased) variance over D elements cannot exceed sqrt(D - 1): the output is
         # bounded by max_d(|gamma_d| sqrt(D - 1) + |beta_d|) -- from the parameters alone, one tiny launch instead of a pass over
         # the activations when a dense layer behind it asks for its operand's magnitude (tensor_bound)
@@ -1007,11 +1072,12 @@ class ConvCLFn(torch.autograd.Function):
     experts and embeddings (IGN/model/ResNet.py:11-22,46; IGN/layers/Embed.py:32-36): padding is materialised by the caller
     (zero rows, circular rows), a strided convolution is a stride-1 one over a space-to-depth view.  Forward and input
     gradient run on ign_clconv_fwd_x6 (the latter on dy zero-padded by k-1 rows with the tap-reversed transposed weights),
-    the weight gradient on ign_clconv_wgrad_x6 where its tap count is instantiated (k in 1,2,3,5,8), else ign_clconv_wgrad."""
+    the weight gradient on ign_clconv_wgrad_x6 where its tap count is instantiated (k in 2,3,5,8), on one ign_linear_wgrad_x6 per tap
+    for the other k > 1 with Ci % 4 == 0, else (k = 1 included) on the fp32-MFMA ign_clconv_wgrad: _conv_wgrad_route.  Each in the
+    arithmetic of _dense_arith."""
 
     @staticmethod
     def forward(ctx, x, w, bias):
-        L = _lib.lib()
         _need_gpu("conv1d_cl", x, w)
         B, Tin, Ci = x.shape
         Co, Ci2, k = w.shape
@@ -1019,79 +1085,49 @@ class ConvCLFn(torch.autograd.Function):
             raise _lib.IgnError(f"conv1d_cl: x {tuple(x.shape)} / w {tuple(w.shape)}: needs matching channels, Tin >= k, Co % 4 == 0")
         x = x.contiguous()
         w = w.contiguous()
-        dev = x.device
-        need_dx = ctx.needs_input_grad[0]
-        wt3 = torch.empty(int(L.ign_clconv_x3_elems(Co, Ci, k)), device=dev, dtype=torch.bfloat16)
-        wd3 = torch.empty(int(L.ign_clconv_x3_elems(Ci, Co, k)), device=dev, dtype=torch.bfloat16) if need_dx else None
-        y = torch.empty(B, Tin - k + 1, Co, device=dev, dtype=torch.float32)
-        ctx.bf16 = torch.is_autocast_enabled()
-        ctx.h3 = (not ctx.bf16) and GEMM_MATH == "f16x3"
+        y = torch.empty(B, Tin - k + 1, Co, device=x.device, dtype=torch.float32)
+        arith = ctx.arith = _dense_arith(torch.is_autocast_enabled())
         ctx.bx = ctx.bw = None
-        if ctx.h3:          # two fp16 planes, three products (see LinearFn)
+        if arith == GEMM_H3:
             ctx.bw, ctx.bx = tensor_bound(w), tensor_bound(x)
-            v1, i1 = _tables(1)
-            _lib.check(L.ign_clconv_pack_weights_h2_multi(1, v1(w.data_ptr()), v1(wt3.data_ptr()), v1(wd3.data_ptr()) if need_dx else None,
-                                                          i1(Co), i1(Ci), i1(k), None, v1(ctx.bw.data_ptr()), _stream()),
-                       "ign_clconv_pack_weights_h2_multi")
-            _lib.check(L.ign_clconv_fwd_h3(_ptr(x), _ptr(wt3), _ptr(bias), None, None, _ptr(y), None, _ptr(ctx.bx), _ptr(ctx.bw), B, Tin, Ci,
-                                           Co, k, _stream()), "ign_clconv_fwd_h3")
-        else:
-            _lib.check(L.ign_clconv_pack_weights_x3(_ptr(w), _ptr(wt3), _ptr(wd3), Co, Ci, k, _stream()), "ign_clconv_pack_weights_x3")
-            _lib.check(_gemm(L, ctx.bf16)[0](_ptr(x), _ptr(wt3), _ptr(bias), None, None, _ptr(y), None, B, Tin, Ci, Co, k, _stream()),
-                       "ign_clconv_fwd_x6")
+        wt3, wd3 = _pack_weights(arith, w, ctx.needs_input_grad[0], ctx.bw)
+        _clconv_fwd(arith, x, wt3, bias, None, None, y, None, (B, Tin, Ci, Co, k), _ptr(ctx.bx), _ptr(ctx.bw))
         ctx.save_for_backward(x)
         ctx.wd3, ctx.dims, ctx.has_bias = wd3, (B, Tin, Ci, Co, k), bias is not None
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        L = _lib.lib()
         (x,) = ctx.saved_tensors
         B, Tin, Ci, Co, k = ctx.dims
         Tout = Tin - k + 1
         dx = dw = db = None
         # dy zero-padded by k-1 rows per side: the operand of the input gradient, and the layout the weight gradient reads
         gyp = torch.nn.functional.pad(gy, (0, 0, k - 1, k - 1)) if k > 1 else gy.contiguous()
-        bg = tensor_bound(gyp) if ctx.h3 else None            # (the zero rows do not change the maximum)
+        arith = ctx.arith
+        bg = tensor_bound(gyp) if arith == GEMM_H3 else None  # (the zero rows do not change the maximum)
         if ctx.needs_input_grad[0]:
             dx = torch.empty(B, Tin, Ci, device=gy.device, dtype=torch.float32)
-            if ctx.h3:
-                _lib.check(L.ign_clconv_fwd_h3(_ptr(gyp), _ptr(ctx.wd3), None, None, None, _ptr(dx), None, _ptr(bg), _ptr(ctx.bw), B,
-                                               Tout + 2 * (k - 1), Co, Ci, k, _stream()), "ign_clconv_fwd_h3(dx)")
-            else:
-                _lib.check(_gemm(L, ctx.bf16)[0](_ptr(gyp), _ptr(ctx.wd3), None, None, None, _ptr(dx), None, B, Tout + 2 * (k - 1), Co,
-                                                 Ci, k, _stream()), "ign_clconv_fwd_x6(dx)")
+            _clconv_fwd(arith, gyp, ctx.wd3, None, None, None, dx, None, (B, Tout + 2 * (k - 1), Co, Ci, k), _ptr(bg), _ptr(ctx.bw))
         if ctx.needs_input_grad[1]:
-            x6 = k in (2, 3, 5, 8) and LINEAR_WGRAD == "bf16x6"
-            if not x6 and k > 1 and Ci % 4 == 0 and LINEAR_WGRAD == "bf16x6":
+            route = _conv_wgrad_route(k, Ci)
+            if route == "taps":
                 # tap counts without an instantiated multi-tap kernel (k = 4, 7, 11, ...): one k = 1 GEMM per tap on FLAT row
                 # views.  With dy zero-padded by k-1 rows at the END of every sample, dW[:, :, j] = dy_flat[0 : M-j]^T x_flat[j : M]
                 # -- the pairs that straddle two samples multiply zero rows -- so each tap is the Linear-layer weight gradient
-                # on the split-bf16 kernel with the operand pointer advanced by j rows (no copies of x).
+                # on the split kernel with the operand advanced by j rows (no copies of x).
                 M = B * Tin
                 dye = torch.nn.functional.pad(gy, (0, 0, 0, k - 1)).contiguous()
                 dwt = torch.empty(k, Co, Ci, device=gy.device, dtype=torch.float32)
-                ws = torch.empty(int(L.ign_clconv_wgrad_x6_workspace_bytes(1, M, Ci, Co, 1)) // 4, device=gy.device,
-                                 dtype=torch.float32)
-                fn = L.ign_linear_wgrad_bf16 if ctx.bf16 else L.ign_linear_wgrad_x6
+                ws = _wgrad_workspace(arith, (1, M, Ci, Co, 1), gy.device)
+                xf = x.view(M, Ci)
                 for j in range(k):
-                    xj = ctypes.c_void_p(x.data_ptr() + 4 * j * Ci)
-                    if ctx.h3:
-                        _lib.check(L.ign_linear_wgrad_h3(_ptr(dye), xj, _ptr(dwt[j]), None, _ptr(ws), _ptr(bg), _ptr(ctx.bx), M - j, Ci, Co,
-                                                         _stream()), "ign_linear_wgrad_h3(tap)")
-                    else:
-                        _lib.check(fn(_ptr(dye), xj, _ptr(dwt[j]), None, _ptr(ws), M - j, Ci, Co, _stream()), "ign_linear_wgrad_x6(tap)")
+                    _linear_wgrad(arith, dye, xf[j:], dwt[j], None, M - j, Ci, Co, _ptr(bg), _ptr(ctx.bx), ws)
                 dw = dwt.permute(1, 2, 0).contiguous()
             else:
                 dw = torch.empty(Co, Ci, k, device=gy.device, dtype=torch.float32)
-                wsb, fn, name = ((L.ign_clconv_wgrad_x6_workspace_bytes, _gemm(L, ctx.bf16)[1], "ign_clconv_wgrad_x6") if x6 else
-                                 (L.ign_clconv_wgrad_workspace_bytes, L.ign_clconv_wgrad, "ign_clconv_wgrad"))
-                ws = torch.empty(max(1, int(wsb(B, Tin, Ci, Co, k)) // 4), device=gy.device, dtype=torch.float32)
-                if ctx.h3 and x6:
-                    _lib.check(L.ign_clconv_wgrad_h3(_ptr(gyp), k - 1, _ptr(x), None, None, _ptr(dw), _ptr(ws), _ptr(bg), _ptr(ctx.bx), B,
-                                                     Tin, Ci, Co, k, _stream()), "ign_clconv_wgrad_h3")
-                else:
-                    _lib.check(fn(_ptr(gyp), k - 1, _ptr(x), None, None, _ptr(dw), _ptr(ws), B, Tin, Ci, Co, k, _stream()), name)
+                _clconv_wgrad(arith if route == "split" else GEMM_F32, gyp, k - 1, x, None, None, dw, (B, Tin, Ci, Co, k), _ptr(bg),
+                              _ptr(ctx.bx))
         if ctx.has_bias and ctx.needs_input_grad[2]:
             db = gy.sum(dim=(0, 1))
         return dx, dw, db
@@ -1177,7 +1213,7 @@ class IgnLossFn(torch.autograd.Function):
             if reg.numel() != 1:
                 raise _lib.IgnError(f"ign_loss: the regulariser must be one value, got {tuple(reg.shape)}")
         _lib.check(_lib.lib().ign_loss_fwd_bwd_reg(_ptr(sbm), _ptr(dnn), _ptr(y), _ptr(reg), _ptr(out), _ptr(eta), _ptr(loss2),
-                                                   _ptr(gsd[0]), _ptr(gsd[1]), B, N, float(beta), _stream()), "ign_loss_fwd_bwd")
+                                                   _ptr(gsd[0]), _ptr(gsd[1]), B, N, float(beta), _stream()), "ign_loss_fwd_bwd_reg")
         ctx.save_for_backward(gsd)
         ctx.reg_shape = None if reg is None else tuple(reg.shape)
         ctx.mark_non_differentiable(out, eta)
@@ -1189,9 +1225,7 @@ class IgnLossFn(torch.autograd.Function):
         if gl is None:
             return None, None, None, None, None
         (gsd,) = ctx.saved_tensors
-        unit = _UNIT.get(gl.device)
-        # the root gradient of ops.backward(): exactly 1 -- no scaling launch; otherwise one launch for both logit gradients
-        g = gsd if (unit is not None and gl.data_ptr() == unit.data_ptr()) else gl * gsd
+        g = _unit_or_scaled(gl, gsd)     # the root gradient of ops.backward(): exactly 1 -- no scaling launch; else one for both
         return g[0], g[1], None, None, (gl.reshape(ctx.reg_shape) if ctx.reg_shape is not None else None)
 
 

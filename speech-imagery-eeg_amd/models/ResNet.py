@@ -8,7 +8,7 @@ stride-2 stem is a stride-1 k=4 convolution over the (B, T/2, 2C) space-to-depth
 interleaved to match; no gather), the 1x1 shortcut is ``ops.linear``.  BatchNorm runs on the (B*T, C) view (same statistics as
 BatchNorm1d over (B, C, T)); BatchNorm / ReLU / max-pool / residual add are torch element-wise ops on tensors of <= 33 MB.
 Inside a torch.autocast(bfloat16) region (the reference's default mode) the same kernels run in their single-product bf16 form
-(``ops._gemm``); BatchNorm and the activations stay fp32.  CPU tensors are refused (no CPU fallback).
+(``ops._dense_arith``); BatchNorm and the activations stay fp32.  CPU tensors are refused (no CPU fallback).
 """
 import torch
 import torch.nn as nn
