@@ -97,7 +97,8 @@ int ign_shapelet_fwd_bank(const float* xn_bct, int G, const float* const* w_kcl,
  * SURVEY.md App. A).  g_out is dloss/dp_out with the same (ld, col0) indexing as p_out.
  *   gw_kcl (K,C,L) receives dloss/dw (overwritten, deterministic: fixed-order two-stage reduction over B)
  *   workspace: ign_shapelet_bwd_workspace_bytes() bytes.
- * Gradients w.r.t. the input are not produced (inputs are data: IGN/exp/experiment_classification.py:315).
+ * Gradients w.r.t. the input are not produced here (the training loop's inputs are data: IGN/exp/experiment_classification.py:315);
+ * ign_shapelet_bwd_input below is the separate pass for them.
  * LTS: dloss/dthr is a (B,KC) elementwise reduction the caller forms from g_out and p_out.
  * sign(0) convention (IGN_DIST_L1 only).  The reference differentiates |x - w| with aten::sgn, sign(0) = 0
  * (IGN/model/Shapelet.py:74).  The kernel accumulates P_j = sum_{t: x > w} A_t and returns 2 P_j - sum_t A_t, which counts an
@@ -132,6 +133,40 @@ int ign_shapelet_bwd_bank(const float* xn_bct, int G, const float* const* w_kcl,
                           const float* const* d_save, const float* const* xstat_save, const float* const* wnorm_kc,
                           float* const* gw_kcl, const float* const* gw_add, const float* add_scale_dev, void* workspace,
                           int B, int C, int T, const int* K, const int* L, const int* stride, float eps, int mode, void* stream);
+
+/* Backward of ign_shapelet_fwd w.r.t. the INPUT (saliency, a learnable front-end, input-space regularisers): with dloss/dd the
+ * coefficient ign_shapelet_bwd forms from g_out and the saved d_save / zmu / tstar / p_out / dmin_out,
+ *     gxn_bct[b,c,s] (+)= sum_k sum_{(t,j): t*stride + j = s} dloss/dd[b,t,k,c] * dd/dx,
+ *     IGN_DIST_L1: dd/dx = sign(x[b,c,s] - w[k,c,j]) / L        IGN_DIST_MSE: dd/dx = 2 (x[b,c,s] - w[k,c,j]) / L.
+ * gxn_bct (B,C,T) is overwritten when accumulate == 0 and added to otherwise; samples no window covers receive 0.  Every
+ * output sample is summed by one lane in a fixed order (k, then j ascending) and written once: no float atomics, no
+ * workspace, bitwise reproducible.  Arguments and saved tensors as ign_shapelet_bwd; any stride >= 1, any L <= T (long
+ * shapelets are walked in chunks); rows beyond the forward's LDS staging limit return the forward's IGN_E_TOOBIG.
+ * IGN_DIST_COS / IGN_DIST_PEARS: IGN_E_ARG (input gradients exist for L1 and MSE only).  Nothing is launched on an error.
+ * sign(0) convention (IGN_DIST_L1 only): as for gw_kcl above, an element with x[b,c,s] == w[k,c,j] (bit-equal floats) counts
+ * as sign(x - w) = -1, where the reference's aten::sgn gives 0.  Hence, exactly,
+ *     gxn_bct[b,c,s] = reference[b,c,s] - sum_{(k,t,j): t*stride + j = s, x[b,c,s] == w[k,c,j]} dloss/dd[b,t,k,c] / L,
+ * so the tie terms of gw_kcl and gxn_bct stay negatives of each other, as every other term is.  MSE has no kink.             */
+int ign_shapelet_bwd_input(const float* xn_bct, const float* w_kcl, const float* g_out, const float* p_out,
+                           const float* dmin_out, int ld, int col0, const int32_t* tstar, const float* zmu,
+                           const float* d_save, float* gxn_bct, int accumulate,
+                           int B, int C, int T, int K, int L, int stride, float eps, int mode, void* stream);
+/* Every group of a bank (tables of G <= 8 host entries, as ign_shapelet_bwd_bank): G launches one after another on `stream`,
+ * the first overwriting gxn_bct and the others adding to it, so the result is bitwise that of G ign_shapelet_bwd_input calls
+ * with accumulate = 0, 1, 1, ...  Every group is validated before the first launch.                                         */
+int ign_shapelet_bwd_input_bank(const float* xn_bct, int G, const float* const* w_kcl, const float* g_out, const float* p_out,
+                                const float* dmin_out, int ld, const int* col0, const int32_t* const* tstar,
+                                const float* const* zmu, const float* const* d_save, float* gxn_bct,
+                                int B, int C, int T, const int* K, const int* L, const int* stride, float eps, int mode,
+                                void* stream);
+
+/* Backward of ign_instnorm_fwd: gxn_bct (B,C,T) = dloss/dxn -> gx_btc (B,T,C) = dloss/dx in the loader's layout.  With
+ * y = (x - mu) / (sigma + eps), sigma the unbiased std over T:
+ *     gx_j = [ g_j - mean_T(g) - y_j * (sum_i g_i y_i) / (T - 1) * (sigma + eps) / sigma ] / (sigma + eps).
+ * mu and sigma are recomputed from x_btc with the forward's two-pass scheme (the forward saves no statistics).  A constant
+ * row (sigma == 0), where the reference's autograd yields NaN, receives gx = 0 for every sample of that row.  T >= 2; the
+ * LDS tile limit of ign_instnorm_fwd applies (IGN_E_TOOBIG beyond it).                                                      */
+int ign_instnorm_bwd(const float* x_btc, const float* gxn_bct, float* gx_btc, int B, int T, int C, float eps, void* stream);
 
 /* Fused attention core softmax(scale * Q K^T) V, exact fp32 on the matrix cores (v_mfma_f32_32x32x2_f32), scores never
  * materialised.  Replaces IGN/layers/SelfAttention_Family.py:56-75 (FullAttention: no mask; dropout 0 here -- dropout p > 0

@@ -116,6 +116,24 @@ static int check_dims(const char* who, int B, int C, int T, int K, int L, int st
 }
 
 // ------------------------------------------------------------------------------------------ forward
+// LDS staging of one forward wave -- the row limit of the shapelet path: the input-gradient pass returns the same IGN_E_TOOBIG.
+static int fwd_staging(const char* who, int T, int L, int stride, int* TT_out, int* npass_out, int* xs_len_out, size_t* lds_out) {
+    const int Tw = (T - L) / stride + 1;
+    // TT windows per lane: one wave pass covers the row when Tw <= 1024; strided windows use TT = 1.
+    const int TT = (stride == 1) ? std::min(16, (Tw + 63) / 64) : 1;
+    const int npass = (Tw + 64 * TT - 1) / (64 * TT);
+    int xs_len = (npass * 64 * TT - 1) * stride + (TT - 1) + L;
+    xs_len = (xs_len + 3) & ~3;
+    const size_t park = (npass > 1) ? (size_t)5 * 5 * 64 * 4 : 0;     // per wave: 5 stats x KT<=5 x 64 lanes
+    const size_t lds = (size_t)xs_len * 4 + park;
+    if (lds > 160 * 1024) {       // the whole LDS of a gfx950 CU: rows up to T ~ 40 000 (the longest UEA set is 17 984)
+        ign_set_error("%s: a row needs %zu bytes of LDS staging (T=%d L=%d stride=%d)", who, lds, T, L, stride);
+        return IGN_E_TOOBIG;
+    }
+    *TT_out = TT; *npass_out = npass; *xs_len_out = xs_len; *lds_out = lds;
+    return 0;
+}
+
 struct FwdPlan {
     ShpFwdArgs a;
     int TT, wpb, dist;
@@ -137,18 +155,10 @@ static int plan_fwd(const char* who, const float* xn_bct, const float* w_kcl, co
         return IGN_E_ARG;
     }
     const int Tw = (T - L) / stride + 1;
-    // TT windows per lane: one wave pass covers the row when Tw <= 1024; strided windows use TT = 1.
-    int TT = (stride == 1) ? std::min(16, (Tw + 63) / 64) : 1;
-    const int npass = (Tw + 64 * TT - 1) / (64 * TT);
-    int xs_len = (npass * 64 * TT - 1) * stride + (TT - 1) + L;
-    xs_len = (xs_len + 3) & ~3;
-    int wpb = 1;      // one wave per block: waves share nothing, and the epilogue's __syncthreads() stays wave-local
-    const size_t park = (npass > 1) ? (size_t)5 * 5 * 64 * 4 : 0;     // per wave: 5 stats x KT<=5 x 64 lanes
-    const size_t lds = (size_t)wpb * (xs_len * 4 + park);
-    if (lds > 160 * 1024) {       // the whole LDS of a gfx950 CU: rows up to T ~ 40 000 (the longest UEA set is 17 984)
-        ign_set_error("%s: a row needs %zu bytes of LDS staging (T=%d L=%d stride=%d)", who, lds, T, L, stride);
-        return IGN_E_TOOBIG;
-    }
+    int TT, npass, xs_len, rc2;
+    const int wpb = 1;      // one wave per block: waves share nothing, and the epilogue's __syncthreads() stays wave-local
+    size_t lds;
+    if ((rc2 = fwd_staging(who, T, L, stride, &TT, &npass, &xs_len, &lds))) return rc2;
     ShpFwdArgs& a = pl->a;
     a.xn = xn_bct; a.w = w_kcl; a.thr = thr_kc; a.p_out = p_out; a.dmin_out = dmin_out; a.tstar = tstar; a.zmu = zmu;
     a.d = d_save;
@@ -466,4 +476,81 @@ extern "C" int ign_shapelet_bwd_bank(const float* xn_bct, int G, const float* co
     IgnScopedTimer tm2("reduce_parts", (hipStream_t)stream);
     ign_launch_reduce_bank(t, G, add_scale_dev, (hipStream_t)stream);
     return ign_check_launch("reduce_bank_kernel");
+}
+
+// ------------------------------------------------------------------------------------------ backward w.r.t. the input
+// validate one group and fill its launch arguments; nothing is launched here
+static int plan_bwdx(const char* who, const float* xn_bct, const float* w_kcl, const float* g_out, const float* p_out,
+                     const float* dmin_out, int ld, int col0, const int32_t* tstar, const float* zmu, const float* d_save,
+                     float* gxn_bct, int accumulate, int B, int C, int T, int K, int L, int stride, float eps, int mode,
+                     ShpBwdXArgs* a, int* dist_out, size_t* lds_out) {
+    int dist, gate, rc;
+    if ((rc = split_mode(mode, &dist, &gate, who))) return rc;
+    if (dist != DIST_L1 && dist != DIST_MSE) {
+        ign_set_error("%s: input gradients exist for IGN_DIST_L1 and IGN_DIST_MSE only (mode 0x%x is cosine / pearson)", who, mode);
+        return IGN_E_ARG;
+    }
+    if ((rc = check_dims(who, B, C, T, K, L, stride))) return rc;
+    if (!xn_bct || !w_kcl || !g_out || !tstar || !zmu || !d_save || !gxn_bct || (gate == GATE_LTS && (!p_out || !dmin_out))) {
+        ign_set_error("%s: null pointer argument (d_save is required: run the forward with d_save)", who);
+        return IGN_E_ARG;
+    }
+    if (ld < col0 + K * C || col0 < 0) {
+        ign_set_error("%s: row pitch ld=%d too small for col0=%d + K*C=%d", who, ld, col0, K * C);
+        return IGN_E_ARG;
+    }
+    int TT, npass, xs_len;
+    size_t fwd_lds;
+    if ((rc = fwd_staging(who, T, L, stride, &TT, &npass, &xs_len, &fwd_lds))) return rc;      // the forward's row limit
+    a->xn = xn_bct; a->w = w_kcl; a->g = g_out; a->p = p_out; a->dmin = dmin_out; a->tstar = tstar; a->zmu = zmu; a->d = d_save;
+    a->gx = gxn_bct;
+    a->B = B; a->C = C; a->T = T; a->K = K; a->L = L; a->Tw = (T - L) / stride + 1; a->ld = ld; a->col0 = col0; a->stride = stride;
+    a->gate = gate; a->accumulate = accumulate ? 1 : 0; a->eps = eps; a->invL = 1.0f / (float)L;
+    // No limit of its own: the forward stages at least 63*stride + L floats in 160 KB, so an accepted row has stride <= 650, and
+    // ign_bwdx_plan then needs at most 2 * (512 + 1024 + 512 + 12) floats = 16.5 KB (stride 1; less for every larger stride).
+    // The comparison below cannot fire after fwd_staging passed; it guards the launch against a future change of either plan.
+    const size_t lds = ign_bwdx_plan(a);
+    if (lds > 64 * 1024) {
+        ign_set_error("%s: internal: launch plan needs %zu bytes of LDS (stride=%d)", who, lds, stride);
+        return IGN_E_TOOBIG;
+    }
+    if ((size_t)B * C * a->ntile > 0x7fffffffull) {
+        ign_set_error("%s: B*C*tiles = %zu blocks exceed the grid limit", who, (size_t)B * C * a->ntile);
+        return IGN_E_ARG;
+    }
+    *dist_out = dist; *lds_out = lds;
+    return 0;
+}
+
+extern "C" int ign_shapelet_bwd_input(const float* xn_bct, const float* w_kcl, const float* g_out, const float* p_out,
+                                      const float* dmin_out, int ld, int col0, const int32_t* tstar, const float* zmu,
+                                      const float* d_save, float* gxn_bct, int accumulate, int B, int C, int T, int K, int L,
+                                      int stride, float eps, int mode, void* stream) {
+    ShpBwdXArgs a;
+    int rc, dist;
+    size_t lds;
+    if ((rc = plan_bwdx("ign_shapelet_bwd_input", xn_bct, w_kcl, g_out, p_out, dmin_out, ld, col0, tstar, zmu, d_save, gxn_bct,
+                        accumulate, B, C, T, K, L, stride, eps, mode, &a, &dist, &lds))) return rc;
+    return ign_launch_bwdx(a, dist, lds, (hipStream_t)stream);
+}
+
+extern "C" int ign_shapelet_bwd_input_bank(const float* xn_bct, int G, const float* const* w_kcl, const float* g_out,
+                                           const float* p_out, const float* dmin_out, int ld, const int* col0,
+                                           const int32_t* const* tstar, const float* const* zmu, const float* const* d_save,
+                                           float* gxn_bct, int B, int C, int T, const int* K, const int* L, const int* stride,
+                                           float eps, int mode, void* stream) {
+    static const char* who = "ign_shapelet_bwd_input_bank";
+    if (G <= 0 || G > SHP_MAX_GROUPS || !w_kcl || !col0 || !tstar || !zmu || !d_save || !K || !L || !stride) {
+        ign_set_error("%s: G=%d outside 1..%d or null table", who, G, SHP_MAX_GROUPS);
+        return IGN_E_ARG;
+    }
+    ShpBwdXArgs a[SHP_MAX_GROUPS];
+    int dist[SHP_MAX_GROUPS], rc;
+    size_t lds[SHP_MAX_GROUPS];
+    for (int g = 0; g < G; ++g)          // validate every group before the first launch
+        if ((rc = plan_bwdx(who, xn_bct, w_kcl[g], g_out, p_out, dmin_out, ld, col0[g], tstar[g], zmu[g], d_save[g], gxn_bct,
+                            g > 0, B, C, T, K[g], L[g], stride[g], eps, mode, &a[g], &dist[g], &lds[g]))) return rc;
+    for (int g = 0; g < G; ++g)          // in the order given: the first group overwrites gxn, the others add to it
+        if ((rc = ign_launch_bwdx(a[g], dist[g], lds[g], (hipStream_t)stream))) return rc;
+    return 0;
 }

@@ -92,6 +92,30 @@ typedef void (*shp_bwd_launch_t)(const ShpBwdArgs&, dim3 grid, dim3 block, size_
 shp_bwd_launch_t ign_get_bwd_launcher(int dist, int JJ);            // JJ in {4,8}
 shp_bwd_launch_t ign_get_bwd_strided_launcher(int dist);            // stride > 1: JJ = 4, generic window step
 
+// ---------------------------------------------------------------- backward w.r.t. the input (ign_shapelet_bwd_x.hip)
+struct ShpBwdXArgs {
+    const float* xn;      // (B,C,T)
+    const float* w;       // (K,C,L)
+    const float* g;       // (B,ld)+col0 upstream grad of p_out
+    const float* p;       // (B,ld)+col0 forward gate output (LTS)
+    const float* dmin;    // (B,ld)+col0 (LTS)
+    const int32_t* tstar; // (B,K,C)
+    const float* zmu;     // (B,K,C,2)
+    const float* d;       // (B,C,K,Tw)
+    float* gx;            // (B,C,T)
+    int B, C, T, K, L, Tw, ld, col0, stride;
+    int ntile;            // tiles of SHP_BWDX_TILE samples per row
+    int kb;               // shapelets staged together
+    int mc;               // window offsets m (shapelet position j = s % stride + m * stride) per LDS chunk
+    int M;                // ceil(L / stride): offsets a sample can have
+    int na;               // floats of A staged per shapelet and chunk
+    int gate, accumulate;
+    float eps, invL;
+};
+constexpr int SHP_BWDX_THREADS = 256, SHP_BWDX_SPL = 4, SHP_BWDX_TILE = SHP_BWDX_THREADS * SHP_BWDX_SPL;
+size_t ign_bwdx_plan(ShpBwdXArgs* a);                                  // fills ntile / kb / mc / M / na; -> bytes of LDS
+int ign_launch_bwdx(const ShpBwdXArgs& a, int dist, size_t lds, hipStream_t s);
+
 void ign_launch_reduce_parts(const float* part, float* out, int nparts, size_t n, hipStream_t s);
 
 // the reductions of every group of a bank in one launch (ign_shapelet_bwd.hip)

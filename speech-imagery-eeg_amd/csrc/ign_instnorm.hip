@@ -210,3 +210,104 @@ extern "C" int ign_transpose_btc_to_bct(const float* x_btc, float* out_bct, int 
                        T, C);
     return ign_check_launch("transpose_btc_bct_kernel");
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Backward of the instance normalisation, fused with the transpose back: gxn (B,C,T) -> gx (B,T,C).
+//   y = (x - mu) / (sigma + eps):   gx_j = [ g_j - mean(g) - y_j * (sum_i g_i y_i) / (T - 1) * (sigma + eps) / sigma ] / (sigma + eps)
+// Same tiling as the forward: the T x CT tile of x is staged in LDS, a wave recomputes mean and unbiased variance of a channel with
+// the forward's two passes (nothing is saved by the forward), reads its gradient row as coalesced (c, t) lines, and leaves gx in the
+// tile; the block then writes the tile out in the loader's (t, c) order.  A constant row (sigma == 0) receives zeros.
+__global__ void __launch_bounds__(1024) instnorm_bwd_kernel(const float* __restrict__ x, const float* __restrict__ g,
+                                                           float* __restrict__ gx, int B, int T, int C, int CT, float eps) {
+    extern __shared__ __attribute__((aligned(16))) float tile[];
+    const int pitch = CT + 1;
+    const int nct = (C + CT - 1) / CT;
+    const int b = blockIdx.x / nct;
+    const int c0 = (blockIdx.x - b * nct) * CT;
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    const float* xb = x + (size_t)b * T * C;
+    for (int i0 = tid; i0 < T * CT; i0 += 8 * nthr) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int idx = i0 + u * nthr;
+            const int t = idx / CT, cc = idx - t * CT;
+            v[u] = (idx < T * CT && c0 + cc < C) ? xb[(size_t)t * C + c0 + cc] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int idx = i0 + u * nthr;
+            const int t = idx / CT, cc = idx - t * CT;
+            if (idx < T * CT) tile[t * pitch + cc] = v[u];
+        }
+    }
+    __syncthreads();
+    const int wave = tid >> 6, lane = tid & 63;
+    for (int cc = wave; cc < CT; cc += (nthr >> 6)) {
+        const int c = c0 + cc;
+        if (c >= C) break;
+        float s = 0.f;
+        for (int t = lane; t < T; t += 64) s += tile[t * pitch + cc];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        const float mean = s / (float)T;
+        float v = 0.f;
+        for (int t = lane; t < T; t += 64) {
+            const float dv = tile[t * pitch + cc] - mean;
+            v = fmaf(dv, dv, v);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        const float sigma = sqrtf(v / (float)(T - 1));
+        const float denom = sigma + eps;
+        const float* gr = g + ((size_t)b * C + c) * T;
+        float sg = 0.f, sgy = 0.f;
+        for (int t = lane; t < T; t += 64) {
+            const float gv = gr[t];
+            sg += gv;
+            sgy = fmaf(gv, (tile[t * pitch + cc] - mean) / denom, sgy);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            sg += __shfl_xor(sg, o, 64);
+            sgy += __shfl_xor(sgy, o, 64);
+        }
+        const bool flat = !(sigma > 0.f);                           // constant row: no derivative, zeros by convention
+        const float mg = sg / (float)T;
+        const float coef = flat ? 0.f : sgy / (float)(T - 1) * (denom / sigma);
+        for (int t = lane; t < T; t += 64) {
+            const float y = (tile[t * pitch + cc] - mean) / denom;
+            tile[t * pitch + cc] = flat ? 0.f : (gr[t] - mg - y * coef) / denom;
+        }
+    }
+    __syncthreads();
+    float* ob = gx + (size_t)b * T * C;
+    for (int idx = tid; idx < T * CT; idx += nthr) {
+        const int t = idx / CT, cc = idx - t * CT;
+        if (c0 + cc < C) ob[(size_t)t * C + c0 + cc] = tile[t * pitch + cc];
+    }
+}
+
+extern "C" int ign_instnorm_bwd(const float* x_btc, const float* gxn_bct, float* gx_btc, int B, int T, int C, float eps,
+                                void* stream) {
+    static const char* who = "ign_instnorm_bwd";
+    if (!x_btc || !gxn_bct || !gx_btc || B <= 0 || T < 2 || C <= 0) {
+        ign_set_error("%s: null pointer or bad dimension (B=%d T=%d C=%d; the unbiased std needs T >= 2)", who, B, T, C);
+        return IGN_E_ARG;
+    }
+    int CT = 32;                                                    // the forward's tile rule
+    while (CT > 1 && (size_t)T * (CT + 1) * 4 > 150 * 1024) CT >>= 1;
+    const size_t lds = (size_t)T * (CT + 1) * 4;
+    const int threads = lds > 64 * 1024 ? 1024 : 256;
+    if (lds > 160 * 1024) {
+        ign_set_error("%s: T=%d does not fit the LDS tile", who, T);
+        return IGN_E_TOOBIG;
+    }
+    const int nct = (C + CT - 1) / CT;
+    if (lds > 64 * 1024)
+        (void)hipFuncSetAttribute((const void*)instnorm_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    IgnScopedTimer tm("instnorm_bwd", (hipStream_t)stream);
+    hipLaunchKernelGGL(instnorm_bwd_kernel, dim3((unsigned)B * nct), dim3(threads), lds, (hipStream_t)stream, x_btc, gxn_bct, gx_btc,
+                       B, T, C, CT, eps);
+    return ign_check_launch("instnorm_bwd_kernel");
+}

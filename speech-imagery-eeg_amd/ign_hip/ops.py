@@ -47,7 +47,17 @@ def _need_gpu(name, *ts):
 
 def instance_norm(x_btc, want_raw=False, eps=1e-8, input_bound=False):
     """(B,T,C) -> normalised (B,C,T) [+ raw transpose].  Replaces IGN/model/Shapelet.py:186-187.
-    `input_bound`: also attach max |x| to `x_btc` (see cached_bound) for a consumer of the raw batch."""
+    `input_bound`: also attach max |x| to `x_btc` (see cached_bound) for a consumer of the raw batch.
+    An autograd node (InstanceNormFn) when, and only when, `x_btc` requires a gradient and grad mode is on; the training step,
+    whose inputs are data, runs the plain pass below."""
+    if x_btc.requires_grad and torch.is_grad_enabled():
+        _need_gpu("instance_norm", x_btc)
+        xn, xt = InstanceNormFn.apply(x_btc, want_raw, eps, input_bound)
+        return xn, xt
+    return _instance_norm(x_btc, want_raw, eps, input_bound)
+
+
+def _instance_norm(x_btc, want_raw, eps, input_bound):
     _need_gpu("instance_norm", x_btc)
     x = x_btc.contiguous()
     B, T, C = x.shape
@@ -63,6 +73,36 @@ def instance_norm(x_btc, want_raw=False, eps=1e-8, input_bound=False):
     else:
         _lib.check(L.ign_instnorm_fwd(_ptr(x), _ptr(xn), _ptr(xt), B, T, C, eps, _stream()), "ign_instnorm_fwd")
     return xn, xt
+
+
+class InstanceNormFn(torch.autograd.Function):
+    """instance_norm for an input that requires a gradient: the same forward launch; the backward recomputes mean and std from
+    x (ign_instnorm_bwd -- the forward saves no statistics) and returns the gradient in the loader's (B,T,C) layout.  A gradient
+    of the raw transpose `xt` is transposed back and added."""
+
+    @staticmethod
+    def forward(ctx, x_btc, want_raw, eps, input_bound):
+        xn, xt = _instance_norm(x_btc, want_raw, eps, input_bound)
+        ctx.eps = float(eps)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x_btc)
+        return xn, xt
+
+    @staticmethod
+    def backward(ctx, gxn, gxt):
+        x_btc, = ctx.saved_tensors
+        gx = None
+        if gxn is not None:
+            _need_gpu("instance_norm backward", gxn)
+            x = x_btc.contiguous()
+            B, T, C = x.shape
+            gxn = gxn.contiguous()
+            gx = torch.empty_like(x)
+            _lib.check(_lib.lib().ign_instnorm_bwd(_ptr(x), _ptr(gxn), _ptr(gx), B, T, C, ctx.eps, _stream()), "ign_instnorm_bwd")
+        if gxt is not None:
+            gt = gxt.permute(0, 2, 1)
+            gx = gt.contiguous() if gx is None else gx + gt
+        return gx, None, None, None
 
 
 def contiguous_bct(x):
@@ -184,6 +224,37 @@ def _bank_backward(xn, ws, gP, P, D, saved, eps, mode, gw_add=None, add_scale=No
     return gws
 
 
+def _input_grad_supported(name, mode):
+    """Raise at FORWARD time when the input needs a gradient the kernels do not produce (cosine / pearson)."""
+    if (mode & 0xf) >= DIST_COS:
+        raise _lib.IgnError(f"{name}: the input requires a gradient, but input gradients through the shapelet bank exist for the "
+                            f"L1 ('euclidean') and MSE (memory_efficient) distances only, not for cosine / pearson (mode 0x{mode:x})")
+
+
+def _bank_backward_input(xn, ws, gP, P, D, saved, eps, mode):
+    """dloss/dxn (B,C,T) of every group from gP = dloss/dP (B, ld): the groups run one after another on the stream, the first
+    overwriting the result and the others adding to it (no atomics: bitwise repeatable)."""
+    B, C, T = xn.shape
+    ld = P.shape[1]
+    L = _lib.lib()
+    G = len(ws)
+    gxn = torch.empty_like(xn)
+    if G <= 8:
+        _, ia = _tables(G)
+        _lib.check(L.ign_shapelet_bwd_input_bank(
+            _ptr(xn), G, _pv(ws), _ptr(gP), _ptr(P), _ptr(D), ld, ia(*[sv[3] for sv in saved]), _pv([sv[0] for sv in saved]),
+            _pv([sv[1] for sv in saved]), _pv([sv[2] for sv in saved]), _ptr(gxn), B, C, T, ia(*[w.shape[0] for w in ws]),
+            ia(*[w.shape[2] for w in ws]), ia(*[sv[4] for sv in saved]), float(eps), int(mode), _stream()),
+            "ign_shapelet_bwd_input_bank")
+        return gxn
+    for g, w in enumerate(ws):
+        tstar, zmu, dsave, col0, stride, _ = saved[g]
+        _lib.check(L.ign_shapelet_bwd_input(_ptr(xn), _ptr(w), _ptr(gP), _ptr(P), _ptr(D), ld, col0, _ptr(tstar), _ptr(zmu),
+                                            _ptr(dsave), _ptr(gxn), 1 if g else 0, B, C, T, w.shape[0], w.shape[2], stride,
+                                            float(eps), int(mode), _stream()), "ign_shapelet_bwd_input")
+    return gxn
+
+
 def _threshold_grads(gP, P, ws, saved, C):
     """LTS: dP/dthr = sigma'(thr - m) = P(1-P), summed over the batch  (IGN/model/Shapelet.py:109)"""
     gt = (gP * P * (1 - P)).sum(0)
@@ -207,7 +278,10 @@ class ShapeletBankFn(torch.autograd.Function):
         thrs = [t.contiguous() for t in params[n_groups:]] if (mode & GATE_LTS) else [None] * n_groups
         _need_gpu("shapelet_fwd", xn, *ws, *[t for t in thrs if t is not None])
         xn = xn.contiguous()
-        need_grad = any(ctx.needs_input_grad[5:])     # grad mode is off inside forward(); ask the node instead
+        if ctx.needs_input_grad[0]:
+            _input_grad_supported("shapelet_bank", mode)
+        # grad mode is off inside forward(); ask the node instead.  The distances are kept when the input alone needs a gradient.
+        need_grad = any(ctx.needs_input_grad[5:]) or ctx.needs_input_grad[0]
         P, D, saved = _bank_forward(xn, ws, thrs, eps, mode, strides, need_grad)
         Tstar = _cat_tstar(saved, xn.shape[0])
         ctx.mark_non_differentiable(D, Tstar)
@@ -226,9 +300,12 @@ class ShapeletBankFn(torch.autograd.Function):
         if gP is None:
             return (None,) * (5 + G + (G if mode & GATE_LTS else 0))
         gP = gP.contiguous()
+        gxn = _bank_backward_input(xn, ws, gP, P, D, saved, eps, mode) if ctx.needs_input_grad[0] else None
+        if not any(ctx.needs_input_grad[5:]):         # only the input needs a gradient: no weight / threshold work
+            return (gxn,) + (None,) * (4 + G + (G if mode & GATE_LTS else 0))
         grads_w = _bank_backward(xn, ws, gP, P, D, saved, eps, mode)
         grads_t = _threshold_grads(gP, P, ws, saved, xn.shape[1]) if mode & GATE_LTS else []
-        return (None, None, None, None, None, *grads_w, *grads_t)
+        return (gxn, None, None, None, None, *grads_w, *grads_t)
 
 
 def shapelet_bank(xn, weights, eps, mode=DIST_L1 | GATE_RBF, strides=None, thresholds=None, return_tstar=False):
@@ -266,7 +343,9 @@ class SbmFn(torch.autograd.Function):
         _need_gpu("sbm", xn, W, *ws, *[t for t in thrs if t is not None])
         xn, W = xn.contiguous(), W.contiguous()
         B, C, T = xn.shape
-        need_grad = any(ctx.needs_input_grad[2:])
+        if ctx.needs_input_grad[0]:
+            _input_grad_supported("sbm", mode)
+        need_grad = any(ctx.needs_input_grad[2:]) or ctx.needs_input_grad[0]
         L = _lib.lib()
         P, D, saved = _bank_forward(xn, ws, thrs, eps, mode, strides, need_grad)
         Tstar = _cat_tstar(saved, B) if want_tstar else None
@@ -303,14 +382,16 @@ class SbmFn(torch.autograd.Function):
         B, C, T = xn.shape
         L = _lib.lib()
         greg = greg.contiguous().reshape(1) if greg is not None else None
+        need_x, need_W, need_p = ctx.needs_input_grad[0], ctx.needs_input_grad[2], any(ctx.needs_input_grad[3:])
         gW = None
         if fuse_head and gout is not None:
             N, F_ = W.shape
             gout = gout.contiguous()
             gPh = torch.empty_like(P)
-            gW = torch.empty_like(W)
+            gW = torch.empty_like(W) if (need_W or not need_x) else None       # (frozen head under an input gradient: gX only)
             _lib.check(L.ign_head_bwd_acc(_ptr(gout), _ptr(P), _ptr(W), _ptr(gPh), _ptr(gW), None,
-                                          _ptr(gWreg) if greg is not None else None, _ptr(greg), B, F_, N, P.stride(0), _stream()),
+                                          _ptr(gWreg) if (greg is not None and gW is not None) else None, _ptr(greg), B, F_, N,
+                                          P.stride(0), _stream()),
                        "ign_head_bwd_acc")
             gP = gPh if gP is None else gPh + gP
         elif greg is not None and ctx.needs_input_grad[2]:
@@ -318,12 +399,15 @@ class SbmFn(torch.autograd.Function):
         if gP is None:             # nothing reached the gate outputs: only the regulariser moves the shapelets
             grads_w = [(gd * greg if (gdiv is not None and greg is not None) else None) for gd in (gdiv or [None] * G)]
             grads_t = [None] * G if mode & GATE_LTS else []
-        else:
-            gP = gP.contiguous()
-            add = gdiv if (gdiv is not None and greg is not None) else None
-            grads_w = _bank_backward(xn, ws, gP, P, D, saved, eps, mode, gw_add=add, add_scale=greg if add is not None else None)
-            grads_t = _threshold_grads(gP, P, ws, saved, C) if mode & GATE_LTS else []
-        return (None, None, gW, *grads_w, *grads_t)
+            return (None, None, gW, *grads_w, *grads_t)
+        gP = gP.contiguous()
+        gxn = _bank_backward_input(xn, ws, gP, P, D, saved, eps, mode) if need_x else None
+        if need_x and not need_p:          # only the input (and perhaps the head) needs a gradient: no weight / threshold work
+            return (gxn, None, gW) + (None,) * (G + (G if mode & GATE_LTS else 0))
+        add = gdiv if (gdiv is not None and greg is not None) else None
+        grads_w = _bank_backward(xn, ws, gP, P, D, saved, eps, mode, gw_add=add, add_scale=greg if add is not None else None)
+        grads_t = _threshold_grads(gP, P, ws, saved, C) if mode & GATE_LTS else []
+        return (gxn, None, gW, *grads_w, *grads_t)
 
 
 def _bl_strides(t, name):
