@@ -534,6 +534,14 @@ int ign_clconv_fwd(const float* x, const float* wt_fwd, const float* bias, const
 int ign_clconv_dgrad(const float* dyp, const float* wt_dgrad, const float* y_in, const float* a_in, const float* b_in,
                      const float* mean_in, const float* invstd_in, float* g_in, float* stat_part,
                      int B, int Tin, int Ci, int Co, int k, void* stream);
+/* ign_clconv_dgrad_input: the data gradient of a convolution whose input is RAW DATA (the expert's first block: no BatchNorm / ReLU
+ *   below it), gx[b,t,ci] = sum_{jj,co} dyp[b,t+jj,co] w[co,ci,k-1-jj]  (gx (B,Tin,Ci); dyp, wt_dgrad as for ign_clconv_dgrad).
+ *   Plain epilogue: no bias, no mask, no partial sums, nothing written outside gx.  Any Ci >= 1 (the channel count of the data:
+ *   122, 6, 3, 1 -- ragged n-tiles store per column), Co % 4 == 0.  Fixed-order sums, no atomics: bitwise repeatable.  The _x6 /
+ *   _bf16 / _h3 forms (declared with their siblings below) take the packed transposed weights of their arithmetic, k <= 16;
+ *   _h3 the bounds of |dL/dy| and |W|.  Timed under "clconv_dgrad_input".  What the saliency of the gated mixture runs
+ *   (utils/saliency.py, explain="gated" / "dnn"); the reference gets it from autograd through nn.Conv1d (IGN/model/FullyConvNet.py:32). */
+int ign_clconv_dgrad_input(const float* dyp, const float* wt_dgrad, float* gx, int B, int Tin, int Ci, int Co, int k, void* stream);
 /* Split-bf16 ("x6") variants of fwd / dgrad: the same maths at fp32 rounding-level accuracy on the bf16 matrix cores.
  * gfx950 executes fp32-input MFMA at the fp32 vector rate; here every fp32 operand is split exactly into three bf16 terms
  * and the six partial products of weight >= 2^-16 are accumulated in fp32 (v_mfma_f32_32x32x16_bf16): 2.7x the fp32-MFMA
@@ -553,6 +561,7 @@ int ign_clconv_fwd_x6(const float* x, const void* wt3_fwd, const float* bias, co
 int ign_clconv_dgrad_x6(const float* dyp, const void* wt3_dgrad, const float* y_in, const float* a_in, const float* b_in,
                         const float* mean_in, const float* invstd_in, float* g_in, float* stat_part,
                         int B, int Tin, int Ci, int Co, int k, void* stream);
+int ign_clconv_dgrad_input_x6(const float* dyp, const void* wt3_dgrad, float* gx, int B, int Tin, int Ci, int Co, int k, void* stream);
 /* Weight gradient on the bf16 matrix cores (same split): operands staged row-major and read with the transposing LDS read
  * ds_read_b64_tr_b16; one staged input span serves all k taps.  k in {2, 3, 5, 8} (the FCN expert's kernels), Co % 4 == 0;
  * k = 1 (a Linear layer over the B*Tin rows; needs Ci % 4 == 0, dy_pad == 0, no prologue) runs 128 x 128 tiles instead.
@@ -623,6 +632,8 @@ int ign_linear_dgrad_gelu_h3(const float* g, const void* wd_h2, const float* u, 
 int ign_clconv_dgrad_h3(const float* dyp, const void* wt_h2_dgrad, const float* y_in, const float* a_in, const float* b_in,
                         const float* mean_in, const float* invstd_in, float* g_in, float* stat_part, const float* bound_dy,
                         const float* bound_w, int B, int Tin, int Ci, int Co, int k, void* stream);
+int ign_clconv_dgrad_input_h3(const float* dyp, const void* wt_h2_dgrad, float* gx, const float* bound_dy, const float* bound_w,
+                              int B, int Tin, int Ci, int Co, int k, void* stream);
 int ign_clconv_wgrad_h3(const float* dyp, int dy_pad, const float* x, const float* pro_a, const float* pro_b, float* dw_oik,
                         void* workspace, const float* bound_dy, const float* bound_x, int B, int Tin, int Ci, int Co, int k,
                         void* stream);
@@ -640,6 +651,8 @@ int ign_clconv_fwd_bf16(const float* x, const void* wt3_fwd, const float* bias, 
 int ign_clconv_dgrad_bf16(const float* dyp, const void* wt3_dgrad, const float* y_in, const float* a_in, const float* b_in,
                           const float* mean_in, const float* invstd_in, float* g_in, float* stat_part,
                           int B, int Tin, int Ci, int Co, int k, void* stream);
+int ign_clconv_dgrad_input_bf16(const float* dyp, const void* wt3_dgrad, float* gx, int B, int Tin, int Ci, int Co, int k,
+                                void* stream);
 int ign_clconv_wgrad_bf16(const float* dyp, int dy_pad, const float* x, const float* pro_a, const float* pro_b,
                           float* dw_oik, void* workspace, int B, int Tin, int Ci, int Co, int k, void* stream);
 /* A Linear layer's weight AND bias gradient in one pass over dy (M, Co) and x (M, Ci): dW = dy^T x on the split-bf16 k = 1 kernel,
@@ -660,7 +673,7 @@ int ign_clconv_wgrad(const float* dyp, int dy_pad, const float* x, const float* 
  * affine_eval: the same a, b, mean, invstd from the running statistics (module.eval()).
  * relu_pool_fwd: pooled[b,c] = mean_t relu(a_c*y[b,t,c] + b_c)            (BatchNorm + ReLU + AdaptiveAvgPool1d(1)).
  * relu_pool_bwd: g[b,t,c] = gpool[b,c]/T * [a_c*y + b_c > 0] and per-block partials (ign_bn_relu_pool_bwd_parts(B,T), 2, C)
- *   of sum g and sum g*yhat.
+ *   of sum g and sum g*yhat (part NULL: the sums are not written -- an input-only backward with running statistics reads none).
  * finalize_bwd: partials -> dbeta = sum g, dgamma = sum g*yhat.
  * bwd_apply: dy = a*(g - (dbeta + yhat*dgamma)/R) [training] or a*g [eval], written into (B, pad + T + pad, C) with the
  *   pad rows zeroed (the layout ign_clconv_dgrad / ign_clconv_wgrad read).                                          */

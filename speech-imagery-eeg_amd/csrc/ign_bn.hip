@@ -174,9 +174,12 @@ __global__ void __launch_bounds__(256) bn_relu_pool_bwd_kernel(const float* __re
             }
             vstore<4>(g + off, gg);
         }
+        if (part) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) { sm[rofs * C + col + q] = s0[q]; sm[(rif + rofs) * C + col + q] = s1[q]; }
+            for (int q = 0; q < 4; ++q) { sm[rofs * C + col + q] = s0[q]; sm[(rif + rofs) * C + col + q] = s1[q]; }
+        }
     }
+    if (!part) return;                                    // (uniform) nobody reads the sums: an input-only backward in eval mode
     __syncthreads();
     const size_t pi = (size_t)bi * gridDim.x + blockIdx.x;
     for (int c = threadIdx.x; c < C; c += 256) {
@@ -430,7 +433,7 @@ extern "C" int ign_bn_relu_pool_bwd(const float* y, const float* gpool, const fl
                                     const float* invstd, float* g, float* part, int B, int T, int C, void* stream) {
     int rc;
     if ((rc = bn_check("ign_bn_relu_pool_bwd", (long long)B * T, C))) return rc;
-    if (!y || !gpool || !a || !b || !mean || !invstd || !g || !part) { ign_set_error("ign_bn_relu_pool_bwd: null pointer"); return IGN_E_ARG; }
+    if (!y || !gpool || !a || !b || !mean || !invstd || !g) { ign_set_error("ign_bn_relu_pool_bwd: null pointer"); return IGN_E_ARG; }
     const int rif = 256 / (C / 4);
     IgnScopedTimer tm("bn_relu_pool_bwd", (hipStream_t)stream);
     hipLaunchKernelGGL(bn_relu_pool_bwd_kernel, dim3((T + POOL_ROWS - 1) / POOL_ROWS, B), dim3(256), (size_t)2 * rif * C * 4,

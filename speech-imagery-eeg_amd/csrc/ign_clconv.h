@@ -44,7 +44,8 @@ __device__ __forceinline__ void vstore(float* p, const float (&d)[V]) {
     else *p = d[0];
 }
 
-enum { EPI_BIAS_STATS = 0, EPI_MASK_STATS = 1, EPI_GELU_BWD = 2 };
+// EPI_PLAIN: C = acc and nothing else -- no bias, no mask, no partial sums (the data gradient into the raw input series)
+enum { EPI_BIAS_STATS = 0, EPI_MASK_STATS = 1, EPI_GELU_BWD = 2, EPI_PLAIN = 3 };
 
 // d gelu(u) / du of the exact (erf) GELU, as aten::gelu_backward evaluates it: Phi(u) + u phi(u)
 __device__ __forceinline__ float ign_gelu_grad(float u) {
@@ -111,7 +112,7 @@ __device__ __forceinline__ void nt_epilogue_body(const GemmNTArgs& a, const f32x
                     if (ok) { s1[j] += v; s2[j] = fmaf(v, v, s2[j]); }
                 } else if (EPI == EPI_GELU_BWD) {
                     v *= ign_gelu_grad(yv[r]);
-                } else {
+                } else if (EPI == EPI_MASK_STATS) {
                     v = (fmaf(ea, yv[r], eb) > 0.f) ? v : 0.f;
                     if (ok) { s1[j] += v; s2[j] = fmaf(v, (yv[r] - em) * ei, s2[j]); }
                 }

@@ -358,9 +358,14 @@ template <int EPI>
 static int launch_nt(const GemmNTArgs& a, int V, bool pro, hipStream_t s) {
     const dim3 grid((unsigned)(a.mtiles * a.ntiles)), block(256);
 #define IGN_NT(VV, PP) hipLaunchKernelGGL((clconv_nt_kernel<VV, PP, EPI>), grid, block, 0, s, a)
-    if (V == 4) { if (pro) IGN_NT(4, true); else IGN_NT(4, false); }
-    else if (V == 2) { if (pro) IGN_NT(2, true); else IGN_NT(2, false); }
-    else { if (pro) IGN_NT(1, true); else IGN_NT(1, false); }
+    if constexpr (EPI == EPI_PLAIN) {           // (no prologue variant: its operand is a gradient)
+        if (pro) { ign_set_error("clconv_nt_kernel: the plain epilogue has no prologue variant"); return IGN_E_UNSUP; }
+        if (V == 4) IGN_NT(4, false); else if (V == 2) IGN_NT(2, false); else IGN_NT(1, false);
+    } else {
+        if (V == 4) { if (pro) IGN_NT(4, true); else IGN_NT(4, false); }
+        else if (V == 2) { if (pro) IGN_NT(2, true); else IGN_NT(2, false); }
+        else { if (pro) IGN_NT(1, true); else IGN_NT(1, false); }
+    }
 #undef IGN_NT
     return ign_check_launch("clconv_nt_kernel");
 }
@@ -455,10 +460,11 @@ extern "C" int ign_linear_dgrad_gelu_h3(const float* g, const void* wd_h2, const
 static int clconv_dgrad_impl(const char* who, int x6, const float* dyp, const void* wt_dgrad, const float* y_in, const float* a_in,
                              const float* b_in, const float* mean_in, const float* invstd_in, float* g_in, float* stat_part, int B,
                              int Tin, int Ci, int Co, int k, void* stream, const float* bound_a = nullptr,
-                             const float* bound_w = nullptr) {
+                             const float* bound_w = nullptr, int epi = EPI_MASK_STATS) {
     const int Tout = Tin - k + 1;
-    if (!dyp || !wt_dgrad || !y_in || !a_in || !b_in || !mean_in || !invstd_in || !g_in || B <= 0 || Ci <= 0 || Co <= 0 || k <= 0 ||
-        Tout <= 0) {
+    const bool masked = epi == EPI_MASK_STATS;      // else EPI_PLAIN: the layer below is raw data, g_in = dL/dx and nothing else
+    if (!dyp || !wt_dgrad || (masked && (!y_in || !a_in || !b_in || !mean_in || !invstd_in)) || !g_in || B <= 0 || Ci <= 0 || Co <= 0 ||
+        k <= 0 || Tout <= 0) {
         ign_set_error("%s: bad argument (B=%d Tin=%d Ci=%d Co=%d k=%d)", who, B, Tin, Ci, Co, k);
         return IGN_E_ARG;
     }
@@ -471,17 +477,18 @@ static int clconv_dgrad_impl(const char* who, int x6, const float* dyp, const vo
     a.B3 = x6 ? (const unsigned short*)wt_dgrad : nullptr; a.Kp = 0;
     a.part = stat_part; a.ey = y_in; a.ea = a_in; a.eb = b_in; a.emean = mean_in; a.einv = invstd_in;
     a.mtiles = (int)((M + TM - 1) / TM); a.ntiles = (Ci + TN - 1) / TN;
-    IgnScopedTimer tm("clconv_dgrad", (hipStream_t)stream);
+    if (x6 && k > 16) { ign_set_error("%s: k=%d > 16 taps", who, k); return IGN_E_UNSUP; }
+    IgnScopedTimer tm(masked ? "clconv_dgrad" : "clconv_dgrad_input", (hipStream_t)stream);
     if (x6) {
-        if (k > 16) { ign_set_error("%s: k=%d > 16 taps", who, k); return IGN_E_UNSUP; }
         ConvX6Args c{};
         c.g = a;
         c.cin = Co; c.cp = (Co + 15) / 16 * 16; c.k = k; c.g.Kp = k * c.cp;
         c.sample_pitch = (long long)(Tout + 2 * (k - 1)) * Co; c.rows_in = Tout + 2 * (k - 1); c.trows = Tin; c.tps = (Tin + TM - 1) / TM;
         c.g.mtiles = B * c.tps; c.nprod = x6; c.bound_a = bound_a; c.bound_b = bound_w;
-        return ign_clconv_launch_x6t(c, EPI_MASK_STATS, ign_vec_width(Co), false, (hipStream_t)stream);
+        return ign_clconv_launch_x6t(c, epi, ign_vec_width(Co), false, (hipStream_t)stream);
     }
-    return launch_nt<EPI_MASK_STATS>(a, ign_vec_width(Co), false, (hipStream_t)stream);
+    return masked ? launch_nt<EPI_MASK_STATS>(a, ign_vec_width(Co), false, (hipStream_t)stream)
+                  : launch_nt<EPI_PLAIN>(a, ign_vec_width(Co), false, (hipStream_t)stream);
 }
 
 extern "C" int ign_clconv_dgrad(const float* dyp, const float* wt_dgrad, const float* y_in, const float* a_in, const float* b_in,
@@ -511,6 +518,36 @@ extern "C" int ign_clconv_dgrad_h3(const float* dyp, const void* wt_h2_dgrad, co
     if (!bound_dy || !bound_w) { ign_set_error("ign_clconv_dgrad_h3: null operand bound"); return IGN_E_ARG; }
     return clconv_dgrad_impl("ign_clconv_dgrad_h3", 3, dyp, wt_h2_dgrad, y_in, a_in, b_in, mean_in, invstd_in, g_in, stat_part, B,
                              Tin, Ci, Co, k, stream, bound_dy, bound_w);
+}
+
+// The data gradient of a convolution whose input is RAW DATA (the FCN expert's first block): the same GEMM, the plain epilogue --
+// gx = dL/dx (B, Tin, Ci) for any Ci >= 1 (ragged n-tiles store per column), nothing else written.  Co % 4 == 0.
+static int clconv_dgrad_input_impl(const char* who, int x6, const float* dyp, const void* wt_dgrad, float* gx, int B, int Tin, int Ci,
+                                   int Co, int k, void* stream, const float* bound_dy = nullptr, const float* bound_w = nullptr) {
+    if (Co > 0 && Co % 4) { ign_set_error("%s: needs Co %% 4 == 0 (Co=%d)", who, Co); return IGN_E_UNSUP; }
+    return clconv_dgrad_impl(who, x6, dyp, wt_dgrad, nullptr, nullptr, nullptr, nullptr, nullptr, gx, nullptr, B, Tin, Ci, Co, k, stream,
+                             bound_dy, bound_w, EPI_PLAIN);
+}
+
+extern "C" int ign_clconv_dgrad_input(const float* dyp, const float* wt_dgrad, float* gx, int B, int Tin, int Ci, int Co, int k,
+                                      void* stream) {
+    return clconv_dgrad_input_impl("ign_clconv_dgrad_input", 0, dyp, wt_dgrad, gx, B, Tin, Ci, Co, k, stream);
+}
+
+extern "C" int ign_clconv_dgrad_input_x6(const float* dyp, const void* wt3_dgrad, float* gx, int B, int Tin, int Ci, int Co, int k,
+                                         void* stream) {
+    return clconv_dgrad_input_impl("ign_clconv_dgrad_input_x6", 6, dyp, wt3_dgrad, gx, B, Tin, Ci, Co, k, stream);
+}
+
+extern "C" int ign_clconv_dgrad_input_bf16(const float* dyp, const void* wt3_dgrad, float* gx, int B, int Tin, int Ci, int Co, int k,
+                                           void* stream) {
+    return clconv_dgrad_input_impl("ign_clconv_dgrad_input_bf16", 1, dyp, wt3_dgrad, gx, B, Tin, Ci, Co, k, stream);
+}
+
+extern "C" int ign_clconv_dgrad_input_h3(const float* dyp, const void* wt_h2_dgrad, float* gx, const float* bound_dy, const float* bound_w,
+                                         int B, int Tin, int Ci, int Co, int k, void* stream) {
+    if (!bound_dy || !bound_w) { ign_set_error("ign_clconv_dgrad_input_h3: null operand bound"); return IGN_E_ARG; }
+    return clconv_dgrad_input_impl("ign_clconv_dgrad_input_h3", 3, dyp, wt_h2_dgrad, gx, B, Tin, Ci, Co, k, stream, bound_dy, bound_w);
 }
 
 static int wgrad_splits(long long M, int tiles) {

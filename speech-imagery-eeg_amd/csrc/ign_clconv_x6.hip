@@ -901,9 +901,14 @@ static int launch_x6t(const ConvX6Args& a, int V, bool pro, hipStream_t s) {
         }                                                                                                                    \
         hipLaunchKernelGGL((clconv_x6t_kernel<VV, PP, EPI, NP>), grid, block, X6tLds<NP>::BYTES, s, a);                       \
     } while (0)
-    if (V == 4) { if (pro) IGN_X6T(4, true); else IGN_X6T(4, false); }
-    else if (V == 2) { if (pro) IGN_X6T(2, true); else IGN_X6T(2, false); }
-    else { if (pro) IGN_X6T(1, true); else IGN_X6T(1, false); }
+    if constexpr (EPI == EPI_PLAIN) {           // (no prologue variant: its operand is a gradient)
+        if (pro) { ign_set_error("clconv_x6t_kernel: the plain epilogue has no prologue variant"); return IGN_E_UNSUP; }
+        if (V == 4) IGN_X6T(4, false); else if (V == 2) IGN_X6T(2, false); else IGN_X6T(1, false);
+    } else {
+        if (V == 4) { if (pro) IGN_X6T(4, true); else IGN_X6T(4, false); }
+        else if (V == 2) { if (pro) IGN_X6T(2, true); else IGN_X6T(2, false); }
+        else { if (pro) IGN_X6T(1, true); else IGN_X6T(1, false); }
+    }
 #undef IGN_X6T
     return ign_check_launch("clconv_x6t_kernel");
 }
@@ -935,6 +940,9 @@ int ign_clconv_launch_x6t(const ConvX6Args& a, int epi, int V, bool pro, hipStre
     if (a.k == 1 && a.g.N % 256 == 0 && V == 4 && !pro && epi == EPI_BIAS_STATS && !a.g.part &&
         a.tps * 1 == a.g.mtiles && a.trows == a.g.M)
         return a.nprod == 1 ? launch_x6w<1>(a, s) : a.nprod == 3 ? launch_x6w<2>(a, s) : launch_x6w<3>(a, s);
+    if (epi == EPI_PLAIN)
+        return a.nprod == 1 ? launch_x6t<EPI_PLAIN, 1>(a, V, pro, s) : a.nprod == 3 ? launch_x6t<EPI_PLAIN, 2>(a, V, pro, s)
+                                                                                      : launch_x6t<EPI_PLAIN, 3>(a, V, pro, s);
     if (a.nprod == 1)
         return epi == EPI_BIAS_STATS ? launch_x6t<EPI_BIAS_STATS, 1>(a, V, pro, s) : launch_x6t<EPI_MASK_STATS, 1>(a, V, pro, s);
     if (a.nprod == 3)

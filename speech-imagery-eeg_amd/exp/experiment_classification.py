@@ -374,17 +374,18 @@ class Experiment(object):
         self.model.train()
         return loss, acc
 
-    def saliency(self, loader=None, target=None):
-        """Input saliency of the interpretable expert over `loader` (default: the test loader) -> one host tensor (N,T,C):
-        per sample the gradient of a class logit w.r.t. the input series (utils.saliency.input_saliency; SBM / LTS / InterpGN).
-        `target`: an int, or None for each sample's predicted class."""
+    def saliency(self, loader=None, target=None, explain="sbm"):
+        """Input saliency over `loader` (default: the test loader) -> one host tensor (N,T,C): per sample the gradient of a class
+        logit w.r.t. the input series (utils.saliency.input_saliency; SBM / LTS / InterpGN).
+        `target`: an int, or None for each sample's predicted class.  `explain`: "sbm" (the interpretable expert, the default),
+        "gated" (the mixture an InterpGN with the FCN expert predicts with) or "dnn" (the FCN expert's logits)."""
         from utils.saliency import input_saliency
         out = []
         for batch_x, label, padding_mask in (self.test_loader if loader is None else loader):
             if batch_x.size(0) == 0:
                 continue
             batch_x, _, _ = self._to_device(batch_x, label, padding_mask)
-            out.append(input_saliency(self.model, batch_x, target).cpu())
+            out.append(input_saliency(self.model, batch_x, target, explain=explain).cpu())
         if not out:
             return torch.empty(0, self.args.seq_len, self.args.enc_in)
         return torch.cat(out)

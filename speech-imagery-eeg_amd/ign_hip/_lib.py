@@ -124,6 +124,10 @@ SIGNATURES = {
     "ign_clconv_dgrad_h3": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]),
     "ign_clconv_wgrad_h3": (ci, [vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]),
     "ign_linear_wgrad_h3": (ci, [vp, vp, vp, vp, vp, vp, vp, ll, ci, ci, vp]),
+    "ign_clconv_dgrad_input": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, vp]),
+    "ign_clconv_dgrad_input_x6": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, vp]),
+    "ign_clconv_dgrad_input_bf16": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, vp]),
+    "ign_clconv_dgrad_input_h3": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]),
     "ign_bn_bwd_apply_amax": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]),
     "ign_head_bwd_acc": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ll, vp]),
     "ign_loss_fwd_bwd_reg": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, cf, vp]),

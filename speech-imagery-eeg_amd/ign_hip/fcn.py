@@ -79,12 +79,13 @@ class BnState:
 
 
 class FcnBodyFn(torch.autograd.Function):
-    """forward(x (B,T,C), states, w1, b1, gamma1, beta1, w2, ..., beta3) -> pooled (B, C3)."""
+    """forward(x (B,T,C), states, w1, b1, gamma1, beta1, w2, ..., beta3) -> pooled (B, C3).
+    The gradient w.r.t. x is opt-in (fcn_body's `input_grad`): without it the backward refuses one, as inputs are data."""
 
     @staticmethod
     def forward(ctx, x, states_arith, *params):
         L = _lib.lib()
-        states, arith, has_head = states_arith
+        states, arith, has_head, input_grad = states_arith
         head_w, head_b = (params[-2], params[-1]) if has_head else (None, None)
         if has_head:
             params = params[:-2]
@@ -96,6 +97,9 @@ class FcnBodyFn(torch.autograd.Function):
         dev = x.device
         f32 = dict(device=dev, dtype=torch.float32)
         need_grad = any(ctx.needs_input_grad[2:2 + len(params)])
+        want_gx = bool(input_grad and ctx.needs_input_grad[0])
+        # the transposed tap-reversed weights: blocks 2.. whenever a backward runs, block 1 only for the gradient into x
+        need_dx = [(need_grad or want_gx) if l else want_gx for l in range(nl)]
         slots = zbuf = xbound = None
         inputs, affine, wds, shapes = [x], [], [], []
         pa = pb = None
@@ -107,7 +111,7 @@ class FcnBodyFn(torch.autograd.Function):
             wts = [torch.empty(int(L.ign_clconv_x3_elems(w.shape[0], w.shape[1], w.shape[2])), device=dev, dtype=torch.bfloat16)
                    for w in ws_]
             wds_ = [torch.empty(int(L.ign_clconv_x3_elems(w.shape[1], w.shape[0], w.shape[2])), device=dev, dtype=torch.bfloat16)
-                    if (l > 0 and need_grad) else None for l, w in enumerate(ws_)]
+                    if need_dx[l] else None for l, w in enumerate(ws_)]
             vpa, ia, lla = ctypes.c_void_p * nl, ctypes.c_int * nl, ctypes.c_longlong * nl
             pv = lambda ts: vpa(*[(t.data_ptr() if t is not None else None) for t in ts])
             bumps = [st.bump for st in states]
@@ -159,7 +163,7 @@ class FcnBodyFn(torch.autograd.Function):
             y = torch.empty(B, Tout, Co, **f32)
             nparts = int(L.ign_clconv_mtiles(B * Tout) if arith == ops.GEMM_F32 else L.ign_clconv_x6_mtiles(B, Tout))
             part = torch.empty(nparts, 2, Co, **f32) if st.use_batch_stats else None
-            wt, wd = (packed[0][l], packed[1][l]) if packed is not None else ops._pack_weights(arith, w, l > 0 and need_grad)
+            wt, wd = (packed[0][l], packed[1][l]) if packed is not None else ops._pack_weights(arith, w, need_dx[l])
             ops._clconv_fwd(arith, h, wt, b, pa, pb, y, part, (B, Tin, Ci, Co, k), _slot(slots, 4 * l + 1) if l else _ptr(xbound),
                             _slot(slots, 4 * l))
             a, bb, mean, invstd = (torch.empty(Co, **f32) for _ in range(4))
@@ -197,15 +201,16 @@ class FcnBodyFn(torch.autograd.Function):
         ctx.head = head
         ctx.head_needs = tuple(ctx.needs_input_grad[-2:]) if has_head else None
         ctx.saved = (inputs, affine, wds, shapes, [st.use_batch_stats for st in states], arith, slots, zbuf, xbound) \
-            if (need_grad or (has_head and any(ctx.head_needs))) else None
+            if (need_grad or want_gx or (has_head and any(ctx.head_needs))) else None
         ctx.body_grad = need_grad
+        ctx.want_gx = want_gx
         return out
 
     @staticmethod
     def backward(ctx, gpool):
         if ctx.saved is None:
             raise _lib.IgnError("fcn_body backward called but the forward ran without parameter gradients enabled")
-        if ctx.needs_input_grad[0]:
+        if ctx.needs_input_grad[0] and not ctx.want_gx:
             raise _lib.IgnError("fcn_body: gradient w.r.t. the input series is not implemented (inputs are data)")
         L = _lib.lib()
         inputs, affine, wds, shapes, batch_stats, arith, slots, zbuf, xbound = ctx.saved
@@ -214,19 +219,21 @@ class FcnBodyFn(torch.autograd.Function):
         dev = gpool.device
         f32 = dict(device=dev, dtype=torch.float32)
         gpool = gpool.contiguous()
+        need_w, want_gx = ctx.body_grad, ctx.want_gx
         head_grads = ()
         if ctx.head is not None:
-            # gpool is the gradient of the LOGITS here: head backward first (pooled-row gradient, weight and bias gradients, one launch)
+            # gpool is the gradient of the LOGITS here: head backward first (pooled-row gradient, weight and bias gradients, one launch;
+            # the pooled-row gradient alone in an input-only backward)
             pooled, head_w, has_b = ctx.head
             N, Cl = head_w.shape
             glog = gpool
             gpool = torch.empty(B, Cl, **f32)
-            ghw = torch.empty_like(head_w)
-            ghb = torch.empty(N, **f32) if has_b else None
+            ghw = torch.empty_like(head_w) if (need_w or any(ctx.head_needs)) else None
+            ghb = torch.empty(N, **f32) if (has_b and ghw is not None) else None
             _lib.check(L.ign_head_bwd(_ptr(glog), _ptr(pooled), _ptr(head_w), _ptr(gpool), _ptr(ghw), _ptr(ghb), B, Cl, N, Cl, _stream()),
                        "ign_head_bwd")
             head_grads = (ghw if ctx.head_needs[0] else None, ghb if ctx.head_needs[1] else None)
-            if not ctx.body_grad:
+            if not (need_w or want_gx):
                 ctx.saved = None
                 return (None, None, *([None] * (4 * nl)), *head_grads)
         grads = [None] * (4 * nl)
@@ -236,8 +243,11 @@ class FcnBodyFn(torch.autograd.Function):
         for (Co_, _, _, _, _), bs_ in zip(shapes, batch_stats):
             zoff.append(ztot)
             ztot += Co_ if bs_ else 0
-        if zbuf is None or zbuf.numel() != ztot:      # (the fp16 path's forward prologue has cleared one of the right size)
+        if need_w and (zbuf is None or zbuf.numel() != ztot):      # (the fp16 path's forward prologue has cleared one of the right size)
             zbuf = torch.zeros(ztot, **f32) if ztot else None
+        # The BatchNorm-backward sums of a block are read by its parameter gradients and, with batch statistics, by dL/dy: an
+        # input-only backward (saliency: every parameter frozen) through running statistics needs none of them
+        sums = [need_w or bs_ for bs_ in batch_stats]
 
         # last block: pool -> ReLU mask -> BatchNorm-backward sums
         Co, Ci, k, Tin, Tout = shapes[-1]
@@ -245,19 +255,23 @@ class FcnBodyFn(torch.autograd.Function):
         y = inputs[-1]
         g = torch.empty_like(y)
         nparts = int(L.ign_bn_relu_pool_bwd_parts(B, Tout))
-        part = torch.empty(nparts, 2, Co, **f32)
+        part = torch.empty(nparts, 2, Co, **f32) if sums[-1] else None
         _lib.check(L.ign_bn_relu_pool_bwd(_ptr(y), _ptr(gpool), _ptr(a), _ptr(bb), _ptr(mean), _ptr(invstd), _ptr(g), _ptr(part),
                                           B, Tout, Co, _stream()), "ign_bn_relu_pool_bwd")
         # weight-gradient partials of every block are reduced by ONE launch at the end (split-bf16 kernels with k in 2,3,5,8)
         defer = all(_wgrad_arith(arith, sh[2]) != ops.GEMM_F32 for sh in shapes) and nl <= 8
         deferred = []
+        gx = None
         for l in range(nl - 1, -1, -1):
             Co, Ci, k, Tin, Tout = shapes[l]
             a, bb, mean, invstd = affine[l]
             y = inputs[l + 1]
-            dbeta, dgamma = torch.empty(Co, **f32), torch.empty(Co, **f32)
-            _lib.check(L.ign_bn_finalize_bwd(_ptr(part), nparts, Co, _ptr(dbeta), _ptr(dgamma), _stream()), "ign_bn_finalize_bwd")
-            pad = (k - 1) if l > 0 else 0
+            dbeta = dgamma = None
+            if sums[l]:
+                dbeta, dgamma = torch.empty(Co, **f32), torch.empty(Co, **f32)
+                _lib.check(L.ign_bn_finalize_bwd(_ptr(part), nparts, Co, _ptr(dbeta), _ptr(dgamma), _stream()), "ign_bn_finalize_bwd")
+            # (the zero rows the data-gradient GEMM reads; the weight gradient skips them: same sums, same bits)
+            pad = (k - 1) if (l > 0 or want_gx) else 0
             dyp = torch.empty(B, Tout + 2 * pad, Co, **f32)
             training = 1 if batch_stats[l] else 0
             # (fp16 path: the kernel also takes max |dL/dy| as it writes the tensor -- the bound its two consumers scale by)
@@ -265,28 +279,39 @@ class FcnBodyFn(torch.autograd.Function):
                                                _slot(slots, 4 * l + 2), B, Tout, Co, pad, training, _stream()),
                        "ign_bn_bwd_apply_amax")
             if DEBUG is not None:
-                DEBUG[f"g{l}"], DEBUG[f"dyp{l}"], DEBUG[f"dbeta{l}"], DEBUG[f"dgamma{l}"] = g.clone(), dyp.clone(), dbeta.clone(), dgamma.clone()
+                DEBUG[f"g{l}"], DEBUG[f"dyp{l}"] = g.clone(), dyp.clone()
+                if sums[l]:
+                    DEBUG[f"dbeta{l}"], DEBUG[f"dgamma{l}"] = dbeta.clone(), dgamma.clone()
             del g
-            # weight gradient; the operand below is relu(bn(y_{l-1})) recomputed on the fly (raw x for the first block)
-            pa, pb = (affine[l - 1][0], affine[l - 1][1]) if l > 0 else (None, None)
-            dw = torch.empty(Co, Ci, k, **f32)
-            ws = ops._clconv_wgrad(_wgrad_arith(arith, k), dyp, pad, inputs[l], pa, pb, None if defer else dw, (B, Tin, Ci, Co, k),
-                                   _slot(slots, 4 * l + 2), _slot(slots, 4 * l + 1) if l else _ptr(xbound))
-            if defer:
-                deferred.append((ws, dw, int(L.ign_clconv_wgrad_x6_nsplit(B, Tin, Ci, Co, k)), Co, Ci, k))
-            del ws
-            grads[4 * l + 0] = dw
-            # bias: zero with batch statistics (see above); with running statistics it is the column sum of dL/dy
-            grads[4 * l + 1] = zbuf[zoff[l]:zoff[l] + Co] if training else dyp.sum(dim=(0, 1))
-            grads[4 * l + 2] = dgamma
-            grads[4 * l + 3] = dbeta
+            if need_w:
+                # weight gradient; the operand below is relu(bn(y_{l-1})) recomputed on the fly (raw x for the first block)
+                pa, pb = (affine[l - 1][0], affine[l - 1][1]) if l > 0 else (None, None)
+                dw = torch.empty(Co, Ci, k, **f32)
+                ws = ops._clconv_wgrad(_wgrad_arith(arith, k), dyp, pad, inputs[l], pa, pb, None if defer else dw, (B, Tin, Ci, Co, k),
+                                       _slot(slots, 4 * l + 2), _slot(slots, 4 * l + 1) if l else _ptr(xbound))
+                if defer:
+                    deferred.append((ws, dw, int(L.ign_clconv_wgrad_x6_nsplit(B, Tin, Ci, Co, k)), Co, Ci, k))
+                del ws
+                grads[4 * l + 0] = dw
+                # bias: zero with batch statistics (see above); with running statistics it is the column sum of dL/dy (block 1 padded
+                # for the input gradient: summed as the unpadded tensor it otherwise is, so the bits do not depend on that option)
+                if training:
+                    grads[4 * l + 1] = zbuf[zoff[l]:zoff[l] + Co]
+                else:
+                    grads[4 * l + 1] = (dyp[:, pad:pad + Tout].contiguous() if (l == 0 and pad) else dyp).sum(dim=(0, 1))
+                grads[4 * l + 2] = dgamma
+                grads[4 * l + 3] = dbeta
             if l > 0:
                 pa_, pb_, pm_, pi_ = affine[l - 1]
                 g = torch.empty(B, Tin, Ci, **f32)
                 nparts = int(L.ign_clconv_mtiles(B * Tin) if arith == ops.GEMM_F32 else L.ign_clconv_x6_mtiles(B, Tin))
-                part = torch.empty(nparts, 2, Ci, **f32)
+                part = torch.empty(nparts, 2, Ci, **f32) if sums[l - 1] else None
                 ops._clconv_dgrad(arith, dyp, wds[l], inputs[l], pa_, pb_, pm_, pi_, g, part, (B, Tin, Ci, Co, k),
                                   _slot(slots, 4 * l + 2), _slot(slots, 4 * l))
+            elif want_gx:
+                # into the raw series: no block below, plain epilogue, any channel count
+                gx = torch.empty(B, Tin, Ci, **f32)
+                ops._clconv_dgrad_input(arith, dyp, wds[0], gx, (B, Tin, Ci, Co, k), _slot(slots, 4 * l + 2), _slot(slots, 4 * l))
             del dyp
         if deferred:
             n = len(deferred)
@@ -296,14 +321,17 @@ class FcnBodyFn(torch.autograd.Function):
                                                        ia(*[d[4] for d in deferred]), ia(*[d[5] for d in deferred]), _stream()),
                        "ign_clconv_wgrad_reduce_multi")
         ctx.saved = None
-        return (None, None, *grads, *head_grads)
+        return (gx, None, *grads, *head_grads)
 
 
-def fcn_body(x, blocks, math=None, head=None):
+def fcn_body(x, blocks, math=None, head=None, input_grad=False):
     """x (B,T,C) float32 on the GPU; blocks = [(conv1d, batchnorm1d), ...] -> pooled (B, C_last).
     `math`: arithmetic of the GEMMs (see CONV_MATH, _fcn_arith); default = "bf16" inside an autocast region, else CONV_MATH.
     `head`: an nn.Linear over the pooled channels (<= ops.HEAD_NMAX outputs) -> its logits (B, N) are returned instead, computed by the
-    pooling launch."""
+    pooling launch.
+    `input_grad`: with it (and x.requires_grad) the backward also returns dL/dx -- block 1's data-gradient GEMM into the raw series
+    (ign_clconv_dgrad_input*).  Off (the default) an input that requires a gradient makes the backward raise: inputs are data.  The
+    parameter gradients are the same bits either way; with every parameter frozen the backward is input-only (no weight gradient)."""
     states = [BnState(bn) for _, bn in blocks]            # (the step counters are bumped by the node's prologue launch)
     arith = _fcn_arith(math, torch.is_autocast_enabled(), states)
     params = []
@@ -317,5 +345,5 @@ def fcn_body(x, blocks, math=None, head=None):
         if head.weight.shape[0] > ops.HEAD_NMAX:
             raise _lib.IgnError(f"fcn_body: the fused head covers up to {ops.HEAD_NMAX} outputs")
         # (a head without bias passes a None placeholder: autograd.Function accepts non-tensor inputs)
-        return FcnBodyFn.apply(x, (states, arith, True), *params, head.weight, head.bias)
-    return FcnBodyFn.apply(x, (states, arith, False), *params)
+        return FcnBodyFn.apply(x, (states, arith, True, bool(input_grad)), *params, head.weight, head.bias)
+    return FcnBodyFn.apply(x, (states, arith, False, bool(input_grad)), *params)

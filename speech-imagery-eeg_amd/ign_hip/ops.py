@@ -814,6 +814,8 @@ def _conv_wgrad_route(k, Ci):
 _CLCONV_FWD = {GEMM_F32: "ign_clconv_fwd", GEMM_X6: "ign_clconv_fwd_x6", GEMM_BF16: "ign_clconv_fwd_bf16", GEMM_H3: "ign_clconv_fwd_h3"}
 _CLCONV_DGRAD = {GEMM_F32: "ign_clconv_dgrad", GEMM_X6: "ign_clconv_dgrad_x6", GEMM_BF16: "ign_clconv_dgrad_bf16",
                  GEMM_H3: "ign_clconv_dgrad_h3"}
+_CLCONV_DGRAD_INPUT = {GEMM_F32: "ign_clconv_dgrad_input", GEMM_X6: "ign_clconv_dgrad_input_x6", GEMM_BF16: "ign_clconv_dgrad_input_bf16",
+                       GEMM_H3: "ign_clconv_dgrad_input_h3"}
 _CLCONV_WGRAD = {GEMM_F32: "ign_clconv_wgrad", GEMM_X6: "ign_clconv_wgrad_x6", GEMM_BF16: "ign_clconv_wgrad_bf16",
                  GEMM_H3: "ign_clconv_wgrad_h3"}
 _LINEAR_WGRAD = {GEMM_X6: "ign_linear_wgrad_x6", GEMM_BF16: "ign_linear_wgrad_bf16", GEMM_H3: "ign_linear_wgrad_h3"}
@@ -835,6 +837,12 @@ def _clconv_dgrad(arith, dyp, wd, y_in, a_in, b_in, mean_in, invstd_in, g_in, pa
     name, tail = _CLCONV_DGRAD[arith], ((b_dy, b_w) if arith == GEMM_H3 else ())
     _lib.check(getattr(_lib.lib(), name)(_ptr(dyp), _ptr(wd), _ptr(y_in), _ptr(a_in), _ptr(b_in), _ptr(mean_in), _ptr(invstd_in),
                                          _ptr(g_in), _ptr(part), *tail, *dims, _stream()), name)
+
+
+def _clconv_dgrad_input(arith, dyp, wd, gx, dims, b_dy=None, b_w=None):
+    """The FCN body's data gradient into the raw input series (no block below: plain epilogue), gx (B, Tin, Ci) for any Ci."""
+    name, tail = _CLCONV_DGRAD_INPUT[arith], ((b_dy, b_w) if arith == GEMM_H3 else ())
+    _lib.check(getattr(_lib.lib(), name)(_ptr(dyp), _ptr(wd), _ptr(gx), *tail, *dims, _stream()), name)
 
 
 def _wgrad_workspace(arith, dims, device):

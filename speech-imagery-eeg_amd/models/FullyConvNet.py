@@ -15,6 +15,10 @@ from ign_hip import fcn, ops
 
 
 class FullyConvNetwork(nn.Module):
+    # Opt-in: with it an input that requires a gradient gets one (block 1's data-gradient GEMM into the raw series,
+    # ign_clconv_dgrad_input*; utils.saliency sets it for explain="gated" / "dnn").  Off, the backward refuses: inputs are data.
+    input_grad = False
+
     def __init__(self, configs):
         super().__init__()
         k1, k2, k3 = (3, 3, 2) if configs.seq_len <= 10 else (8, 5, 3)     # FullyConvNet.py:11-50
@@ -33,5 +37,5 @@ class FullyConvNetwork(nn.Module):
         x = x if x.dtype == torch.float32 else x.float()
         blocks = [(b[0], b[1]) for b in (self.block1, self.block2, self.block3)]
         if ops.head_fits(x.shape[0], self.fc.weight.shape[0]) and not torch.is_autocast_enabled():
-            return fcn.fcn_body(x, blocks, head=self.fc)            # class head inside the pooling launch
-        return ops.head_linear(fcn.fcn_body(x, blocks), self.fc.weight, self.fc.bias)
+            return fcn.fcn_body(x, blocks, head=self.fc, input_grad=self.input_grad)      # class head inside the pooling launch
+        return ops.head_linear(fcn.fcn_body(x, blocks, input_grad=self.input_grad), self.fc.weight, self.fc.bias)
