@@ -1,6 +1,7 @@
 """Autograd ops over the C ABI (include/ign_abi.h).  torch supplies device memory, streams and autograd
 plumbing; the arithmetic is in libign_hip.so.  Every op raises on CPU tensors: there is no fallback path."""
 import ctypes
+from collections import namedtuple
 
 import torch
 
@@ -141,87 +142,111 @@ def _pv(ts):
     return (ctypes.c_void_p * len(ts))(*[(t.data_ptr() if t is not None else None) for t in ts])
 
 
-def _bank_forward(xn, ws, thrs, eps, mode, strides, need_grad):
-    """Forward of every length group of a bank: -> (P, D, saved) with P / D (B, sum_g K_g*C) in the reference's feature order
-    g*K*C + k*C + c (IGN/model/Shapelet.py:84,195-196) and saved[g] = (tstar, zmu, dsave, col0, stride, xstat)."""
-    B, C, T = xn.shape
-    ld = sum(w.shape[0] * C for w in ws)
-    P = torch.empty(B, ld, device=xn.device, dtype=torch.float32)
+BANK_MAX_GROUPS = 8           # SHP_MAX_GROUPS (csrc/ign_common.h): most groups one ign_shapelet_*_bank call takes
+
+# one length group of a bank: parameters, window geometry, first column in P / D, and what the forward saves for the backward
+_Group = namedtuple("_Group", "w thr K L stride Tw col0 tstar zmu dsave xstat")
+
+
+class _Bank:
+    """Host record of one bank forward, built once and kept on the autograd node: the groups, the shape (B, C, T), ld = sum_g K_g*C
+    (the row length of P / D, feature order g*K*C + k*C + c as IGN/model/Shapelet.py:84,195-196), eps, mode, and the host tables the
+    ign_shapelet_*_bank entry points read -- shared by the three launchers below."""
+
+    def __init__(self, xn, ws, thrs, eps, mode, strides, need_grad):
+        B, C, T = xn.shape
+        self.B, self.C, self.T, self.eps, self.mode, self.need_grad = B, C, T, float(eps), int(mode), need_grad
+        f32 = dict(device=xn.device, dtype=torch.float32)
+        want_xstat = need_grad and (mode & 0xf) >= DIST_COS
+        self.groups, col0 = [], 0
+        for g, (w, thr) in enumerate(zip(ws, thrs)):
+            K, Cw, Lg = w.shape
+            if Cw != C:
+                raise _lib.IgnError(f"shapelet group {g}: weights have {Cw} channels, input has {C}")
+            stride = int(strides[g])
+            Tw = (T - Lg) // stride + 1
+            self.groups.append(_Group(
+                w=w, thr=thr, K=K, L=Lg, stride=stride, Tw=Tw, col0=col0,
+                tstar=torch.empty(B, K, C, device=xn.device, dtype=torch.int32), zmu=torch.empty(B, K, C, 2, **f32),
+                dsave=torch.empty(B, C, K, Tw, **f32) if need_grad else None, xstat=torch.empty(B, C, Tw, **f32) if want_xstat else None))
+            col0 += K * C
+        self.G, self.ld, self.n_thr = len(self.groups), col0, (len(self.groups) if mode & GATE_LTS else 0)
+        self.one_call = self.G <= BANK_MAX_GROUPS     # the *_bank entry points take the whole bank; else: group by group
+        cols = {f: [getattr(s, f) for s in self.groups] for f in _Group._fields}
+        self.Ks, self.Ls, self.Ss, self.col0s = ((ctypes.c_int * self.G)(*cols[f]) for f in ("K", "L", "stride", "col0"))
+        self.ws, self.thrs, self.tstars, self.zmus, self.dsaves, self.xstats = (
+            _pv(cols[f]) for f in ("w", "thr", "tstar", "zmu", "dsave", "xstat"))
+
+    def cat_tstar(self):
+        ts = [s.tstar.reshape(self.B, -1) for s in self.groups]
+        return torch.cat(ts, dim=1) if len(ts) > 1 else ts[0]
+
+
+def _bank_fwd(bank, xn):
+    """Forward of every length group: -> (P, D), both (B, ld); the arg-max windows, statistics and distances land in `bank`."""
+    P = torch.empty(bank.B, bank.ld, device=xn.device, dtype=torch.float32)
     D = torch.empty_like(P)
     L = _lib.lib()
-    saved, col0 = [], 0
-    for g, w in enumerate(ws):
-        K, Cw, Lg = w.shape
-        if Cw != C:
-            raise _lib.IgnError(f"shapelet group {g}: weights have {Cw} channels, input has {C}")
-        stride = int(strides[g])
-        Tw = (T - Lg) // stride + 1
-        tstar = torch.empty(B, K, C, device=xn.device, dtype=torch.int32)
-        zmu = torch.empty(B, K, C, 2, device=xn.device, dtype=torch.float32)
-        dsave = torch.empty(B, C, K, Tw, device=xn.device, dtype=torch.float32) if need_grad else None
-        xstat = torch.empty(B, C, Tw, device=xn.device, dtype=torch.float32) \
-            if (need_grad and (mode & 0xf) >= DIST_COS) else None
-        saved.append((tstar, zmu, dsave, col0, stride, xstat))
-        col0 += K * C
-    G = len(ws)
-    if G <= 8:
-        # the whole bank in one call (ign_shapelet_fwd_bank validates every group, then launches group by group)
-        _, ia = _tables(G)
+    if bank.one_call:          # (ign_shapelet_fwd_bank validates every group, then launches group by group)
         _lib.check(L.ign_shapelet_fwd_bank(
-            _ptr(xn), G, _pv(ws), _pv(thrs), _ptr(P), _ptr(D), ld, ia(*[sv[3] for sv in saved]), _pv([sv[0] for sv in saved]),
-            _pv([sv[1] for sv in saved]), _pv([sv[2] for sv in saved]), _pv([sv[5] for sv in saved]), B, C, T,
-            ia(*[w.shape[0] for w in ws]), ia(*[w.shape[2] for w in ws]), ia(*[sv[4] for sv in saved]), float(eps), int(mode),
-            _stream()), "ign_shapelet_fwd_bank")
+            _ptr(xn), bank.G, bank.ws, bank.thrs, _ptr(P), _ptr(D), bank.ld, bank.col0s, bank.tstars, bank.zmus, bank.dsaves, bank.xstats,
+            bank.B, bank.C, bank.T, bank.Ks, bank.Ls, bank.Ss, bank.eps, bank.mode, _stream()), "ign_shapelet_fwd_bank")
     else:
-        for g, w in enumerate(ws):
-            tstar, zmu, dsave, c0, stride, xstat = saved[g]
-            _lib.check(L.ign_shapelet_fwd(_ptr(xn), _ptr(w), _ptr(thrs[g]), _ptr(P), _ptr(D), ld, c0, _ptr(tstar), _ptr(zmu),
-                                          _ptr(dsave), _ptr(xstat), B, C, T, w.shape[0], w.shape[2], stride, float(eps), int(mode),
-                                          _stream()), "ign_shapelet_fwd")
-    return P, D, saved
+        for s in bank.groups:
+            _lib.check(L.ign_shapelet_fwd(
+                _ptr(xn), _ptr(s.w), _ptr(s.thr), _ptr(P), _ptr(D), bank.ld, s.col0, _ptr(s.tstar), _ptr(s.zmu), _ptr(s.dsave),
+                _ptr(s.xstat), bank.B, bank.C, bank.T, s.K, s.L, s.stride, bank.eps, bank.mode, _stream()), "ign_shapelet_fwd")
+    return P, D
 
 
-def _cat_tstar(saved, B):
-    return torch.cat([sv[0].reshape(B, -1) for sv in saved], dim=1) if len(saved) > 1 else saved[0][0].reshape(B, -1)
-
-
-def _bank_backward(xn, ws, gP, P, D, saved, eps, mode, gw_add=None, add_scale=None):
+def _bank_wgrad(bank, xn, gP, P, D, gw_add=None, add_scale=None):
     """dloss/dw of every group (list of (K,C,L) tensors) from gP = dloss/dP (B, ld).  `gw_add[g]` / `add_scale` (a one-element
     device tensor): a batch-independent gradient of the same shapelets that the reduction launch adds as add_scale * gw_add[g]
-    (the diversity regulariser) -- a parameter with two gradient sources then needs no accumulate kernel."""
-    B, C, T = xn.shape
-    ld = P.shape[1]
+    (the diversity regulariser) -- a parameter with two gradient sources then needs no accumulate kernel (group by group: torch)."""
+    B, C, T, mode = bank.B, bank.C, bank.T, bank.mode
     L = _lib.lib()
-    G = len(ws)
     cos = (mode & 0xf) >= DIST_COS
-    wnorms = [w.square().sum(dim=-1).sqrt().contiguous() if cos else None for w in ws]
-    gws = [torch.empty_like(w) for w in ws]
-    if G <= 8:
-        _, ia = _tables(G)
-        Ks, Ls, Ss = ia(*[w.shape[0] for w in ws]), ia(*[w.shape[2] for w in ws]), ia(*[sv[4] for sv in saved])
-        nbytes = L.ign_shapelet_bwd_bank_workspace_bytes(G, B, C, T, Ks, Ls, Ss, mode)
+    wnorms = [s.w.square().sum(dim=-1).sqrt().contiguous() if cos else None for s in bank.groups]
+    gws = [torch.empty_like(s.w) for s in bank.groups]
+    if bank.one_call:
+        Ks, Ls, Ss = bank.Ks, bank.Ls, bank.Ss
+        nbytes = L.ign_shapelet_bwd_bank_workspace_bytes(bank.G, B, C, T, Ks, Ls, Ss, mode)
         if nbytes == 0:
             raise _lib.IgnError(f"shapelet backward: no launch plan for K={list(Ks)} L={list(Ls)} stride={list(Ss)}")
         work = torch.empty(nbytes // 4, device=xn.device, dtype=torch.float32)
         _lib.check(L.ign_shapelet_bwd_bank(
-            _ptr(xn), G, _pv(ws), _ptr(gP), _ptr(P), _ptr(D), ld, ia(*[sv[3] for sv in saved]), _pv([sv[0] for sv in saved]),
-            _pv([sv[1] for sv in saved]), _pv([sv[2] for sv in saved]), _pv([sv[5] for sv in saved]), _pv(wnorms), _pv(gws),
-            _pv(gw_add) if gw_add is not None else None, _ptr(add_scale), _ptr(work), B, C, T, Ks, Ls, Ss, float(eps), int(mode),
-            _stream()), "ign_shapelet_bwd_bank")
+            _ptr(xn), bank.G, bank.ws, _ptr(gP), _ptr(P), _ptr(D), bank.ld, bank.col0s, bank.tstars, bank.zmus, bank.dsaves, bank.xstats,
+            _pv(wnorms), _pv(gws), _pv(gw_add) if gw_add is not None else None, _ptr(add_scale), _ptr(work), B, C, T, Ks, Ls, Ss,
+            bank.eps, mode, _stream()), "ign_shapelet_bwd_bank")
         return gws
-    for g, w in enumerate(ws):
-        K, _, Lg = w.shape
-        tstar, zmu, dsave, col0, stride, xstat = saved[g]
-        nbytes = L.ign_shapelet_bwd_workspace_bytes(B, C, T, K, Lg, stride, mode)
+    for g, s in enumerate(bank.groups):
+        nbytes = L.ign_shapelet_bwd_workspace_bytes(B, C, T, s.K, s.L, s.stride, mode)
         if nbytes == 0:
-            raise _lib.IgnError(f"shapelet backward: no launch plan for K={K} L={Lg} stride={stride}")
+            raise _lib.IgnError(f"shapelet backward: no launch plan for K={s.K} L={s.L} stride={s.stride}")
         work = torch.empty(nbytes // 4, device=xn.device, dtype=torch.float32)
-        _lib.check(L.ign_shapelet_bwd(_ptr(xn), _ptr(w), _ptr(gP), _ptr(P), _ptr(D), ld, col0,
-                                      _ptr(tstar), _ptr(zmu), _ptr(dsave), _ptr(xstat), _ptr(wnorms[g]), _ptr(gws[g]), _ptr(work),
-                                      B, C, T, K, Lg, stride, eps, mode, _stream()), "ign_shapelet_bwd")
+        _lib.check(L.ign_shapelet_bwd(
+            _ptr(xn), _ptr(s.w), _ptr(gP), _ptr(P), _ptr(D), bank.ld, s.col0, _ptr(s.tstar), _ptr(s.zmu), _ptr(s.dsave), _ptr(s.xstat),
+            _ptr(wnorms[g]), _ptr(gws[g]), _ptr(work), B, C, T, s.K, s.L, s.stride, bank.eps, mode, _stream()), "ign_shapelet_bwd")
         if gw_add is not None and gw_add[g] is not None:
             gws[g] = gws[g] + (gw_add[g] if add_scale is None else gw_add[g] * add_scale)
     return gws
+
+
+def _bank_xgrad(bank, xn, gP, P, D):
+    """dloss/dxn (B,C,T) of every group from gP = dloss/dP (B, ld): the groups run one after another on the stream, the first
+    overwriting the result and the others adding to it (no atomics: bitwise repeatable)."""
+    L = _lib.lib()
+    gxn = torch.empty_like(xn)
+    if bank.one_call:
+        _lib.check(L.ign_shapelet_bwd_input_bank(
+            _ptr(xn), bank.G, bank.ws, _ptr(gP), _ptr(P), _ptr(D), bank.ld, bank.col0s, bank.tstars, bank.zmus, bank.dsaves, _ptr(gxn),
+            bank.B, bank.C, bank.T, bank.Ks, bank.Ls, bank.Ss, bank.eps, bank.mode, _stream()), "ign_shapelet_bwd_input_bank")
+    else:
+        for g, s in enumerate(bank.groups):
+            _lib.check(L.ign_shapelet_bwd_input(
+                _ptr(xn), _ptr(s.w), _ptr(gP), _ptr(P), _ptr(D), bank.ld, s.col0, _ptr(s.tstar), _ptr(s.zmu), _ptr(s.dsave), _ptr(gxn),
+                1 if g else 0, bank.B, bank.C, bank.T, s.K, s.L, s.stride, bank.eps, bank.mode, _stream()), "ign_shapelet_bwd_input")
+    return gxn
 
 
 def _input_grad_supported(name, mode):
@@ -231,34 +256,37 @@ def _input_grad_supported(name, mode):
                             f"L1 ('euclidean') and MSE (memory_efficient) distances only, not for cosine / pearson (mode 0x{mode:x})")
 
 
-def _bank_backward_input(xn, ws, gP, P, D, saved, eps, mode):
-    """dloss/dxn (B,C,T) of every group from gP = dloss/dP (B, ld): the groups run one after another on the stream, the first
-    overwriting the result and the others adding to it (no atomics: bitwise repeatable)."""
-    B, C, T = xn.shape
-    ld = P.shape[1]
-    L = _lib.lib()
-    G = len(ws)
-    gxn = torch.empty_like(xn)
-    if G <= 8:
-        _, ia = _tables(G)
-        _lib.check(L.ign_shapelet_bwd_input_bank(
-            _ptr(xn), G, _pv(ws), _ptr(gP), _ptr(P), _ptr(D), ld, ia(*[sv[3] for sv in saved]), _pv([sv[0] for sv in saved]),
-            _pv([sv[1] for sv in saved]), _pv([sv[2] for sv in saved]), _ptr(gxn), B, C, T, ia(*[w.shape[0] for w in ws]),
-            ia(*[w.shape[2] for w in ws]), ia(*[sv[4] for sv in saved]), float(eps), int(mode), _stream()),
-            "ign_shapelet_bwd_input_bank")
-        return gxn
-    for g, w in enumerate(ws):
-        tstar, zmu, dsave, col0, stride, _ = saved[g]
-        _lib.check(L.ign_shapelet_bwd_input(_ptr(xn), _ptr(w), _ptr(gP), _ptr(P), _ptr(D), ld, col0, _ptr(tstar), _ptr(zmu),
-                                            _ptr(dsave), _ptr(gxn), 1 if g else 0, B, C, T, w.shape[0], w.shape[2], stride,
-                                            float(eps), int(mode), _stream()), "ign_shapelet_bwd_input")
-    return gxn
-
-
-def _threshold_grads(gP, P, ws, saved, C):
+def _threshold_grads(bank, gP, P):
     """LTS: dP/dthr = sigma'(thr - m) = P(1-P), summed over the batch  (IGN/model/Shapelet.py:109)"""
     gt = (gP * P * (1 - P)).sum(0)
-    return [gt[sv[3]:sv[3] + w.shape[0] * C].view(1, w.shape[0], C) for w, sv in zip(ws, saved)]
+    return [gt[s.col0:s.col0 + s.K * bank.C].view(1, s.K, bank.C) for s in bank.groups]
+
+
+def _node_forward(xn, others, params, G, eps, mode, strides, need_x, need_rest, gpu_name, grad_name):
+    """What the forwards of ShapeletBankFn and SbmFn share: unpack w_0..w_{G-1}[, thr_0..thr_{G-1}], refuse what the kernels do not
+    take (`gpu_name` / `grad_name`: the node in a device / dtype error / in the input-gradient refusal; `others`: its further tensor inputs), build
+    the record and run the forward -> (xn, bank, P, D).  The distances are kept when the input alone needs a gradient."""
+    ws = [w.contiguous() for w in params[:G]]
+    thrs = [t.contiguous() for t in params[G:]] if (mode & GATE_LTS) else [None] * G
+    _need_gpu(gpu_name, xn, *others, *ws, *[t for t in thrs if t is not None])
+    xn = xn.contiguous()
+    if need_x:
+        _input_grad_supported(grad_name, mode)
+    bank = _Bank(xn, ws, thrs, eps, mode, strides, need_x or need_rest)
+    return (xn, bank, *_bank_fwd(bank, xn))
+
+
+def _node_backward(bank, xn, gP, P, D, need_x, need_params, gw_add=None, add_scale=None):
+    """What the backwards share, from gP = dloss/dP (None: nothing reached P): -> (gxn, grads_w, grads_t), the lists with one entry
+    per group / per threshold (none without LTS).  Only the input needing a gradient means no weight / threshold work."""
+    none = [None] * bank.G, [None] * bank.n_thr
+    if gP is None:
+        return (None, *none)
+    gP = gP.contiguous()
+    gxn = _bank_xgrad(bank, xn, gP, P, D) if need_x else None
+    if need_x and not need_params:
+        return (gxn, *none)
+    return gxn, _bank_wgrad(bank, xn, gP, P, D, gw_add, add_scale), (_threshold_grads(bank, gP, P) if bank.n_thr else [])
 
 
 class ShapeletBankFn(torch.autograd.Function):
@@ -270,41 +298,26 @@ class ShapeletBankFn(torch.autograd.Function):
     Tstar (int32) is the WINDOW INDEX of the best match -- arg-max_t p for the RBF gate, arg-min_t d for LTS, first index on
     ties; the match covers samples [Tstar*stride, Tstar*stride + L) -- which is what the reference's shapelet plots need
     (IGN/utils/shapelet_util.py:153 recomputes it on the host by sliding every shapelet over every series).
+    The node keeps the bank record (`ctx.bank`, a _Bank); xn, P, Dmin and the parameters go through save_for_backward.
     """
 
     @staticmethod
     def forward(ctx, xn, eps, mode, strides, n_groups, *params):
-        ws = [w.contiguous() for w in params[:n_groups]]
-        thrs = [t.contiguous() for t in params[n_groups:]] if (mode & GATE_LTS) else [None] * n_groups
-        _need_gpu("shapelet_fwd", xn, *ws, *[t for t in thrs if t is not None])
-        xn = xn.contiguous()
-        if ctx.needs_input_grad[0]:
-            _input_grad_supported("shapelet_bank", mode)
-        # grad mode is off inside forward(); ask the node instead.  The distances are kept when the input alone needs a gradient.
-        need_grad = any(ctx.needs_input_grad[5:]) or ctx.needs_input_grad[0]
-        P, D, saved = _bank_forward(xn, ws, thrs, eps, mode, strides, need_grad)
-        Tstar = _cat_tstar(saved, xn.shape[0])
+        xn, bank, P, D = _node_forward(xn, (), params, n_groups, eps, mode, strides, ctx.needs_input_grad[0],
+                                       any(ctx.needs_input_grad[5:]), gpu_name="shapelet_fwd", grad_name="shapelet_bank")
+        Tstar = bank.cat_tstar()
         ctx.mark_non_differentiable(D, Tstar)
         ctx.set_materialize_grads(False)              # (else autograd fills a zero tensor per unused output, one launch each)
-        ctx.meta = (float(eps), int(mode), n_groups, saved, need_grad)
-        ctx.save_for_backward(xn, P, D, *ws, *[t for t in thrs if t is not None])
+        ctx.bank = bank
+        ctx.save_for_backward(xn, P, D, *(s.w for s in bank.groups), *(s.thr for s in bank.groups if s.thr is not None))
         return P, D, Tstar
 
     @staticmethod
     def backward(ctx, gP, gD, gT):
-        eps, mode, G, saved, had_grad = ctx.meta
-        if not had_grad:
+        if not ctx.bank.need_grad:
             raise _lib.IgnError("shapelet backward called but the forward ran without saving distances")
         xn, P, D = ctx.saved_tensors[:3]
-        ws = ctx.saved_tensors[3:3 + G]
-        if gP is None:
-            return (None,) * (5 + G + (G if mode & GATE_LTS else 0))
-        gP = gP.contiguous()
-        gxn = _bank_backward_input(xn, ws, gP, P, D, saved, eps, mode) if ctx.needs_input_grad[0] else None
-        if not any(ctx.needs_input_grad[5:]):         # only the input needs a gradient: no weight / threshold work
-            return (gxn,) + (None,) * (4 + G + (G if mode & GATE_LTS else 0))
-        grads_w = _bank_backward(xn, ws, gP, P, D, saved, eps, mode)
-        grads_t = _threshold_grads(gP, P, ws, saved, xn.shape[1]) if mode & GATE_LTS else []
+        gxn, grads_w, grads_t = _node_backward(ctx.bank, xn, gP, P, D, ctx.needs_input_grad[0], any(ctx.needs_input_grad[5:]))
         return (gxn, None, None, None, None, *grads_w, *grads_t)
 
 
@@ -338,48 +351,40 @@ class SbmFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xn, cfg, W, *params):
         eps, mode, strides, G, lam_reg, lam_div, fuse_head, want_tstar, reg_ws = cfg
-        ws = [w.contiguous() for w in params[:G]]
-        thrs = [t.contiguous() for t in params[G:]] if (mode & GATE_LTS) else [None] * G
-        _need_gpu("sbm", xn, W, *ws, *[t for t in thrs if t is not None])
-        xn, W = xn.contiguous(), W.contiguous()
-        B, C, T = xn.shape
-        if ctx.needs_input_grad[0]:
-            _input_grad_supported("sbm", mode)
-        need_grad = any(ctx.needs_input_grad[2:]) or ctx.needs_input_grad[0]
+        xn, bank, P, D = _node_forward(xn, (W,), params, G, eps, mode, strides, ctx.needs_input_grad[0],
+                                       any(ctx.needs_input_grad[2:]), gpu_name="sbm", grad_name="sbm")
+        W = W.contiguous()
+        ws = [s.w for s in bank.groups]
         L = _lib.lib()
-        P, D, saved = _bank_forward(xn, ws, thrs, eps, mode, strides, need_grad)
-        Tstar = _cat_tstar(saved, B) if want_tstar else None
+        Tstar = bank.cat_tstar() if want_tstar else None
         # regularisers: value + gradients, one launch
         use_div = lam_div > 0.0
         gWreg = torch.empty_like(W)
         gdiv = [torch.empty_like(w) for w in ws] if use_div else None
         reg = torch.empty(1, device=xn.device, dtype=torch.float32)
         Gd = G if use_div else 0
-        _, ia = _tables(max(G, 1))
-        _lib.check(L.ign_sbm_reg_fwd_bwd(_ptr(W), _ptr(gWreg), W.numel(), float(lam_reg), Gd, _pv(ws), _pv(gdiv) if use_div else None,
-                                         ia(*[w.shape[0] for w in ws]), ia(*[w.shape[2] for w in ws]), C, float(lam_div), 1e-6,
-                                         _ptr(reg), _ptr(reg_ws), _stream()), "ign_sbm_reg_fwd_bwd")
+        _lib.check(L.ign_sbm_reg_fwd_bwd(_ptr(W), _ptr(gWreg), W.numel(), float(lam_reg), Gd, bank.ws, _pv(gdiv) if use_div else None,
+                                         bank.Ks, bank.Ls, bank.C, float(lam_div), 1e-6, _ptr(reg), _ptr(reg_ws), _stream()),
+                   "ign_sbm_reg_fwd_bwd")
         out = None
         if fuse_head:
             N, F_ = W.shape
             _check_classes("sbm head", N)
-            out = torch.empty(B, N, device=xn.device, dtype=torch.float32)
-            _lib.check(L.ign_head_fwd(_ptr(P), _ptr(W), None, _ptr(out), B, F_, N, P.stride(0), _stream()), "ign_head_fwd")
+            out = torch.empty(bank.B, N, device=xn.device, dtype=torch.float32)
+            _lib.check(L.ign_head_fwd(_ptr(P), _ptr(W), None, _ptr(out), bank.B, F_, N, P.stride(0), _stream()), "ign_head_fwd")
         ctx.set_materialize_grads(False)
         nd = [D] + ([Tstar] if Tstar is not None else [])
         ctx.mark_non_differentiable(*nd)
-        ctx.meta = (float(eps), int(mode), G, saved, need_grad, fuse_head, gdiv)
+        ctx.bank, ctx.fuse_head, ctx.gdiv = bank, fuse_head, gdiv
         ctx.save_for_backward(xn, P, D, W, gWreg, *ws)
         return P, D, Tstar, reg, out
 
     @staticmethod
     def backward(ctx, gP, gD, gT, greg, gout):
-        eps, mode, G, saved, had_grad, fuse_head, gdiv = ctx.meta
-        if not had_grad:
+        bank, fuse_head, gdiv = ctx.bank, ctx.fuse_head, ctx.gdiv
+        if not bank.need_grad:
             raise _lib.IgnError("shapelet backward called but the forward ran without saving distances")
         xn, P, D, W, gWreg = ctx.saved_tensors[:5]
-        ws = ctx.saved_tensors[5:5 + G]
-        B, C, T = xn.shape
         L = _lib.lib()
         greg = greg.contiguous().reshape(1) if greg is not None else None
         need_x, need_W, need_p = ctx.needs_input_grad[0], ctx.needs_input_grad[2], any(ctx.needs_input_grad[3:])
@@ -390,23 +395,16 @@ class SbmFn(torch.autograd.Function):
             gPh = torch.empty_like(P)
             gW = torch.empty_like(W) if (need_W or not need_x) else None       # (frozen head under an input gradient: gX only)
             _lib.check(L.ign_head_bwd_acc(_ptr(gout), _ptr(P), _ptr(W), _ptr(gPh), _ptr(gW), None,
-                                          _ptr(gWreg) if (greg is not None and gW is not None) else None, _ptr(greg), B, F_, N,
+                                          _ptr(gWreg) if (greg is not None and gW is not None) else None, _ptr(greg), bank.B, F_, N,
                                           P.stride(0), _stream()),
                        "ign_head_bwd_acc")
             gP = gPh if gP is None else gPh + gP
-        elif greg is not None and ctx.needs_input_grad[2]:
+        elif greg is not None and need_W:
             gW = gWreg * greg
-        if gP is None:             # nothing reached the gate outputs: only the regulariser moves the shapelets
-            grads_w = [(gd * greg if (gdiv is not None and greg is not None) else None) for gd in (gdiv or [None] * G)]
-            grads_t = [None] * G if mode & GATE_LTS else []
-            return (None, None, gW, *grads_w, *grads_t)
-        gP = gP.contiguous()
-        gxn = _bank_backward_input(xn, ws, gP, P, D, saved, eps, mode) if need_x else None
-        if need_x and not need_p:          # only the input (and perhaps the head) needs a gradient: no weight / threshold work
-            return (gxn, None, gW) + (None,) * (G + (G if mode & GATE_LTS else 0))
         add = gdiv if (gdiv is not None and greg is not None) else None
-        grads_w = _bank_backward(xn, ws, gP, P, D, saved, eps, mode, gw_add=add, add_scale=greg if add is not None else None)
-        grads_t = _threshold_grads(gP, P, ws, saved, C) if mode & GATE_LTS else []
+        gxn, grads_w, grads_t = _node_backward(bank, xn, gP, P, D, need_x, need_p, add, greg if add is not None else None)
+        if gP is None and add is not None:             # nothing reached the gate outputs: only the regulariser moves the shapelets
+            grads_w = [gd * greg for gd in add]
         return (gxn, None, gW, *grads_w, *grads_t)
 
 

@@ -163,11 +163,11 @@ class ShapeBottleneckModel(nn.Module):
     def _fused_forward(self, x, xn):
         """Bank + linear head + both regularisers as ONE autograd node (ops.SbmFn): 1 instance-norm launch, G shapelet launches,
         1 regulariser launch, 1 head launch -- and a backward without a single torch kernel.  Returns None when the
-        configuration is outside that node (pearson centring runs through autograd; > 8 groups; > 16 shapelets per group)."""
+        configuration is outside that node (pearson centring runs through autograd; > ops.BANK_MAX_GROUPS groups; > 16 shapelets per group)."""
         first = self.shapelets[0]
         mode = first.mode()
         G = len(self.shapelets)
-        if (mode & 0xf) == ops.DIST_PEARSON or G > 8 or max(s.n for s in self.shapelets) > 16 or not x.is_cuda \
+        if (mode & 0xf) == ops.DIST_PEARSON or G > ops.BANK_MAX_GROUPS or max(s.n for s in self.shapelets) > 16 or not x.is_cuda \
                 or x.dtype != torch.float32:
             return None
         if xn is None:

@@ -44,11 +44,12 @@ def step_bank(mode):
     xn, _ = ops.instance_norm(torch.randn(B, T, C, device=dev))
     ws = [torch.randn(K, C, L, device=dev) for L in Ls]
     thrs = [torch.rand(1, K, C, device=dev) for _ in Ls] if mode & ops.GATE_LTS else [None] * len(Ls)
-    P, D, saved = ops._bank_forward(xn, ws, thrs, 1.0, mode, [1] * len(Ls), True)
+    bank = ops._Bank(xn, ws, thrs, 1.0, mode, [1] * len(Ls), True)
+    P, D = ops._bank_fwd(bank, xn)
     gP = torch.randn_like(P)
     E = sum(B * C * K * (T - L + 1) * L for L in Ls)
-    w = _median_ms(lambda: ops._bank_backward(xn, ws, gP, P, D, saved, 1.0, mode))
-    x = _median_ms(lambda: ops._bank_backward_input(xn, ws, gP, P, D, saved, 1.0, mode))
+    w = _median_ms(lambda: ops._bank_wgrad(bank, xn, gP, P, D))
+    x = _median_ms(lambda: ops._bank_xgrad(bank, xn, gP, P, D))
     return dict(element_ops=E, weight_pass=w, input_pass=x, input_over_weight=x["median_ms"] / w["median_ms"],
                 input_pass_Telem_per_s=E / x["median_ms"] / 1e9, weight_pass_Telem_per_s=E / w["median_ms"] / 1e9)
 

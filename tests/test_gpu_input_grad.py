@@ -289,6 +289,32 @@ def test_input_grad_is_bitwise_repeatable_and_bank_equals_groups():
     assert torch.equal(acc, runs[0])
 
 
+def test_nine_group_bank_input_grad_equals_the_sum_of_the_groups():
+    """More groups than one ign_shapelet_bwd_input_bank call takes (ops.BANK_MAX_GROUPS = 8): the per-group entry point runs nine
+    times, the first overwriting and the others adding in place, in group order.  K = 5, L = 5, 8, ..., 29, the fifth group at
+    stride 2.  Compared as the multi-group case above compares its bank of three: torch.equal with the group gradients added in
+    the same order (every sample is one fp32 add per group on either side)."""
+    dev = _dev()
+    import speech_imagery_eeg_amd  # noqa
+    from ign_hip import ops
+    Ls = tuple(range(5, 30, 3))
+    strides = tuple(2 if i == 4 else 1 for i in range(len(Ls)))
+    assert len(Ls) == 9
+    xn, ws, thrs, r = _case_tensors(99, 2, 4, 64, (5,) * len(Ls), Ls)
+    _, gx, _, _ = _hip_bank(dev, xn, ws, thrs, 0.9, L1, RBF, strides, r)
+    x = xn.to(dev).requires_grad_(True)
+    rd = r.to(dev)
+    col, acc = 0, None
+    for w, stride in zip(ws, strides):
+        n = w.shape[0] * w.shape[1]
+        p, _ = ops.shapelet_bank(x, [w.to(dev)], 0.9, L1 | RBF, [stride])
+        gi, = torch.autograd.grad((p * rd[:, col:col + n]).sum(), x)
+        acc = gi if acc is None else acc + gi
+        col += n
+    assert gx.shape == xn.shape and float(gx.abs().max()) > 0.0
+    assert torch.equal(acc, gx)
+
+
 @pytest.mark.parametrize("cls_name", ["ShapeBottleneckModel", "DistThresholdSBM"])
 def test_parameter_grads_do_not_depend_on_x_requires_grad(cls_name):
     dev = _dev()

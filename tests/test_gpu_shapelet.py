@@ -366,6 +366,36 @@ def test_bank_call_is_bitwise_the_per_group_result(B, C, T, Ks, Ls):
         col += n
 
 
+@pytest.mark.parametrize("gate", [0x00, 0x10], ids=["l1-rbf", "l1-lts"])
+def test_nine_group_bank_is_bitwise_the_per_group_result(gate):
+    """More groups than one ign_shapelet_*_bank call takes (ops.BANK_MAX_GROUPS = 8): the bank then goes through the per-group
+    entry points, and must still reproduce nine single-group banks bit for bit -- outputs, arg-max windows, weight gradients and,
+    with LTS, threshold gradients.  K = 5, L = 5, 8, ..., 29, the fifth group at stride 2."""
+    dev = _dev()
+    import speech_imagery_eeg_amd  # noqa
+    from ign_hip import ops
+    B, C, T, K, Ls = 2, 4, 64, 5, tuple(range(5, 30, 3))
+    strides = [2 if i == 4 else 1 for i in range(len(Ls))]
+    assert len(Ls) == 9
+    g = torch.Generator().manual_seed(sum(Ls) + gate)
+    xn = torch.randn(B, C, T, generator=g).to(dev)
+    ws = [torch.randn(K, C, L, generator=g).to(dev).requires_grad_(True) for L in Ls]
+    thrs = [torch.rand(1, K, C, generator=g).to(dev).requires_grad_(True) for _ in Ls] if gate else None
+    r = torch.randn(B, len(Ls) * K * C, generator=g).to(dev)
+    p, d, t = ops.shapelet_bank(xn, ws, 0.9, gate, strides, thrs, return_tstar=True)
+    grads = torch.autograd.grad((p * r).sum(), ws + (thrs or []))
+    n = K * C
+    for i, w in enumerate(ws):
+        cols = slice(i * n, (i + 1) * n)
+        own = [w] + ([thrs[i]] if gate else [])
+        pi, di, ti = ops.shapelet_bank(xn, [w], 0.9, gate, [strides[i]], [thrs[i]] if gate else None, return_tstar=True)
+        gi = torch.autograd.grad((pi * r[:, cols]).sum(), own)
+        assert torch.equal(pi, p[:, cols]) and torch.equal(di, d[:, cols]) and torch.equal(ti, t[:, cols])
+        assert torch.equal(gi[0], grads[i])
+        if gate:
+            assert torch.equal(gi[1], grads[len(ws) + i])
+
+
 def test_full_size_properties():
     """B=256, C=122, T=1000 (BASELINE config 1): size-independent checks the oracle cannot reach in seconds."""
     dev = _dev()
