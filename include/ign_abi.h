@@ -40,6 +40,7 @@ extern "C" {
 #define IGN_DIST_PEARS 3   /* 1 - pearson     IGN/model/Shapelet.py:67-69,11-19                          */
 #define IGN_GATE_RBF   0x00 /* exp(-(eps d)^2) + straight-through max   IGN/model/Shapelet.py:77-84      */
 #define IGN_GATE_LTS   0x10 /* straight-through soft-min + sigmoid(thr - min_d)  Shapelet.py:105-111     */
+#define IGN_TIE_EXACT  0x20 /* opt-in: L1 backward passes use sign(0) = 0 at x == w, as aten::sgn (see below) */
 
 int         ign_abi_version(void);
 const char* ign_last_error(void);
@@ -110,6 +111,11 @@ int ign_shapelet_fwd_bank(const float* xn_bct, int G, const float* const* w_kcl,
  * fixtures tests/golden/shapelet_tie_{l1,lts}.npz: tests/test_gpu_shapelet.py::test_exact_ties_differ_from_sgn0_by_exactly_
  * the_documented_term asserts this identity (and nothing else) at 1e-4.  Other distances have no kink (MSE: the factor x - w
  * is 0 at a tie; cosine / pearson: smooth).
+ * IGN_TIE_EXACT (mode bit 0x20, opt-in) selects separate IGN_DIST_L1 instantiations that add A where x > w, subtract it where
+ * x < w and add nothing where x == w: such an element contributes 0 to gw_kcl, as aten::sgn does, so gw_kcl equals the
+ * reference on the tie fixtures too.  Same staging, same fixed-order reduction, same workspace size, bitwise repeatable;
+ * slower than the default (two compares per element).  The forward ignores the bit; with MSE / cosine / pearson it is accepted
+ * and changes nothing (same kernels, same bits).
  * stride > 1 (IGN/model/Shapelet.py:162: int(log2 L) once seq_len >= 3000 -- run_uea.sh's MotorImagery, EigenWorms) is
  * served by a generic-step kernel; shapelets longer than 2048 positions are split over several blocks.  Rows up to
  * T ~ 40 000 fit the forward's LDS staging (160 KB per CU); beyond that both calls return IGN_E_TOOBIG.             */
@@ -146,7 +152,9 @@ int ign_shapelet_bwd_bank(const float* xn_bct, int G, const float* const* w_kcl,
  * sign(0) convention (IGN_DIST_L1 only): as for gw_kcl above, an element with x[b,c,s] == w[k,c,j] (bit-equal floats) counts
  * as sign(x - w) = -1, where the reference's aten::sgn gives 0.  Hence, exactly,
  *     gxn_bct[b,c,s] = reference[b,c,s] - sum_{(k,t,j): t*stride + j = s, x[b,c,s] == w[k,c,j]} dloss/dd[b,t,k,c] / L,
- * so the tie terms of gw_kcl and gxn_bct stay negatives of each other, as every other term is.  MSE has no kink.             */
+ * so the tie terms of gw_kcl and gxn_bct stay negatives of each other, as every other term is.  MSE has no kink.
+ * With IGN_TIE_EXACT in `mode` an element with x[b,c,s] == w[k,c,j] contributes 0 to gxn_bct as well (a separate L1
+ * instantiation: compare both ways, add nothing at a tie), as aten::sgn does, so gxn_bct equals the reference.             */
 int ign_shapelet_bwd_input(const float* xn_bct, const float* w_kcl, const float* g_out, const float* p_out,
                            const float* dmin_out, int ld, int col0, const int32_t* tstar, const float* zmu,
                            const float* d_save, float* gxn_bct, int accumulate,

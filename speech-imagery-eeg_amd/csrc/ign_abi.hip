@@ -100,12 +100,15 @@ shp_fwd_launch_t ign_get_fwd_launcher(int dist, int TT, int KT) {
 static int split_mode(int mode, int* dist, int* gate, const char* who) {
     *dist = mode & 0xf;
     *gate = (mode & IGN_GATE_LTS) ? GATE_LTS : GATE_RBF;
-    if ((mode & ~0x1f) != 0 || *dist > IGN_DIST_PEARS) {
+    if ((mode & ~0x3f) != 0 || *dist > IGN_DIST_PEARS) {
         ign_set_error("%s: unknown mode 0x%x", who, mode);
         return IGN_E_ARG;
     }
     return 0;
 }
+
+// IGN_TIE_EXACT picks the sign(0) = 0 instantiations of the two L1 backward passes; every other distance ignores the bit.
+static bool tie_exact(int mode, int dist) { return (mode & IGN_TIE_EXACT) != 0 && dist == DIST_L1; }
 
 static int check_dims(const char* who, int B, int C, int T, int K, int L, int stride) {
     if (B <= 0 || C <= 0 || T <= 0 || K <= 0 || L <= 0 || stride <= 0 || L > T) {
@@ -354,7 +357,7 @@ static int plan_bwd(int B, int C, int T, int K, int L, int Tw, int stride, BwdPl
 }
 
 extern "C" size_t ign_shapelet_bwd_workspace_bytes(int B, int C, int T, int K, int L, int stride, int mode) {
-    (void)mode;
+    (void)mode;       // IGN_TIE_EXACT included: its kernels use the default's plan, LDS and partial buffer
     if (B <= 0 || C <= 0 || T <= 0 || K <= 0 || L <= 0 || stride < 1 || L > T) return 0;
     BwdPlan p;
     if (plan_bwd(B, C, T, K, L, (T - L) / stride + 1, stride, &p)) return 0;
@@ -389,7 +392,8 @@ static int launch_bwd_group(const char* who, const float* xn_bct, const float* w
         ign_set_error("%s: no launch plan for K=%d L=%d Tw=%d stride=%d", who, K, L, Tw, stride);
         return rc;
     }
-    shp_bwd_launch_t fn = (stride > 1) ? ign_get_bwd_strided_launcher(dist) : ign_get_bwd_launcher(dist, p.JJ);
+    shp_bwd_launch_t fn = (stride > 1) ? ign_get_bwd_strided_launcher(dist, tie_exact(mode, dist))
+                                       : ign_get_bwd_launcher(dist, p.JJ, tie_exact(mode, dist));
     if (!fn) {
         ign_set_error("%s: no kernel for JJ=%d dist=%d", who, p.JJ, dist);
         return IGN_E_UNSUP;
@@ -531,7 +535,7 @@ extern "C" int ign_shapelet_bwd_input(const float* xn_bct, const float* w_kcl, c
     size_t lds;
     if ((rc = plan_bwdx("ign_shapelet_bwd_input", xn_bct, w_kcl, g_out, p_out, dmin_out, ld, col0, tstar, zmu, d_save, gxn_bct,
                         accumulate, B, C, T, K, L, stride, eps, mode, &a, &dist, &lds))) return rc;
-    return ign_launch_bwdx(a, dist, lds, (hipStream_t)stream);
+    return ign_launch_bwdx(a, dist, tie_exact(mode, dist), lds, (hipStream_t)stream);
 }
 
 extern "C" int ign_shapelet_bwd_input_bank(const float* xn_bct, int G, const float* const* w_kcl, const float* g_out,
@@ -551,6 +555,6 @@ extern "C" int ign_shapelet_bwd_input_bank(const float* xn_bct, int G, const flo
         if ((rc = plan_bwdx(who, xn_bct, w_kcl[g], g_out, p_out, dmin_out, ld, col0[g], tstar[g], zmu[g], d_save[g], gxn_bct,
                             g > 0, B, C, T, K[g], L[g], stride[g], eps, mode, &a[g], &dist[g], &lds[g]))) return rc;
     for (int g = 0; g < G; ++g)          // in the order given: the first group overwrites gxn, the others add to it
-        if ((rc = ign_launch_bwdx(a[g], dist[g], lds[g], (hipStream_t)stream))) return rc;
+        if ((rc = ign_launch_bwdx(a[g], dist[g], tie_exact(mode, dist[g]), lds[g], (hipStream_t)stream))) return rc;
     return 0;
 }

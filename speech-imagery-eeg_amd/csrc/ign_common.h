@@ -89,8 +89,9 @@ struct ShpBwdArgs {
     int njt;              // strided kernel only: tiles of cpk*JJ shapelet positions per shapelet (L > 2048 needs > 1)
 };
 typedef void (*shp_bwd_launch_t)(const ShpBwdArgs&, dim3 grid, dim3 block, size_t lds, hipStream_t);
-shp_bwd_launch_t ign_get_bwd_launcher(int dist, int JJ);            // JJ in {4,8}
-shp_bwd_launch_t ign_get_bwd_strided_launcher(int dist);            // stride > 1: JJ = 4, generic window step
+// tie_exact (IGN_TIE_EXACT) selects the sign(0) = 0 instantiation of an L1 kernel; other distances have one kernel each
+shp_bwd_launch_t ign_get_bwd_launcher(int dist, int JJ, bool tie_exact);      // JJ in {4,8}
+shp_bwd_launch_t ign_get_bwd_strided_launcher(int dist, bool tie_exact);      // stride > 1: JJ = 4, generic window step
 
 // ---------------------------------------------------------------- backward w.r.t. the input (ign_shapelet_bwd_x.hip)
 struct ShpBwdXArgs {
@@ -114,7 +115,7 @@ struct ShpBwdXArgs {
 };
 constexpr int SHP_BWDX_THREADS = 256, SHP_BWDX_SPL = 4, SHP_BWDX_TILE = SHP_BWDX_THREADS * SHP_BWDX_SPL;
 size_t ign_bwdx_plan(ShpBwdXArgs* a);                                  // fills ntile / kb / mc / M / na; -> bytes of LDS
-int ign_launch_bwdx(const ShpBwdXArgs& a, int dist, size_t lds, hipStream_t s);
+int ign_launch_bwdx(const ShpBwdXArgs& a, int dist, bool tie_exact, size_t lds, hipStream_t s);
 
 void ign_launch_reduce_parts(const float* part, float* out, int nparts, size_t n, hipStream_t s);
 

@@ -51,6 +51,30 @@ __device__ __forceinline__ void bwd_l1_step(float (&acc)[JJ], const float (&wa)[
     }
 }
 
+// IGN_TIE_EXACT (opt-in): the signed sum itself, acc += A where x > w, acc -= A where x < w, nothing where x == w --
+// sign(0) = 0 as aten::sgn.  The sequence of bwd_l1_step twice per element, EXEC restored after every compare: 4 VALU +
+// 2 SALU, the same JJ accumulators (no second sum, no S), so the register budget and the occupancy stay those of the default.
+template <int JJ>
+__device__ __forceinline__ void bwd_l1_tie_step(float (&acc)[JJ], const float (&wa)[JJ], const float (&wb)[JJ],
+                                                const float (&wreg)[JJ], const float (&A)[JJ]) {
+#pragma unroll
+    for (int t = 0; t < JJ; ++t) {
+#pragma unroll
+        for (int jj = 0; jj < JJ; jj += 2) {
+#define IGN_WIN(q) ((t + jj + (q)) < JJ ? wa[(t + jj + (q)) % JJ] : wb[(t + jj + (q)) % JJ])
+            asm volatile(
+                "v_cmpx_gt_f32 %2, %4\n\tv_add_f32 %0, %0, %6\n\ts_mov_b64 exec, -1\n\t"
+                "v_cmpx_lt_f32 %2, %4\n\tv_sub_f32 %0, %0, %6\n\ts_mov_b64 exec, -1\n\t"
+                "v_cmpx_gt_f32 %3, %5\n\tv_add_f32 %1, %1, %6\n\ts_mov_b64 exec, -1\n\t"
+                "v_cmpx_lt_f32 %3, %5\n\tv_sub_f32 %1, %1, %6\n\ts_mov_b64 exec, -1"
+                : "+v"(acc[jj]), "+v"(acc[jj + 1])
+                : "v"(IGN_WIN(0)), "v"(IGN_WIN(1)), "v"(wreg[jj]), "v"(wreg[jj + 1]), "v"(A[t])
+                : "vcc");
+#undef IGN_WIN
+        }
+    }
+}
+
 template <int JJ>
 __device__ __forceinline__ void bwd_mse_step(float (&acc)[JJ], const float (&wa)[JJ], const float (&wb)[JJ],
                                              const float (&wreg)[JJ], const float (&A)[JJ]) {
@@ -89,9 +113,11 @@ __device__ __forceinline__ void lds_load(float (&dst)[JJ], const float* p) {
 // x[t*stride + j] from the LDS chunk and A[k][t] as a broadcast.  A shapelet longer than 512*JJ positions is split over
 // `njt` blocks (blockIdx.z = k*njt + tile), each recomputing A for its shapelet (kb = 1).  Same staging, same fixed-order
 // reduction, same outputs; built for the long-sequence UEA sets (MotorImagery, EigenWorms), not for the benchmark shape.
-template <int JJ, int DIST, bool STRIDED = false>
+// TIE (IGN_TIE_EXACT, L1 only): the hot step is bwd_l1_tie_step / a two-way select, and the result is the accumulator itself.
+template <int JJ, int DIST, bool STRIDED = false, bool TIE = false>
 __global__ void __launch_bounds__(512, 7) shp_bwd_kernel(const ShpBwdArgs a) {
     static_assert(JJ % 4 == 0, "float4 LDS reads need 4-float alignment");
+    static_assert(!TIE || DIST == DIST_L1, "the exact-tie variant exists for L1 only");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* xs = smem;                        // [xs_len]      x[b,c,t0 + i]
     float* As = smem + a.xs_len;             // [kb][tc]      A[k][t0 + t]
@@ -262,7 +288,8 @@ __global__ void __launch_bounds__(512, 7) shp_bwd_kernel(const ShpBwdArgs a) {
 #pragma unroll
                     for (int jj = 0; jj < JJ; ++jj) {
                         const float xv = xw[jj];
-                        if (DIST == DIST_L1)       acc[jj] += (xv > wreg[jj]) ? At : 0.f;
+                        if (TIE)                   acc[jj] += (xv > wreg[jj]) ? At : (xv < wreg[jj]) ? -At : 0.f;
+                        else if (DIST == DIST_L1)  acc[jj] += (xv > wreg[jj]) ? At : 0.f;
                         else if (DIST == DIST_MSE) acc[jj] = fmaf(At, xv - wreg[jj], acc[jj]);
                         else                       acc[jj] = fmaf(At, xv, acc[jj]);
                     }
@@ -274,12 +301,14 @@ __global__ void __launch_bounds__(512, 7) shp_bwd_kernel(const ShpBwdArgs a) {
             for (int t = 0; t < a.tc; t += 2 * JJ) {         // tc is a multiple of 2*JJ: two ping-pong steps
                 lds_load<JJ>(Wb, xl + t + JJ);
                 lds_load<JJ>(A, Ak + t);
-                if (DIST == DIST_L1)       bwd_l1_step<JJ>(acc, Wa, Wb, wreg, A);
+                if (TIE)                   bwd_l1_tie_step<JJ>(acc, Wa, Wb, wreg, A);
+                else if (DIST == DIST_L1)  bwd_l1_step<JJ>(acc, Wa, Wb, wreg, A);
                 else if (DIST == DIST_MSE) bwd_mse_step<JJ>(acc, Wa, Wb, wreg, A);
                 else                       bwd_dot_step<JJ>(acc, Wa, Wb, A);
                 lds_load<JJ>(Wa, xl + t + 2 * JJ);
                 lds_load<JJ>(A, Ak + t + JJ);
-                if (DIST == DIST_L1)       bwd_l1_step<JJ>(acc, Wb, Wa, wreg, A);
+                if (TIE)                   bwd_l1_tie_step<JJ>(acc, Wb, Wa, wreg, A);
+                else if (DIST == DIST_L1)  bwd_l1_step<JJ>(acc, Wb, Wa, wreg, A);
                 else if (DIST == DIST_MSE) bwd_mse_step<JJ>(acc, Wb, Wa, wreg, A);
                 else                       bwd_dot_step<JJ>(acc, Wb, Wa, A);
             }
@@ -291,17 +320,17 @@ __global__ void __launch_bounds__(512, 7) shp_bwd_kernel(const ShpBwdArgs a) {
 #pragma unroll
         for (int jj = 0; jj < JJ; ++jj)
             if (j0 + jbase + jj < a.L)
-                out[j0 + jbase + jj] = (DIST == DIST_L1) ? 2.f * acc[jj] - ssum
+                out[j0 + jbase + jj] = TIE ? acc[jj] : (DIST == DIST_L1) ? 2.f * acc[jj] - ssum
                                 : (DIST == DIST_MSE) ? acc[jj] : acc[jj] + wreg[jj] * ssum;
     }
 }
 
-template <int JJ, int DIST>
+template <int JJ, int DIST, bool TIE = false>
 static void shp_bwd_launch(const ShpBwdArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
-    hipLaunchKernelGGL((shp_bwd_kernel<JJ, DIST, false>), grid, block, lds, s, a);
+    hipLaunchKernelGGL((shp_bwd_kernel<JJ, DIST, false, TIE>), grid, block, lds, s, a);
 }
 
-template <int DIST>
+template <int DIST, bool TIE = false>
 static void shp_bwd_strided_launch(const ShpBwdArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
-    hipLaunchKernelGGL((shp_bwd_kernel<4, DIST, true>), grid, block, lds, s, a);
+    hipLaunchKernelGGL((shp_bwd_kernel<4, DIST, true, TIE>), grid, block, lds, s, a);
 }

@@ -1,8 +1,11 @@
 // Backward instantiations + the fixed-order reduction over batch slices.
 #include "ign_shapelet_bwd.h"
 
-shp_bwd_launch_t ign_get_bwd_launcher(int dist, int JJ) {
-    if (dist == DIST_L1) {
+shp_bwd_launch_t ign_get_bwd_launcher(int dist, int JJ, bool tie_exact) {
+    if (dist == DIST_L1 && tie_exact) {
+        if (JJ == 4) return shp_bwd_launch<4, DIST_L1, true>;
+        if (JJ == 8) return shp_bwd_launch<8, DIST_L1, true>;
+    } else if (dist == DIST_L1) {
         if (JJ == 4) return shp_bwd_launch<4, DIST_L1>;
         if (JJ == 8) return shp_bwd_launch<8, DIST_L1>;
     } else if (dist == DIST_MSE) {
@@ -18,7 +21,8 @@ shp_bwd_launch_t ign_get_bwd_launcher(int dist, int JJ) {
     return nullptr;
 }
 
-shp_bwd_launch_t ign_get_bwd_strided_launcher(int dist) {
+shp_bwd_launch_t ign_get_bwd_strided_launcher(int dist, bool tie_exact) {
+    if (dist == DIST_L1 && tie_exact) return shp_bwd_strided_launch<DIST_L1, true>;
     switch (dist) {
         case DIST_L1: return shp_bwd_strided_launch<DIST_L1>;
         case DIST_MSE: return shp_bwd_strided_launch<DIST_MSE>;

@@ -35,9 +35,11 @@ __device__ __forceinline__ float shp_dldd(int gate, float d1, int t, int ts, flo
     return gm * (hard + sft * (mu - d1));
 }
 
-template <int DIST, bool S1>
+// TIE (IGN_TIE_EXACT, L1 only): the step adds av where x > w, subtracts it where x < w and adds nothing where x == w.
+template <int DIST, bool S1, bool TIE = false>
 __global__ void __launch_bounds__(SHP_BWDX_THREADS) shp_bwdx_kernel(const ShpBwdXArgs a) {
     constexpr int SPL = SHP_BWDX_SPL, TILE = SHP_BWDX_TILE, NT = SHP_BWDX_THREADS;
+    static_assert(!TIE || DIST == DIST_L1, "the exact-tie variant exists for L1 only");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int stride = S1 ? 1 : a.stride;
     const int wlen = a.mc * stride;
@@ -129,8 +131,9 @@ __global__ void __launch_bounds__(SHP_BWDX_THREADS) shp_bwdx_kernel(const ShpBwd
 #pragma unroll
                         for (int i = 0; i < SPL; ++i) {
                             const float av = ab[i][-mm];
-                            if (DIST == DIST_L1) acc[i] += (x[i] > wj) ? av : -av;
-                            else                 acc[i] = fmaf(av, x[i] - wj, acc[i]);
+                            if (TIE)                  acc[i] += (x[i] > wj) ? av : (x[i] < wj) ? -av : 0.f;
+                            else if (DIST == DIST_L1) acc[i] += (x[i] > wj) ? av : -av;
+                            else                      acc[i] = fmaf(av, x[i] - wj, acc[i]);
                         }
                     } else {
 #pragma unroll
@@ -138,8 +141,9 @@ __global__ void __launch_bounds__(SHP_BWDX_THREADS) shp_bwdx_kernel(const ShpBwd
                             const int jl = r[i] + mm * stride;                  // < wlen; position j = m0*stride + jl
                             const float wj = wsk[jl];
                             const float av = (m0 * stride + jl < a.L) ? ab[i][-mm] : 0.f;
-                            if (DIST == DIST_L1) acc[i] += (x[i] > wj) ? av : -av;
-                            else                 acc[i] = fmaf(av, x[i] - wj, acc[i]);
+                            if (TIE)                  acc[i] += (x[i] > wj) ? av : (x[i] < wj) ? -av : 0.f;
+                            else if (DIST == DIST_L1) acc[i] += (x[i] > wj) ? av : -av;
+                            else                      acc[i] = fmaf(av, x[i] - wj, acc[i]);
                         }
                     }
                 }
@@ -166,10 +170,13 @@ size_t ign_bwdx_plan(ShpBwdXArgs* a) {
     return ((size_t)a->kb * ((size_t)a->mc * a->stride + a->na + 8)) * sizeof(float);
 }
 
-int ign_launch_bwdx(const ShpBwdXArgs& a, int dist, size_t lds, hipStream_t s) {
+int ign_launch_bwdx(const ShpBwdXArgs& a, int dist, bool tie_exact, size_t lds, hipStream_t s) {
     const dim3 grid((unsigned)((size_t)a.B * a.C * a.ntile)), block(SHP_BWDX_THREADS);
     IgnScopedTimer tm("shp_bwd_x", s);
-    if (dist == DIST_L1) {
+    if (dist == DIST_L1 && tie_exact) {
+        if (a.stride == 1) hipLaunchKernelGGL((shp_bwdx_kernel<DIST_L1, true, true>), grid, block, lds, s, a);
+        else               hipLaunchKernelGGL((shp_bwdx_kernel<DIST_L1, false, true>), grid, block, lds, s, a);
+    } else if (dist == DIST_L1) {
         if (a.stride == 1) hipLaunchKernelGGL((shp_bwdx_kernel<DIST_L1, true>), grid, block, lds, s, a);
         else               hipLaunchKernelGGL((shp_bwdx_kernel<DIST_L1, false>), grid, block, lds, s, a);
     } else {

@@ -14,6 +14,7 @@ ATTN_MATH = os.environ.get("IGN_ATTN_MATH", "bf16x6")          # "f32": attentio
 LAYERNORM_MIN_ROWS = 0        # round 1 kept torch below 64k rows; with the row-count-aware grid and the parallel reduce the HIP kernels win everywhere
 LINEAR_WGRAD = "bf16x6"       # weight gradient of ops.linear on the split kernels; "f32" (set by tests / diag scripts): the fp32-MFMA TN kernel
 GATE_RBF, GATE_LTS = 0x00, 0x10
+TIE_EXACT = 0x20              # IGN_TIE_EXACT: the L1 backward passes take sign(0) = 0 at x == w, as aten::sgn; travels inside `mode`
 HEAD_NMAX = 256               # IGN_HEAD_NMAX (include/ign_abi.h): widest class head of ign_head_* / ign_loss_*
 HEAD_WIDE_BMAX = 640          # batch bound of ign_head_bwd above 16 classes (one 16-class chunk of the logit gradient in 40 KB of LDS)
 

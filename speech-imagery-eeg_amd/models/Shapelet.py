@@ -9,6 +9,8 @@ runs as one autograd node over ``ign_shapelet_fwd/bwd`` (include/ign_abi.h), whi
 
 There is no CPU path: tensors must live on the GPU and libign_hip.so must be built (ign_hip._lib).
 """
+import os
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -39,6 +41,10 @@ def _distance_code(distance_func, memory_efficient, lts=False):
 class Shapelet(nn.Module):
     """One length group: K shapelets of length L on C channels (IGN/model/Shapelet.py:46-87)."""
     gate = ops.GATE_RBF
+    # L1 backward passes with sign(0) = 0 at x == w, as the reference's aten::sgn (ops.TIE_EXACT; include/ign_abi.h), instead of
+    # the default kernels' -1: for shapelets initialised as copies of training windows.  Slower; the default is read once, on
+    # import, from IGN_TIE_EXACT=1, and the attribute is assignable per class, model (set_tie_exact) or instance.
+    tie_exact = os.environ.get("IGN_TIE_EXACT") == "1"
 
     def __init__(self, dim_data, shapelet_len, num_shapelet=10, stride=1, eps=1., distance_func='euclidean',
                  memory_efficient=False):
@@ -53,7 +59,10 @@ class Shapelet(nn.Module):
         self.eps = eps
 
     def mode(self):
-        return _distance_code(self.distance_func, self.memory_efficient, self.gate == ops.GATE_LTS) | self.gate
+        mode = _distance_code(self.distance_func, self.memory_efficient, self.gate == ops.GATE_LTS) | self.gate
+        if self.tie_exact and (mode & 0xf) == ops.DIST_L1:
+            mode |= ops.TIE_EXACT
+        return mode
 
     def forward(self, x):
         """x: instance-normalised (B, C, T) -> (p, d_min), each (B, K*C) with feature index k*C + c."""
@@ -198,6 +207,13 @@ class ShapeBottleneckModel(nn.Module):
         p, d, t = self.shapelet_features(x, xn)
         out = self.head(p)
         return out, ModelInfo(d=d, p=p, shapelet_preds=out, preds=out, loss=self.loss().unsqueeze(0), t=t)
+
+    def set_tie_exact(self, flag=True):
+        """Switch every length group to (or from) the exact sign(0) = 0 L1 backward passes (Shapelet.tie_exact); the bank runs
+        in the first group's mode, so a model-level switch sets all of them.  Returns self."""
+        for s in self.shapelets:
+            s.tie_exact = bool(flag)
+        return self
 
     def match_layout(self):
         """per feature column (g*K*C + k*C + c): (window stride, shapelet length) -- turns ModelInfo.t into sample ranges"""
