@@ -1,4 +1,5 @@
-// Expert-head GEMMs, the gini gate and the flat Adam update: the small HBM-bound pieces of the training step.
+// Expert-head GEMMs, the flat Adam update and the SBM regularisers: the small HBM-bound pieces of the training step.  (The gini
+// gate and the fused loss tails are in ign_loss.hip.)
 //
 //  * head GEMM  out[b,n] = sum_f X[b,f] W[n,f] (+ bias[n])  with N = number of classes (2..IGN_HEAD_NMAX = 256; above 16 in
 //    16-class chunks, one extra grid dimension, same launch count) -- "skinny":
@@ -6,8 +7,6 @@
 //    IGN/model/FullyConvNet.py:50,58.  N is far too small for an MFMA tile to pay (a 32x32 tile would be >90 % padding)
 //    and the op moves 4*(B*F + N*F) bytes for 2*B*F*N flops (intensity ~N/2 flop/byte): HBM/L2 bound, so it is a
 //    coalesced float4 streaming kernel with N accumulators per thread and a block reduction.
-//  * gini gate  eta = (N*sum softmax(s)^2 - 1)/(N-1); out = eta*s + (1-eta)*d   IGN/model/InterpGN.py:44-52, fwd + bwd; and the
-//    fused loss tail (gate + both cross-entropies + their logit gradients): one thread per row up to 16 classes, one wave per row above.
 //  * Adam       one launch over the flat parameter / gradient / moment buffers (torch.optim.Adam semantics,
 //    IGN/exp/experiment_classification.py:136,338).
 #include "ign_common.h"
@@ -200,256 +199,6 @@ __global__ void __launch_bounds__(256) head_bwd_xw_kernel(const float* __restric
     }
 }
 
-// ------------------------------------------------------------------------------------------------ gini gate
-// forward: q = softmax(s); G = sum q^2; eta = (N G - 1)/(N - 1); [eta > thr -> 1]; out = eta s + (1 - eta) d
-// backward: d eta / d s_j = (2N/(N-1)) q_j (q_j - G); ds = eta*gout + (sum_n gout_n (s_n - d_n)) * deta/ds ; dd = (1-eta)*gout
-__global__ void __launch_bounds__(256) gate_fwd_kernel(const float* __restrict__ s, const float* __restrict__ d,
-                                                       float* __restrict__ out, float* __restrict__ eta_out, int B, int N,
-                                                       float thr, int use_thr) {
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    if (b >= B) return;
-    const float* sr = s + (long long)b * N;
-    float mx = -INFINITY;
-    for (int n = 0; n < N; ++n) mx = fmaxf(mx, sr[n]);
-    float z = 0.f, z2 = 0.f;
-    for (int n = 0; n < N; ++n) {
-        const float e = expf(sr[n] - mx);
-        z += e;
-        z2 += e * e;
-    }
-    float eta = ((float)N * (z2 / (z * z)) - 1.f) / (float)(N - 1);
-    if (use_thr && eta > thr) eta = 1.f;
-    eta_out[b] = eta;
-    for (int n = 0; n < N; ++n) out[(long long)b * N + n] = eta * sr[n] + (1.f - eta) * d[(long long)b * N + n];
-}
-
-__global__ void __launch_bounds__(256) gate_bwd_kernel(const float* __restrict__ s, const float* __restrict__ d,
-                                                       const float* __restrict__ gout, const float* __restrict__ geta,
-                                                       float* __restrict__ gs, float* __restrict__ gd, int B, int N,
-                                                       float thr, int use_thr) {
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    if (b >= B) return;
-    const float* sr = s + (long long)b * N;
-    const float* dr = d + (long long)b * N;
-    const float* gr = gout + (long long)b * N;
-    float mx = -INFINITY;
-    for (int n = 0; n < N; ++n) mx = fmaxf(mx, sr[n]);
-    float z = 0.f, z2 = 0.f, dot = geta ? geta[b] : 0.f;
-    for (int n = 0; n < N; ++n) {
-        const float e = expf(sr[n] - mx);
-        z += e;
-        z2 += e * e;
-        dot += gr[n] * (sr[n] - dr[n]);
-    }
-    const float G = z2 / (z * z);
-    float eta = ((float)N * G - 1.f) / (float)(N - 1);
-    float c = 2.f * (float)N / (float)(N - 1) * dot;
-    if (use_thr && eta > thr) { eta = 1.f; c = 0.f; }         // the hard branch has no gradient through eta
-    for (int n = 0; n < N; ++n) {
-        const float q = expf(sr[n] - mx) / z;
-        gs[(long long)b * N + n] = eta * gr[n] + c * q * (q - G);
-        gd[(long long)b * N + n] = (1.f - eta) * gr[n];
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ fused training-loss tail
-// IGN's per-step loss tail, IGN/exp/experiment_classification.py:320-329 + IGN/model/InterpGN.py:44-52, in ONE launch:
-//   out = eta*s + (1-eta)*d (gini gate);  loss = CE(out, y) + beta*CE(s, y)  (batch means);  and the gradients of that
-//   loss w.r.t. both experts' logits -- what torch spends ~40 softmax / nll / mean / add kernels (forward + backward) on,
-//   all of them serialised between the last forward kernel and the first backward kernel.
-// One block; thread <-> rows b, b+256, ...; the two CE sums are reduced through LDS in thread order (deterministic).
-constexpr int LOSS_NMAX = 16;
-__global__ void __launch_bounds__(256) ign_loss_kernel(const float* __restrict__ s, const float* __restrict__ d,
-                                                       const long long* __restrict__ y, float* __restrict__ out,
-                                                       float* __restrict__ eta_out, float* __restrict__ loss2,
-                                                       float* __restrict__ gs, float* __restrict__ gd, int B, int N, float beta,
-                                                       const float* __restrict__ reg) {
-    __shared__ float red[2][256];
-    float ce_o = 0.f, ce_s = 0.f;
-    const float invB = 1.f / (float)B;
-    for (int b = threadIdx.x; b < B; b += 256) {
-        float sv[LOSS_NMAX], ov[LOSS_NMAX], q[LOSS_NMAX];
-        const float* sr = s + (long long)b * N;
-        const float* dr = d + (long long)b * N;
-        const int yb = (int)y[b];
-        float mx = -INFINITY;
-        for (int n = 0; n < N; ++n) { sv[n] = sr[n]; mx = fmaxf(mx, sv[n]); }
-        float z = 0.f, z2 = 0.f;
-        for (int n = 0; n < N; ++n) { q[n] = expf(sv[n] - mx); z += q[n]; z2 += q[n] * q[n]; }
-        const float G = z2 / (z * z);
-        const float eta = ((float)N * G - 1.f) / (float)(N - 1);
-        eta_out[b] = eta;
-        const float lse_s = mx + logf(z);
-        ce_s += lse_s - sv[yb];
-        float mo = -INFINITY;
-        for (int n = 0; n < N; ++n) {
-            ov[n] = eta * sv[n] + (1.f - eta) * dr[n];
-            out[(long long)b * N + n] = ov[n];
-            mo = fmaxf(mo, ov[n]);
-        }
-        float zo = 0.f;
-        for (int n = 0; n < N; ++n) zo += expf(ov[n] - mo);
-        ce_o += mo + logf(zo) - ov[yb];
-        // gradients: g_out = (softmax(out) - onehot)/B ; through the gate (see gate_bwd_kernel) ; + beta*(softmax(s) - onehot)/B
-        float dot = 0.f;
-        float go[LOSS_NMAX];
-        for (int n = 0; n < N; ++n) {
-            go[n] = (expf(ov[n] - mo) / zo - (n == yb ? 1.f : 0.f)) * invB;
-            dot += go[n] * (sv[n] - dr[n]);
-        }
-        const float c = 2.f * (float)N / (float)(N - 1) * dot;
-        for (int n = 0; n < N; ++n) {
-            const float qn = q[n] / z;
-            gs[(long long)b * N + n] = eta * go[n] + c * qn * (qn - G) + beta * (qn - (n == yb ? 1.f : 0.f)) * invB;
-            gd[(long long)b * N + n] = (1.f - eta) * go[n];
-        }
-    }
-    red[0][threadIdx.x] = ce_o;
-    red[1][threadIdx.x] = ce_s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float a = 0.f, b2 = 0.f;
-        for (int i = 0; i < 256; ++i) { a += red[0][i]; b2 += red[1][i]; }
-        loss2[0] = a * invB;
-        loss2[1] = b2 * invB;
-        loss2[2] = a * invB + beta * (b2 * invB) + (reg ? reg[0] : 0.f);        // + info.loss.mean() (exp:325-329)
-    }
-}
-
-// The same loss tail for 16 < N <= IGN_HEAD_NMAX: one block of 16 waves, one wave per row (rows w, w + 16, ...), the lanes cover
-// the classes in chunks of 64 and every row-wide max / sum is a butterfly over the wave (each lane ends with the same value).
-// The arithmetic per row is ign_loss_kernel's.  Each row's two CE terms go to LDS at their row index; one thread adds them in
-// ascending row order (LOSS_TILE rows at a time), so the batch mean does not depend on how the waves were scheduled.
-constexpr int LOSS_WAVES = 16, LOSS_TILE = 1024, LOSS_KMAX = IGN_HEAD_NMAX / 64;
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__global__ void __launch_bounds__(LOSS_WAVES * 64) ign_loss_wide_kernel(const float* __restrict__ s, const float* __restrict__ d,
-                                                                        const long long* __restrict__ y, float* __restrict__ out,
-                                                                        float* __restrict__ eta_out, float* __restrict__ loss2,
-                                                                        float* __restrict__ gs, float* __restrict__ gd, int B, int N,
-                                                                        float beta, const float* __restrict__ reg) {
-    __shared__ float ce[2][LOSS_TILE];
-    __shared__ float tot[2];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float invB = 1.f / (float)B;
-    if (threadIdx.x == 0) { tot[0] = 0.f; tot[1] = 0.f; }
-    for (int base = 0; base < B; base += LOSS_TILE) {
-        const int rows = min(LOSS_TILE, B - base);
-        for (int r = wave; r < rows; r += LOSS_WAVES) {
-            const int b = base + r;
-            const float* sr = s + (long long)b * N;
-            const float* dr = d + (long long)b * N;
-            const int yb = (int)y[b];
-            float sv[LOSS_KMAX], dv[LOSS_KMAX], q[LOSS_KMAX], ov[LOSS_KMAX], eo[LOSS_KMAX];
-            float mx = -INFINITY;
-#pragma unroll
-            for (int k = 0; k < LOSS_KMAX; ++k) {
-                const int n = k * 64 + lane;
-                sv[k] = n < N ? sr[n] : -INFINITY;
-                dv[k] = n < N ? dr[n] : 0.f;
-                mx = fmaxf(mx, sv[k]);
-            }
-            mx = wave_max(mx);
-            float z = 0.f, z2 = 0.f;
-#pragma unroll
-            for (int k = 0; k < LOSS_KMAX; ++k) {
-                q[k] = k * 64 + lane < N ? expf(sv[k] - mx) : 0.f;
-                z += q[k];
-                z2 += q[k] * q[k];
-            }
-            z = wave_sum(z);
-            z2 = wave_sum(z2);
-            const float G = z2 / (z * z);
-            const float eta = ((float)N * G - 1.f) / (float)(N - 1);
-            if (lane == 0) eta_out[b] = eta;
-            float mo = -INFINITY, s_y = 0.f, o_y = 0.f;
-#pragma unroll
-            for (int k = 0; k < LOSS_KMAX; ++k) {
-                const int n = k * 64 + lane;
-                ov[k] = eta * sv[k] + (1.f - eta) * dv[k];
-                if (n < N) {
-                    out[(long long)b * N + n] = ov[k];
-                    mo = fmaxf(mo, ov[k]);
-                }
-                if (n == yb) { s_y = sv[k]; o_y = ov[k]; }
-            }
-            mo = wave_max(mo);
-            s_y = wave_sum(s_y);                  // exactly one lane holds the label's logits, the others add zeros
-            o_y = wave_sum(o_y);
-            float zo = 0.f;
-#pragma unroll
-            for (int k = 0; k < LOSS_KMAX; ++k) {
-                eo[k] = k * 64 + lane < N ? expf(ov[k] - mo) : 0.f;
-                zo += eo[k];
-            }
-            zo = wave_sum(zo);
-            // gradients: g_out = (softmax(out) - onehot)/B ; through the gate (see gate_bwd_kernel) ; + beta*(softmax(s) - onehot)/B
-            float dot = 0.f;
-#pragma unroll
-            for (int k = 0; k < LOSS_KMAX; ++k) {
-                const int n = k * 64 + lane;
-                eo[k] = (eo[k] / zo - (n == yb ? 1.f : 0.f)) * invB;          // go
-                if (n < N) dot += eo[k] * (sv[k] - dv[k]);
-            }
-            dot = wave_sum(dot);
-            const float c = 2.f * (float)N / (float)(N - 1) * dot;
-#pragma unroll
-            for (int k = 0; k < LOSS_KMAX; ++k) {
-                const int n = k * 64 + lane;
-                if (n < N) {
-                    const float qn = q[k] / z;
-                    gs[(long long)b * N + n] = eta * eo[k] + c * qn * (qn - G) + beta * (qn - (n == yb ? 1.f : 0.f)) * invB;
-                    gd[(long long)b * N + n] = (1.f - eta) * eo[k];
-                }
-            }
-            if (lane == 0) {
-                ce[0][r] = mo + logf(zo) - o_y;
-                ce[1][r] = mx + logf(z) - s_y;
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x == 0)
-            for (int i = 0; i < rows; ++i) { tot[0] += ce[0][i]; tot[1] += ce[1][i]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        const float a = tot[0], b2 = tot[1];
-        loss2[0] = a * invB;
-        loss2[1] = b2 * invB;
-        loss2[2] = a * invB + beta * (b2 * invB) + (reg ? reg[0] : 0.f);        // + info.loss.mean() (exp:325-329)
-    }
-}
-
-extern "C" int ign_loss_fwd_bwd_reg(const float* sbm, const float* dnn, const long long* labels, const float* reg, float* out,
-                                    float* eta, float* loss2, float* gsbm, float* gdnn, int B, int N, float beta, void* stream) {
-    if (!sbm || !dnn || !labels || !out || !eta || !loss2 || !gsbm || !gdnn || B <= 0 || N < 2) {
-        ign_set_error("ign_loss_fwd_bwd: null pointer or bad dimension (B=%d N=%d, N <= %d)", B, N, IGN_HEAD_NMAX);
-        return IGN_E_ARG;
-    }
-    if (N > IGN_HEAD_NMAX) { ign_set_error("ign_loss_fwd_bwd: N=%d classes > %d", N, IGN_HEAD_NMAX); return IGN_E_UNSUP; }
-    if (N > LOSS_NMAX) {
-        hipLaunchKernelGGL(ign_loss_wide_kernel, dim3(1), dim3(LOSS_WAVES * 64), 0, (hipStream_t)stream, sbm, dnn, labels, out, eta,
-                           loss2, gsbm, gdnn, B, N, beta, reg);
-        return ign_check_launch("ign_loss_wide_kernel");
-    }
-    hipLaunchKernelGGL(ign_loss_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, sbm, dnn, labels, out, eta, loss2, gsbm, gdnn, B, N,
-                       beta, reg);
-    return ign_check_launch("ign_loss_kernel");
-}
-
-extern "C" int ign_loss_fwd_bwd(const float* sbm, const float* dnn, const long long* labels, float* out, float* eta, float* loss2,
-                                float* gsbm, float* gdnn, int B, int N, float beta, void* stream) {
-    return ign_loss_fwd_bwd_reg(sbm, dnn, labels, nullptr, out, eta, loss2, gsbm, gdnn, B, N, beta, stream);
-}
-
 // ------------------------------------------------------------------------------------------------ Adam
 __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, long long n, float lr, float b1, float b2,
@@ -591,28 +340,6 @@ extern "C" int ign_head_bwd_acc(const float* g, const float* X, const float* W, 
         if ((rc = ign_check_launch("head_bwd_w_kernel"))) return rc;
     }
     return 0;
-}
-
-extern "C" int ign_gate_fwd(const float* sbm, const float* dnn, float* out, float* eta, int B, int N, float gating_value,
-                            int use_gating_value, void* stream) {
-    if (!sbm || !dnn || !out || !eta || B <= 0 || N < 2) {
-        ign_set_error("ign_gate_fwd: null pointer or bad dimension (B=%d N=%d)", B, N);
-        return IGN_E_ARG;
-    }
-    hipLaunchKernelGGL(gate_fwd_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, sbm, dnn, out, eta, B, N,
-                       gating_value, use_gating_value);
-    return ign_check_launch("gate_fwd_kernel");
-}
-
-extern "C" int ign_gate_bwd(const float* sbm, const float* dnn, const float* gout, const float* geta, float* gsbm,
-                            float* gdnn, int B, int N, float gating_value, int use_gating_value, void* stream) {
-    if (!sbm || !dnn || !gout || !gsbm || !gdnn || B <= 0 || N < 2) {
-        ign_set_error("ign_gate_bwd: null pointer or bad dimension (B=%d N=%d)", B, N);
-        return IGN_E_ARG;
-    }
-    hipLaunchKernelGGL(gate_bwd_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, sbm, dnn, gout, geta, gsbm,
-                       gdnn, B, N, gating_value, use_gating_value);
-    return ign_check_launch("gate_bwd_kernel");
 }
 
 extern "C" int ign_adam_step(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2,

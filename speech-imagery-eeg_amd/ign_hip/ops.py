@@ -1285,39 +1285,63 @@ def backward(loss):
         loss.backward()
 
 
+def _loss_tail(entry, sbm, dnn, crit, beta, reg):
+    """The one launcher of the gated loss tails -> (loss3, out, eta, gsd): loss3[2] = criterion(gate(sbm, dnn)) + beta*criterion(sbm)
+    [+ reg], gsd (2, B, N) = its gradient w.r.t. (sbm, dnn) in one buffer.  `entry`: "ign_loss" (cross-entropy, crit = (labels,)) or
+    "ign_crps_loss" (CRPS, crit = (target, edges)); `crit` sits between `dnn` and `reg` in the entry point's signature."""
+    symbol = {"ign_loss": "ign_loss_fwd_bwd_reg", "ign_crps_loss": "ign_loss_crps_fwd_bwd_reg"}[entry]
+    B, N = sbm.shape
+    out = torch.empty_like(sbm)
+    gsd = torch.empty(2, B, N, device=sbm.device, dtype=torch.float32)
+    eta = torch.empty(B, 1, device=sbm.device, dtype=torch.float32)
+    loss3 = torch.empty(3, device=sbm.device, dtype=torch.float32)
+    if reg is not None:
+        reg = reg.contiguous().reshape(-1)
+        if reg.numel() != 1:
+            raise _lib.IgnError(f"{entry}: the regulariser must be one value, got {tuple(reg.shape)}")
+    _lib.check(getattr(_lib.lib(), symbol)(_ptr(sbm), _ptr(dnn), *map(_ptr, crit), _ptr(reg), _ptr(out), _ptr(eta), _ptr(loss3),
+                                           _ptr(gsd[0]), _ptr(gsd[1]), B, N, float(beta), _stream()), symbol)
+    return loss3, out, eta, gsd
+
+
+def _tail_forward(ctx, entry, sbm, dnn, prepare, crit, beta, reg):
+    """What the forwards of IgnLossFn and IgnCrpsLossFn share -> (loss, out, eta); out / eta are reporting outputs.  `prepare`
+    (_ce_inputs / _crps_inputs) checks the node's criterion arguments `crit` against the (B, N) logits and converts them."""
+    _need_gpu(entry, sbm, dnn, reg)
+    sbm, dnn = sbm.contiguous(), dnn.contiguous()
+    if dnn.shape != sbm.shape:                        # the kernel reads B*N elements of each
+        raise _lib.IgnError(f"{entry}: expert logits {tuple(sbm.shape)} vs {tuple(dnn.shape)}")
+    loss3, out, eta, gsd = _loss_tail(entry, sbm, dnn, prepare(entry, sbm, *crit), beta, reg)
+    ctx.save_for_backward(gsd)
+    ctx.n_crit, ctx.has_reg = len(crit), reg is not None
+    ctx.mark_non_differentiable(out, eta)
+    ctx.set_materialize_grads(False)              # no zero-filled "gradients" of the two reporting outputs per step
+    return loss3[2], out, eta
+
+
+def _tail_backward(ctx, gl):
+    """-> (gsbm, gdnn, None per criterion argument and for beta, greg = the root gradient, passed through)."""
+    if gl is None:
+        return (None,) * (ctx.n_crit + 4)
+    g = _unit_or_scaled(gl, ctx.saved_tensors[0])     # the root of ops.backward(): exactly 1 -- no scaling launch; else one for both
+    return (g[0], g[1], *(None,) * (ctx.n_crit + 1), gl.reshape(1) if ctx.has_reg else None)
+
+
+def _ce_inputs(name, logits, y):
+    _check_classes(name, logits.shape[1])
+    return (y.contiguous().long(),)
+
+
 class IgnLossFn(torch.autograd.Function):
-    """CE(gate(sbm, dnn), y) + beta * CE(sbm, y) [+ reg] with both logit gradients from one launch (ign_loss_fwd_bwd_reg)."""
+    """CE(gate(sbm, dnn), y) + beta * CE(sbm, y) [+ reg] with both logit gradients from one launch (_loss_tail)."""
 
     @staticmethod
     def forward(ctx, sbm, dnn, y, beta, reg):
-        _need_gpu("ign_loss", sbm, dnn, reg)
-        sbm, dnn = sbm.contiguous(), dnn.contiguous()
-        y = y.contiguous().long()
-        B, N = sbm.shape
-        _check_classes("ign_loss", N)
-        out = torch.empty_like(sbm)
-        gsd = torch.empty(2, B, N, device=sbm.device, dtype=torch.float32)       # (d loss / d sbm, d loss / d dnn), one buffer
-        eta = torch.empty(B, 1, device=sbm.device, dtype=torch.float32)
-        loss2 = torch.empty(3, device=sbm.device, dtype=torch.float32)
-        if reg is not None:
-            reg = reg.contiguous().reshape(-1)
-            if reg.numel() != 1:
-                raise _lib.IgnError(f"ign_loss: the regulariser must be one value, got {tuple(reg.shape)}")
-        _lib.check(_lib.lib().ign_loss_fwd_bwd_reg(_ptr(sbm), _ptr(dnn), _ptr(y), _ptr(reg), _ptr(out), _ptr(eta), _ptr(loss2),
-                                                   _ptr(gsd[0]), _ptr(gsd[1]), B, N, float(beta), _stream()), "ign_loss_fwd_bwd_reg")
-        ctx.save_for_backward(gsd)
-        ctx.reg_shape = None if reg is None else tuple(reg.shape)
-        ctx.mark_non_differentiable(out, eta)
-        ctx.set_materialize_grads(False)              # no zero-filled "gradients" of the two reporting outputs per step
-        return loss2[2], out, eta
+        return _tail_forward(ctx, "ign_loss", sbm, dnn, _ce_inputs, (y,), beta, reg)
 
     @staticmethod
     def backward(ctx, gl, gout, geta):
-        if gl is None:
-            return None, None, None, None, None
-        (gsd,) = ctx.saved_tensors
-        g = _unit_or_scaled(gl, gsd)     # the root gradient of ops.backward(): exactly 1 -- no scaling launch; else one for both
-        return g[0], g[1], None, None, (gl.reshape(ctx.reg_shape) if ctx.reg_shape is not None else None)
+        return _tail_backward(ctx, gl)
 
 
 def ign_loss(sbm_out, dnn_out, y, beta=1.0, reg=None):
@@ -1375,40 +1399,15 @@ def crps_loss(logits, target, edges):
 
 
 class IgnCrpsLossFn(torch.autograd.Function):
-    """CRPS(gate(sbm, dnn)) + beta * CRPS(sbm) [+ reg] with both logit gradients from one launch (ign_loss_crps_fwd_bwd_reg)."""
+    """CRPS(gate(sbm, dnn)) + beta * CRPS(sbm) [+ reg] with both logit gradients from one launch (_loss_tail)."""
 
     @staticmethod
     def forward(ctx, sbm, dnn, target, edges, beta, reg):
-        _need_gpu("ign_crps_loss", sbm, dnn, reg)
-        sbm, dnn = sbm.contiguous(), dnn.contiguous()
-        if dnn.shape != sbm.shape:
-            raise _lib.IgnError(f"ign_crps_loss: expert logits {tuple(sbm.shape)} vs {tuple(dnn.shape)}")
-        B, N = sbm.shape
-        target, edges = _crps_inputs("ign_crps_loss", sbm, target, edges)
-        out = torch.empty_like(sbm)
-        gsd = torch.empty(2, B, N, device=sbm.device, dtype=torch.float32)       # (d loss / d sbm, d loss / d dnn), one buffer
-        eta = torch.empty(B, 1, device=sbm.device, dtype=torch.float32)
-        loss3 = torch.empty(3, device=sbm.device, dtype=torch.float32)
-        if reg is not None:
-            reg = reg.contiguous().reshape(-1)
-            if reg.numel() != 1:
-                raise _lib.IgnError(f"ign_crps_loss: the regulariser must be one value, got {tuple(reg.shape)}")
-        _lib.check(_lib.lib().ign_loss_crps_fwd_bwd_reg(_ptr(sbm), _ptr(dnn), _ptr(target), _ptr(edges), _ptr(reg), _ptr(out),
-                                                        _ptr(eta), _ptr(loss3), _ptr(gsd[0]), _ptr(gsd[1]), B, N, float(beta),
-                                                        _stream()), "ign_loss_crps_fwd_bwd_reg")
-        ctx.save_for_backward(gsd)
-        ctx.reg_shape = None if reg is None else tuple(reg.shape)
-        ctx.mark_non_differentiable(out, eta)
-        ctx.set_materialize_grads(False)
-        return loss3[2], out, eta
+        return _tail_forward(ctx, "ign_crps_loss", sbm, dnn, _crps_inputs, (target, edges), beta, reg)
 
     @staticmethod
     def backward(ctx, gl, gout, geta):
-        if gl is None:
-            return None, None, None, None, None, None
-        (gsd,) = ctx.saved_tensors
-        g = _unit_or_scaled(gl, gsd)
-        return g[0], g[1], None, None, None, (gl.reshape(ctx.reg_shape) if ctx.reg_shape is not None else None)
+        return _tail_backward(ctx, gl)
 
 
 def ign_crps_loss(sbm_out, dnn_out, target, edges, beta=1.0, reg=None):

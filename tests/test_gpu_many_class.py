@@ -153,8 +153,12 @@ def _loss64(s, d, y, beta, reg):
     return loss.detach(), out.detach(), eta.detach(), s.grad, d.grad
 
 
-@pytest.mark.parametrize("N", [17, 39, 100])
-@pytest.mark.parametrize("B", [5, 256, 1500])
+# the wave-per-row kernel's chunk edges at B = 17 (one wave takes a second row): N = 64 is the last full single chunk, 65 puts one
+# lane into a second chunk, 256 fills every chunk
+_TAIL_CASES = [(B, N) for B in (5, 256, 1500) for N in (17, 39, 100)] + [(17, 64), (17, 65), (17, 256)]
+
+
+@pytest.mark.parametrize("B,N", _TAIL_CASES)
 def test_loss_tail_vs_float64(N, B):
     dev = _dev()
     _lib()

@@ -265,7 +265,7 @@ def test_diversity_kernel_vs_torch():
         assert float((w.grad.cpu().double() - wd.grad).abs().max()) <= 1e-4 * scale + 1e-12, (K, C, L)
 
 
-@pytest.mark.parametrize("B,N,beta", [(256, 3, 1.0), (8, 4, 0.37), (700, 3, 0.0), (1, 2, 1.0)])
+@pytest.mark.parametrize("B,N,beta", [(256, 3, 1.0), (8, 4, 0.37), (700, 3, 0.0), (1, 2, 1.0), (257, 16, 0.37)])
 def test_fused_loss_tail_vs_torch(B, N, beta):
     """ops.ign_loss (gate + CE(mixture) + beta*CE(sbm) + both logit gradients in one launch) against the torch composition
     of IGN/exp/experiment_classification.py:320-329 in float64."""
@@ -290,6 +290,28 @@ def test_fused_loss_tail_vs_torch(B, N, beta):
     rel = lambda a, b: float((a.detach().double().cpu() - b.detach()).abs().max() / b.detach().abs().max().clamp_min(1e-12))
     assert rel(out, out_r) < 1e-5 and rel(eta, eta_r) < 1e-5
     assert rel(sg.grad, sd.grad) < 1e-4 and rel(dg.grad, dd.grad) < 1e-4
+
+
+@pytest.mark.parametrize("B,N", [(1, 2), (257, 16), (300, 5)])
+def test_fused_loss_tail_mixture_is_the_gate_kernels(B, N):
+    """Up to 16 classes the fused tail's mixture and eta are bitwise ops.gini_gate's (one gate rule in csrc/ign_loss.hip), and two
+    calls agree bitwise in the loss and both gradients.  B = 257 gives thread 0 a second row, N = 16 fills the register row."""
+    dev = _dev()
+    import speech_imagery_eeg_amd  # noqa
+    from ign_hip import ops
+    g = torch.Generator().manual_seed(B * 31 + N)
+    s, d = (torch.randn(B, N, generator=g) * 2).to(dev), (torch.randn(B, N, generator=g) * 2).to(dev)
+    y = torch.randint(0, N, (B,), generator=g).to(dev)
+    res = []
+    for _ in range(2):
+        sv, dv = s.clone().requires_grad_(True), d.clone().requires_grad_(True)
+        loss, out, eta = ops.ign_loss(sv, dv, y, 0.37)
+        loss.backward()
+        res.append((loss.detach(), out, eta, sv.grad, dv.grad))
+    mix, eta = ops.gini_gate(s, d)
+    assert torch.equal(res[0][1], mix) and torch.equal(res[0][2], eta)
+    for a, b in zip(*res):
+        assert torch.equal(a, b), "two calls differ"
 
 
 @pytest.mark.parametrize("cls,sbm_cls,dfunc", [("SBM", "linear", "euclidean"), ("SBM", "bilinear", "euclidean"),
