@@ -405,6 +405,36 @@ int ign_gather_flat(const void* const* src, const long long* off, const long lon
 int ign_adam_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, float lr,
                       float beta1, float beta2, float eps, int* step_dev, float* bc_dev, void* stream);
 
+/* Gradient clipping on the flat gradient buffer (torch.nn.utils.clip_grad_norm_, IGN/exp/experiment_classification.py:336-337).
+ * ign_grad_norm_clip: out2[0] = ||g||_2 over the n floats of g (the zero padding between parameter slots adds nothing),
+ * out2[1] = min(1, max_norm / (out2[0] + 1e-6)), the coefficient clip_grad_norm_ multiplies the gradients by.  One launch and no
+ * host synchronisation: every block sums the squares of a fixed contiguous slice of 4096 floats (16-byte loads, wave butterfly,
+ * waves in order through LDS) into one partial; the block that finishes last adds the partials in index order (in double).  No
+ * float atomics: the result is bitwise repeatable and independent of how the launch was scheduled.  Non-finite values get no
+ * special case -- an inf gradient gives the coefficient 0 (inf * 0 = NaN in that element), a NaN gradient a NaN coefficient, as
+ * in torch.  g and workspace 16-byte aligned.  workspace: ign_grad_norm_workspace_bytes(n) bytes, ZERO-FILLED ONCE before the
+ * first call (it holds an integer ticket counter that every call hands back at zero); calls that share a workspace must be
+ * ordered on one stream.                                                                                                      */
+size_t ign_grad_norm_workspace_bytes(long long n);
+int ign_grad_norm_clip(const float* g, long long n, float max_norm, float* out2, void* workspace, void* stream);
+
+/* ign_adam_step / ign_adam_step_dev reading grad[i] * coef_dev[0] (coef_dev = out2 + 1 of ign_grad_norm_clip): clipping folded
+ * into the optimizer, no extra pass over the gradients and no write to them.  coef_dev == NULL: exactly ign_adam_step /
+ * ign_adam_step_dev (same kernels, same bits).                                                                               */
+int ign_adam_step_clip(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, float lr,
+                       float beta1, float beta2, float eps, int step, const float* coef_dev, void* stream);
+int ign_adam_step_clip_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, float lr,
+                           float beta1, float beta2, float eps, int* step_dev, float* bc_dev, const float* coef_dev,
+                           void* stream);
+
+/* g[i] *= coef_dev[0] in place, i < n (g 16-byte aligned): for callers that want the gradients themselves clipped, the
+ * stand-alone clip_grad_norm_ contract.                                                                                      */
+int ign_scale_flat(float* g, long long n, const float* coef_dev, void* stream);
+
+/* ign_gather_flat that ADDS src[i] into flat + off[i] instead of overwriting: gradient accumulation over micro-batches in one
+ * launch per micro-step (one extra read of each slot) instead of one accumulate kernel per parameter.                        */
+int ign_gather_flat_acc(const void* const* src, const long long* off, const long long* n, int count, float* flat, void* stream);
+
 /* EEG-CNN block 1 without its (B,F1,C,T) intermediate (1 GB at B=256) -- see csrc/ign_eegcnn.hip for the algebra.
  * Replaces the BatchNorm-1 batch statistics of IGN/model/eegcnn.py:90-91 (block1_conv1 -> block1_bn1):
  *   y1[r,f,t] = sum_j w1[f,j] xpad[r, t+j]   (rows r = (b,c); 'same' zero padding, pad_left on the left)
@@ -707,7 +737,7 @@ int ign_bn_bwd_apply(const float* g, const float* y, const float* a, const float
 /* Per-kernel HIP-event timing (measurement only; off by default).  When enabled every kernel launch made by
  * this library is bracketed by hipEventRecord on the caller's stream.  ign_timing_read() waits for the recorded
  * events of `label` ("shp_fwd", "shp_bwd", "reduce_parts", "instnorm", "attn_fwd", "attn_bwd_dkdv", "attn_bwd_dq",
- * "attn_delta", "head_fwd", "head_bwd_x", "head_bwd_w", "adam",
+ * "attn_delta", "head_fwd", "head_bwd_x", "head_bwd_w", "adam", "grad_norm", "scale_flat", "gather_acc",
  * "conv1_sumsq_fwd", "conv1_sumsq_bwd", "dwconv1d", "dwconv1d_bwd_w"), and returns the accumulated
  * device milliseconds and launch count since the last enable.  Not for use under graph capture.             */
 int ign_timing_enable(int on);

@@ -24,6 +24,7 @@ import torch.nn.functional as F
 
 from data_provider.data_factory import data_provider
 from data_provider.device_prefetch import DevicePrefetcher, standardise_raw_batch
+from ign_hip import ddp as ign_ddp
 from ign_hip import ops as ign_ops
 from ign_hip.ddp import FlatAdam, FlatParamBucket
 from models.FullyConvNet import FullyConvNetwork
@@ -99,6 +100,8 @@ class Experiment(object):
             self.optimizer = FlatAdam(self.bucket, lr=self.args.lr)
         else:
             self.optimizer = torch.optim.Adam(self.model.parameters(), lr=self.args.lr)
+        # clipping and accumulation run on the flat buffer (ign_grad_norm_clip, ign_gather_flat_acc) when the optimizer is FlatAdam
+        self._flat_step = isinstance(self.optimizer, ign_ddp.FlatAdam)
         self.scheduler = torch.optim.lr_scheduler.CosineAnnealingWarmRestarts(self.optimizer, T_0=self.args.train_epochs)
         self.checkpoint_dir = "./checkpoints/{}/{}/dnn-{}_seed-{}_k-{}_div-{}_reg-{}_eps-{}_beta-{}_dfunc-{}_cls-{}".format(
             args.model, args.dataset, args.dnn_type, args.seed, args.num_shapelet, args.lambda_div, args.lambda_reg,
@@ -212,12 +215,22 @@ class Experiment(object):
             if a.gradient_accumulation_steps > 1:
                 loss = loss / a.gradient_accumulation_steps
             ign_ops.backward(loss)                 # = loss.backward() (a cached unit root gradient on the GPU)
-            if train_step % a.gradient_accumulation_steps == 0:
+            micro = train_step % a.gradient_accumulation_steps
+            if self._flat_step and a.gradient_accumulation_steps > 1:
+                # the micro-batch gradients are summed in the flat buffer: the first micro-step of a cycle overwrites the slots,
+                # the later ones add (one launch each); p.grad is None again for the next backward pass
+                self.bucket.gather(accumulate=micro != 1)
+                if micro:
+                    self.bucket.zero_grad()
+            if micro == 0:
                 if self.bucket is not None:
                     self.bucket.allreduce()
-                if a.gradient_clip > 0:
-                    nn.utils.clip_grad_norm_(self.model.parameters(), max_norm=a.gradient_clip)
-                self.optimizer.step()
+                if self._flat_step:
+                    self.optimizer.step(max_norm=a.gradient_clip if a.gradient_clip > 0 else None)
+                else:
+                    if a.gradient_clip > 0:
+                        nn.utils.clip_grad_norm_(self.model.parameters(), max_norm=a.gradient_clip)
+                    self.optimizer.step()
                 if a.pos_weight:
                     self.model.step()
                 if self.bucket is not None:
@@ -245,8 +258,7 @@ class Experiment(object):
     def _graph_eligible(self, amp):
         a = self.args
         return (getattr(a, 'hipgraph', False) and self.device.type == 'cuda' and not amp and not self.distributed
-                and a.gradient_accumulation_steps == 1 and a.gradient_clip <= 0 and a.model in ('InterpGN', 'SBM', 'LTS')
-                and isinstance(self.optimizer, FlatAdam) and not self._attention_dropout_active())
+                and a.model in ('InterpGN', 'SBM', 'LTS') and self._flat_step and not self._attention_dropout_active())
 
     def _attention_dropout_active(self):
         """Attention dropout draws a fresh seed per call on the host; a captured graph would replay one mask (ops.attention refuses
@@ -267,32 +279,59 @@ class Experiment(object):
         if not self.optimizer.capturable:          # the step count moves to the device so that a captured launch sequence stays valid
             self.optimizer.make_capturable()
 
-        def step_fn(batch_x, label, padding_mask):
+        # Gradient accumulation over K micro-batches: at most TWO graphs per key.  "micro" = forward, loss / K, backward and an
+        # ADDING gather (ign_gather_flat_acc); "close" = the same, then all-reduce, gradient norm, clipped Adam, clamp -- and one
+        # fill of the flat buffer at its end, so that every micro-step of every cycle, the first included, adds into zeros and
+        # needs no overwriting variant of its own (0 + g = g: the sums are those of the eager loop, which overwrites in the
+        # first micro-step).  K = 1 captures only "close", with the overwriting gather and no fill: the step as it always was.
+        # max_norm is a kernel argument, constant over a run; the coefficient stays on the device, so a replay clips by the norm
+        # of ITS gradients.
+        K = a.gradient_accumulation_steps
+        max_norm = a.gradient_clip if a.gradient_clip > 0 else None
+
+        def step_fn(batch_x, label, padding_mask, close=True):
             logits, info = self._forward(batch_x, padding_mask)
             loss = self._train_loss(logits, info, label, beta, False)
+            if K > 1:
+                loss = loss / K
             ign_ops.backward(loss)
+            if K > 1:
+                self.bucket.gather(accumulate=True)
+                if not close:
+                    return loss.detach()
             self.bucket.allreduce()
-            self.optimizer.step()
+            self.optimizer.step(max_norm=max_norm)
             if a.pos_weight:
                 self.model.step()
             self.bucket.zero_grad()
+            if K > 1:
+                self.bucket.clear()
             return loss.detach()
 
+        def micro_fn(batch_x, label, padding_mask):
+            return step_fn(batch_x, label, padding_mask, close=False)
+
+        if K > 1 and not getattr(self, '_graph_acc_primed', False):
+            self.bucket.clear()                    # every micro-step adds: the first cycle starts from zeros as well
+            self._graph_acc_primed = True
         losses, graphed, key = [], getattr(self, '_graphed', None), (beta, lr, a.batch_size)
         for batch_x, label, padding_mask in self.train_loader:
             train_step += 1
             batch_x, label, padding_mask = self._to_device(batch_x, label, padding_mask)
+            kind, fn = ('close', step_fn) if train_step % K == 0 else ('micro', micro_fn)
             if batch_x.shape[0] != a.batch_size:                  # ragged last batch: eager
-                losses.append(step_fn(batch_x, label, padding_mask).clone())
+                losses.append(fn(batch_x, label, padding_mask).clone())
                 continue
             if graphed is None or graphed[0] != key:
+                graphed = self._graphed = (key, {})
+            if kind not in graphed[1]:
                 # beta and lr are kernel ARGUMENTS: a new value needs a new capture.  This batch runs eagerly (which also performs
                 # every first-call initialisation outside the capture); the capture that follows records the launch sequence
                 # without executing it, so the parameter trajectory is exactly the eager one
-                losses.append(step_fn(batch_x, label, padding_mask).clone())
-                graphed = self._graphed = (key, GraphedTrainStep(step_fn, (batch_x, label, padding_mask), warmup=0))
+                losses.append(fn(batch_x, label, padding_mask).clone())
+                graphed[1][kind] = GraphedTrainStep(fn, (batch_x, label, padding_mask), warmup=0)
                 continue
-            losses.append(graphed[1](batch_x, label, padding_mask).clone())
+            losses.append(graphed[1][kind](batch_x, label, padding_mask).clone())
         return losses, train_step
 
     def train(self):

@@ -66,6 +66,12 @@ SIGNATURES = {
     "ign_adam_step": (ci, [vp, vp, vp, vp, ll, cf, cf, cf, cf, ci, vp]),
     "ign_gather_flat": (ci, [vp, vp, vp, ci, vp, vp]),
     "ign_adam_step_dev": (ci, [vp, vp, vp, vp, ll, cf, cf, cf, cf, vp, vp, vp]),
+    "ign_grad_norm_workspace_bytes": (sz, [ll]),
+    "ign_grad_norm_clip": (ci, [vp, ll, cf, vp, vp, vp]),
+    "ign_adam_step_clip": (ci, [vp, vp, vp, vp, ll, cf, cf, cf, cf, ci, vp, vp]),
+    "ign_adam_step_clip_dev": (ci, [vp, vp, vp, vp, ll, cf, cf, cf, cf, vp, vp, vp, vp]),
+    "ign_scale_flat": (ci, [vp, ll, vp, vp]),
+    "ign_gather_flat_acc": (ci, [vp, vp, vp, ci, vp, vp]),
     "ign_conv1_sumsq_workspace_bytes": (sz, [ci, ci, ci]),
     "ign_conv1_sumsq_fwd": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]),
     "ign_conv1_sumsq_bwd": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]),

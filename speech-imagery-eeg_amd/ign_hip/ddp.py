@@ -41,6 +41,8 @@ class FlatParamBucket:
         # slots that may hold something other than zeros (`gather`): the buffer starts zero-filled, and a parameter that gets no
         # gradient step after step (three of the IGN model's) needs no fill kernel per step to keep its slot at zero
         self._dirty = [False] * len(self.params)
+        self._held = False          # the slots hold a running sum of micro-batch gradients (`gather(accumulate=True)`)
+        self._norm = None           # (out2, workspace) of ign_grad_norm_clip (`grad_norm`)
         self.module = module
 
     @property
@@ -54,7 +56,7 @@ class FlatParamBucket:
         for t in list(self.module.parameters()) + list(self.module.buffers()):
             dist.broadcast(t.data, src=src, group=self.group)
 
-    def gather(self):
+    def gather(self, accumulate=False):
         """Bring the gradients autograd produced into the flat buffer.
 
         On the GPU ``zero_grad`` leaves ``p.grad = None``, so autograd hands every parameter a fresh gradient tensor (no
@@ -62,26 +64,42 @@ class FlatParamBucket:
         at the slot, so clipping, the all-reduce and the optimizer see one buffer.  Parameters whose ``.grad`` already is
         the slot view (CPU path, or a second call) are left alone; parameters without a gradient get zeros -- by a fill only when
         their slot was written since it was last zero (the buffer starts zero-filled; scaling by clipping or averaging keeps
-        zeros zero)."""
+        zeros zero).
+
+        ``accumulate=True`` (gradient accumulation, a later micro-step of a cycle): one ``ign_gather_flat_acc`` launch ADDS the
+        fresh gradients into their slots and ``p.grad`` goes back to None, so autograd never runs its per-parameter accumulate
+        kernels; a parameter without a gradient in this micro-step keeps what its slot holds.  The slots then hold the running sum
+        (``_held``): the next plain ``gather()`` -- the one ``allreduce`` / ``FlatAdam.step`` make -- finds ``p.grad is None``, keeps
+        the slot instead of zeroing it and points ``p.grad`` at it."""
         todo = []
         for i, (p, off, view) in enumerate(zip(self.params, self.offsets, self.views)):
             g = p.grad
             if g is view:
                 self._dirty[i] = True                    # written in place by autograd (CPU path) or by the caller
                 continue
+            if accumulate:
+                if g is not None:
+                    todo.append((g.contiguous(), off, view))
+                    self._dirty[i] = True
+                    p.grad = None
+                continue
             if g is None:
-                if self._dirty[i]:
+                if self._dirty[i] and not self._held:
                     view.zero_()
                     self._dirty[i] = False
             else:
                 todo.append((g.contiguous(), off, view))
                 self._dirty[i] = True
             p.grad = view
+        held, self._held = self._held, bool(accumulate)
         if not todo:
             return
         if not self.flat_grad.is_cuda:
             for g, _, view in todo:
-                view.copy_(g)
+                if accumulate or held:
+                    view.add_(g)
+                else:
+                    view.copy_(g)
             return
         import ctypes
         from . import _lib
@@ -89,8 +107,55 @@ class FlatParamBucket:
         src = (ctypes.c_void_p * n)(*[g.data_ptr() for g, _, _ in todo])
         off = (ctypes.c_longlong * n)(*[o for _, o, _ in todo])
         cnt = (ctypes.c_longlong * n)(*[g.numel() for g, _, _ in todo])
+        if accumulate or held:      # held: fresh gradients on top of a running sum (a cycle closed by a plain gather()) add as well
+            _lib.check(_lib.lib().ign_gather_flat_acc(src, off, cnt, n, ctypes.c_void_p(self.flat_grad.data_ptr()),
+                                                      _lib.stream()), "ign_gather_flat_acc")
+            return
         _lib.check(_lib.lib().ign_gather_flat(src, off, cnt, n, ctypes.c_void_p(self.flat_grad.data_ptr()),
                                               _lib.stream()), "ign_gather_flat")
+
+    def clear(self):
+        """Zero the whole buffer (one fill) and forget every running sum: the state a new bucket starts in."""
+        self.flat_grad.zero_()
+        self._dirty = [False] * len(self.params)
+        self._held = False
+
+    def grad_norm(self, max_norm):
+        """-> (2,) device tensor [||g||_2 over the flat buffer, min(1, max_norm / (norm + 1e-6))] of the gathered gradients: one
+        ``ign_grad_norm_clip`` launch, no host synchronisation.  The tensor is the bucket's own and is rewritten by the next call."""
+        from . import _lib
+        if not self.flat_grad.is_cuda:
+            raise _lib.IgnError("FlatParamBucket.grad_norm runs on the GPU only")
+        self.gather()
+        return self._norm_into(self._norm_buffers()[0], max_norm)
+
+    def _norm_buffers(self):
+        """(out2, workspace) of ign_grad_norm_clip, allocated once; the workspace starts zero-filled (its ticket counter)."""
+        if self._norm is None:
+            from . import _lib
+            n = self.flat_grad.numel()
+            nbytes = int(_lib.lib().ign_grad_norm_workspace_bytes(n))
+            self._norm = (torch.zeros(2, device=self.flat_grad.device, dtype=torch.float32),
+                          torch.zeros((nbytes + 3) // 4, device=self.flat_grad.device, dtype=torch.float32))
+        return self._norm
+
+    def _norm_into(self, out2, max_norm):
+        import ctypes
+        from . import _lib
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+        _lib.check(_lib.lib().ign_grad_norm_clip(ptr(self.flat_grad), self.flat_grad.numel(), float(max_norm), ptr(out2),
+                                                 ptr(self._norm_buffers()[1]), _lib.stream()), "ign_grad_norm_clip")
+        return out2
+
+    def clip_(self, max_norm):
+        """``clip_grad_norm_`` on the flat buffer: the norm launch plus one ``ign_scale_flat`` launch that multiplies the
+        gradients themselves by the coefficient -> the norm before clipping, a device scalar (no host synchronisation)."""
+        import ctypes
+        from . import _lib
+        out2 = self.grad_norm(max_norm)
+        _lib.check(_lib.lib().ign_scale_flat(ctypes.c_void_p(self.flat_grad.data_ptr()), self.flat_grad.numel(),
+                                             ctypes.c_void_p(out2.data_ptr() + 4), _lib.stream()), "ign_scale_flat")
+        return out2[0]
 
     def allreduce(self):
         """Average the gradients over ranks: one collective on the flat bucket."""
@@ -155,6 +220,9 @@ class FlatAdam(torch.optim.Optimizer):
         self.capturable = bool(capturable)
         self.step_dev = torch.zeros(1, device=self.flat_param.device, dtype=torch.int32) if capturable else None
         self.bc_dev = torch.zeros(2, device=self.flat_param.device, dtype=torch.float32) if capturable else None
+        # step(max_norm): [gradient norm, clip coefficient] of the last clipped step, on the device (allocated at the first one)
+        self.norm_dev = None
+        self.last_grad_norm = None
 
     def make_capturable(self):
         """Move the step count to the device (ign_adam_step_dev) so that the optimizer step can be captured into a hipGraph;
@@ -166,7 +234,10 @@ class FlatAdam(torch.optim.Optimizer):
             self.capturable = True
 
     @torch.no_grad()
-    def step(self, closure=None):
+    def step(self, closure=None, max_norm=None):
+        """One Adam step.  ``max_norm`` > 0: gradient clipping as ``clip_grad_norm_(parameters, max_norm)`` in front of the step --
+        one ``ign_grad_norm_clip`` launch leaves [norm, coefficient] in ``last_grad_norm`` / ``norm_dev`` on the device and the
+        ``_clip`` Adam entry point reads every gradient times that coefficient (the gradients themselves are not rewritten)."""
         import ctypes
         loss = closure() if closure is not None else None
         self.bucket.gather()
@@ -174,6 +245,23 @@ class FlatAdam(torch.optim.Optimizer):
         g = self.param_groups[0]
         ptr = lambda t: ctypes.c_void_p(t.data_ptr())
         self._lib.PARAM_GENERATION[0] += 1           # the kernel rewrites the parameters through raw pointers
+        if max_norm is not None and max_norm > 0:
+            if self.norm_dev is None:
+                self.norm_dev = torch.zeros(2, device=self.flat_param.device, dtype=torch.float32)
+                self.last_grad_norm = self.norm_dev[0]
+            self.bucket._norm_into(self.norm_dev, max_norm)
+            coef = ctypes.c_void_p(self.norm_dev.data_ptr() + 4)
+            if self.capturable:
+                self._lib.check(self._lib.lib().ign_adam_step_clip_dev(
+                    ptr(self.flat_param), ptr(self.bucket.flat_grad), ptr(self.exp_avg), ptr(self.exp_avg_sq),
+                    self.flat_param.numel(), g["lr"], g["betas"][0], g["betas"][1], g["eps"], ptr(self.step_dev), ptr(self.bc_dev),
+                    coef, self._lib.stream()), "ign_adam_step_clip_dev")
+                return loss
+            self._lib.check(self._lib.lib().ign_adam_step_clip(
+                ptr(self.flat_param), ptr(self.bucket.flat_grad), ptr(self.exp_avg), ptr(self.exp_avg_sq),
+                self.flat_param.numel(), g["lr"], g["betas"][0], g["betas"][1], g["eps"], self.step_count, coef,
+                self._lib.stream()), "ign_adam_step_clip")
+            return loss
         if self.capturable:
             self._lib.check(self._lib.lib().ign_adam_step_dev(
                 ptr(self.flat_param), ptr(self.bucket.flat_grad), ptr(self.exp_avg), ptr(self.exp_avg_sq),
