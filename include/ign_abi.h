@@ -392,7 +392,8 @@ int ign_sbm_bilinear_bwd(const float* u, const float* v, const float* w, const f
                          float* gv, float* gw, void* workspace, int B, int F, int N, void* stream);
 
 /* One Adam step over flat buffers (torch.optim.Adam semantics, no weight decay / amsgrad): replaces the per-tensor
- * optimizer.step() of IGN/exp/experiment_classification.py:338.  `step` is the 1-based step count.               */
+ * optimizer.step() of IGN/exp/experiment_classification.py:338.  `step` is the 1-based step count; all four buffers
+ * 16-byte aligned.                                                                                                    */
 int ign_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, float lr,
                   float beta1, float beta2, float eps, int step, void* stream);
 
@@ -401,7 +402,8 @@ int ign_adam_step(float* param, const float* grad, float* exp_avg, float* exp_av
 int ign_gather_flat(const void* const* src, const long long* off, const long long* n, int count, float* flat, void* stream);
 
 /* The same step with the step count kept on the device (*step_dev is incremented, bc_dev[2] receives the bias
- * corrections): nothing host-side changes between steps, so the launch sequence can be captured into a hipGraph.      */
+ * corrections): nothing host-side changes between steps, so the launch sequence can be captured into a hipGraph.  All
+ * four buffers 16-byte aligned.                                                                                       */
 int ign_adam_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, float lr,
                       float beta1, float beta2, float eps, int* step_dev, float* bc_dev, void* stream);
 
@@ -420,7 +422,7 @@ int ign_grad_norm_clip(const float* g, long long n, float max_norm, float* out2,
 
 /* ign_adam_step / ign_adam_step_dev reading grad[i] * coef_dev[0] (coef_dev = out2 + 1 of ign_grad_norm_clip): clipping folded
  * into the optimizer, no extra pass over the gradients and no write to them.  coef_dev == NULL: exactly ign_adam_step /
- * ign_adam_step_dev (same kernels, same bits).                                                                               */
+ * ign_adam_step_dev (same kernels, same bits).  Both: all four buffers 16-byte aligned.                                       */
 int ign_adam_step_clip(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, float lr,
                        float beta1, float beta2, float eps, int step, const float* coef_dev, void* stream);
 int ign_adam_step_clip_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, float lr,

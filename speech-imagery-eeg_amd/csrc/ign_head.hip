@@ -1,5 +1,5 @@
-// Expert-head GEMMs, the flat Adam update and the SBM regularisers: the small HBM-bound pieces of the training step.  (The gini
-// gate and the fused loss tails are in ign_loss.hip.)
+// Expert-head GEMMs and the two SBM regularisers: the small HBM-bound pieces of the training step.  (The gini gate and the fused
+// loss tails are in ign_loss.hip; Adam, the gradient gather and clipping on the flat buffers are in ign_optim.hip.)
 //
 //  * head GEMM  out[b,n] = sum_f X[b,f] W[n,f] (+ bias[n])  with N = number of classes (2..IGN_HEAD_NMAX = 256; above 16 in
 //    16-class chunks, one extra grid dimension, same launch count) -- "skinny":
@@ -7,8 +7,6 @@
 //    IGN/model/FullyConvNet.py:50,58.  N is far too small for an MFMA tile to pay (a 32x32 tile would be >90 % padding)
 //    and the op moves 4*(B*F + N*F) bytes for 2*B*F*N flops (intensity ~N/2 flop/byte): HBM/L2 bound, so it is a
 //    coalesced float4 streaming kernel with N accumulators per thread and a block reduction.
-//  * Adam       one launch over the flat parameter / gradient / moment buffers (torch.optim.Adam semantics,
-//    IGN/exp/experiment_classification.py:136,338).
 #include "ign_common.h"
 
 constexpr int HEAD_NMAX = 16;
@@ -199,163 +197,6 @@ __global__ void __launch_bounds__(256) head_bwd_xw_kernel(const float* __restric
     }
 }
 
-// ------------------------------------------------------------------------------------------------ Adam
-// CLIP: the gradient is read as g * coef[0], the clip coefficient ign_grad_norm_clip left on the device -- clipping costs no pass
-// over the gradients and no write to them.  The CLIP = false instantiations are the kernels as they were.
-template <bool CLIP>
-__global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                   float* __restrict__ v, long long n, float lr, float b1, float b2,
-                                                   float eps, float bc1, float bc2_sqrt, const float* __restrict__ coef) {
-    const long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (i >= n) return;
-    const float step = lr / bc1;
-    const float c = CLIP ? coef[0] : 1.f;
-    if (i + 3 < n) {
-        float4 pv = *reinterpret_cast<float4*>(p + i);
-        float4 gv = *reinterpret_cast<const float4*>(g + i);
-        if (CLIP) { gv.x *= c; gv.y *= c; gv.z *= c; gv.w *= c; }
-        float4 mv = *reinterpret_cast<float4*>(m + i);
-        float4 vv = *reinterpret_cast<float4*>(v + i);
-#define ADAM1(P, G, M, V)                                   \
-        M = b1 * M + (1.f - b1) * G;                         \
-        V = b2 * V + (1.f - b2) * G * G;                     \
-        P -= step * M / (sqrtf(V) / bc2_sqrt + eps);
-        ADAM1(pv.x, gv.x, mv.x, vv.x) ADAM1(pv.y, gv.y, mv.y, vv.y) ADAM1(pv.z, gv.z, mv.z, vv.z) ADAM1(pv.w, gv.w, mv.w, vv.w)
-        *reinterpret_cast<float4*>(p + i) = pv;
-        *reinterpret_cast<float4*>(m + i) = mv;
-        *reinterpret_cast<float4*>(v + i) = vv;
-    } else {
-        for (long long j = i; j < n; ++j) {
-            float pv = p[j], gv = CLIP ? g[j] * c : g[j], mv = m[j], vv = v[j];
-            ADAM1(pv, gv, mv, vv)
-            p[j] = pv; m[j] = mv; v[j] = vv;
-        }
-    }
-}
-
-// Gather per-parameter gradient tensors into the flat bucket in ONE launch (instead of one accumulate kernel per parameter):
-// blockIdx.y = table entry, blockIdx.x strides over its elements.
-constexpr int GATHER_MAX = 96;
-struct GatherTable {
-    const float* src[GATHER_MAX];
-    long long off[GATHER_MAX];
-    long long n[GATHER_MAX];
-};
-// ACC: add into the slots (gradient accumulation over micro-batches: the extra cost is one read of each slot).
-template <bool ACC>
-__global__ void __launch_bounds__(256) gather_flat_kernel(const GatherTable t, float* __restrict__ flat) {
-    const int e = blockIdx.y;
-    const float* __restrict__ src = t.src[e];
-    float* __restrict__ dst = flat + t.off[e];
-    const long long n = t.n[e];
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
-        dst[i] = ACC ? dst[i] + src[i] : src[i];
-}
-
-// Graph-capturable Adam: the step count lives on the device, so a captured launch sequence stays valid when replayed.
-__global__ void adam_tick_kernel(int* __restrict__ step_dev, float* __restrict__ bc_dev, float b1, float b2) {
-    const int step = ++(*step_dev);
-    bc_dev[0] = (float)(1.0 - pow((double)b1, (double)step));
-    bc_dev[1] = (float)sqrt(1.0 - pow((double)b2, (double)step));
-}
-
-template <bool CLIP>
-__global__ void __launch_bounds__(256) adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                       float* __restrict__ v, long long n, float lr, float b1, float b2,
-                                                       float eps, const float* __restrict__ bc_dev, const float* __restrict__ coef) {
-    const long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (i >= n) return;
-    const float bc1 = bc_dev[0], bc2_sqrt = bc_dev[1];
-    const float step = lr / bc1;
-    const float c = CLIP ? coef[0] : 1.f;
-    for (long long j = i; j < min(n, i + 4); ++j) {
-        float pv = p[j], gv = CLIP ? g[j] * c : g[j], mv = m[j], vv = v[j];
-        ADAM1(pv, gv, mv, vv)
-        p[j] = pv; m[j] = mv; v[j] = vv;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ gradient norm / clipping
-// Global L2 norm of the flat gradient buffer and the clip_grad_norm_ coefficient, in ONE launch with a fixed summation order:
-//   stage 1  block b sums the squares of the contiguous slice [b*NORM_SLICE, (b+1)*NORM_SLICE): four 16-byte loads per lane (all
-//            issued before the first use), a lane sum in load order, a butterfly over the wave, the four wave sums through LDS in
-//            wave order -> part[b].  A pure HBM read: 20 VGPRs, so every CU holds its 8 blocks and the grid (256 blocks at 4 MB,
-//            2048 at 32 MB) keeps all of them busy.
-//   stage 2  the block that takes the last ticket of an integer counter (agent-scope release before the ticket, acquire after it)
-//            adds the partials: lane t the contiguous run [t*per, (t+1)*per) in index order, in double, then the same butterfly /
-//            LDS order.  WHICH block does this depends on scheduling; WHAT it computes does not -- no float atomics, bitwise
-//            repeatable.  It hands the counter back at zero, so the workspace is zero-filled once, not per call.
-// Non-finite values get no special case: an inf makes the norm inf and the coefficient 0 (inf * 0 = NaN in that element, like
-// torch's in-place multiply), a NaN makes both NaN (`c > 1 ? 1 : c` keeps a NaN, as torch.clamp(max=1) does).
-constexpr int NORM_SLICE = 4096;                 // floats per stage-1 block = 256 lanes x 4 loads x 4 floats
-constexpr int NORM_HDR = 4;                      // floats in front of the partials: [0] = the ticket counter, 16-byte padding
-__global__ void __launch_bounds__(256) grad_norm_kernel(const float* __restrict__ g, long long n, float max_norm,
-                                                        float* __restrict__ out2, float* __restrict__ ws, int nparts) {
-    __shared__ float red[4];
-    __shared__ double red2[4];
-    __shared__ int last;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long base = (long long)blockIdx.x * NORM_SLICE;
-    const long long end = min(n, base + NORM_SLICE);
-    float4 x[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const long long i = base + (long long)(k * 256 + tid) * 4;
-        x[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (i + 3 < end) x[k] = *reinterpret_cast<const float4*>(g + i);
-        else {                                   // ragged tail of the buffer: zeros add nothing
-            if (i < end) x[k].x = g[i];
-            if (i + 1 < end) x[k].y = g[i + 1];
-            if (i + 2 < end) x[k].z = g[i + 2];
-        }
-    }
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) s += (x[k].x * x[k].x + x[k].y * x[k].y) + (x[k].z * x[k].z + x[k].w * x[k].w);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if (lane == 0) red[wave] = s;
-    __syncthreads();
-    unsigned int* ticket = reinterpret_cast<unsigned int*>(ws);
-    float* part = ws + NORM_HDR;
-    if (tid == 0) {
-        __hip_atomic_store(part + blockIdx.x, ((red[0] + red[1]) + red[2]) + red[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __threadfence();                         // release: the partial is visible device-wide before the ticket is drawn
-        last = atomicAdd(ticket, 1u) == (unsigned int)(nparts - 1);
-    }
-    __syncthreads();
-    if (!last) return;
-    __threadfence();                             // acquire: every other block's partial
-    const int per = (nparts + 255) / 256;
-    double t = 0.0;
-    for (int j = tid * per; j < min(nparts, (tid + 1) * per); ++j)
-        t += (double)__hip_atomic_load(part + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
-    if (lane == 0) red2[wave] = t;
-    __syncthreads();
-    if (tid == 0) {
-        const float norm = (float)sqrt(((red2[0] + red2[1]) + red2[2]) + red2[3]);
-        const float c = max_norm / (norm + 1e-6f);
-        out2[0] = norm;
-        out2[1] = c > 1.f ? 1.f : c;
-        __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // ready for the next call on this stream
-    }
-}
-
-__global__ void __launch_bounds__(256) scale_flat_kernel(float* __restrict__ g, long long n, const float* __restrict__ coef) {
-    const long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (i >= n) return;
-    const float c = coef[0];
-    if (i + 3 < n) {
-        float4 v = *reinterpret_cast<float4*>(g + i);
-        v.x *= c; v.y *= c; v.z *= c; v.w *= c;
-        *reinterpret_cast<float4*>(g + i) = v;
-    } else {
-        for (long long j = i; j < n; ++j) g[j] *= c;
-    }
-}
-
 // ------------------------------------------------------------------------------------------------ C ABI
 extern "C" int ign_head_fwd(const float* X, const float* W, const float* bias, float* out, int B, int F, int N,
                             long long ldx, void* stream) {
@@ -431,145 +272,6 @@ extern "C" int ign_head_bwd_acc(const float* g, const float* X, const float* W, 
         if ((rc = ign_check_launch("head_bwd_w_kernel"))) return rc;
     }
     return 0;
-}
-
-static int adam_step(const char* who, float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2,
-                     float eps, int step, const float* coef_dev, void* stream) {
-    if (!p || !g || !m || !v || n <= 0 || step <= 0) {
-        ign_set_error("%s: null pointer, n <= 0 or step <= 0", who);
-        return IGN_E_ARG;
-    }
-    if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) {
-        ign_set_error("%s: buffers must be 16-byte aligned", who);
-        return IGN_E_ARG;
-    }
-    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-    IgnScopedTimer tm("adam", (hipStream_t)stream);
-    const long long blocks = (n / 4 + 256) / 256;
-    if (coef_dev)
-        hipLaunchKernelGGL(adam_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1,
-                           beta2, eps, (float)bc1, (float)sqrt(bc2), coef_dev);
-    else
-        hipLaunchKernelGGL(adam_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1,
-                           beta2, eps, (float)bc1, (float)sqrt(bc2), coef_dev);
-    return ign_check_launch("adam_kernel");
-}
-
-extern "C" int ign_adam_step(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2,
-                             float eps, int step, void* stream) {
-    return adam_step("ign_adam_step", p, g, m, v, n, lr, beta1, beta2, eps, step, nullptr, stream);
-}
-
-extern "C" int ign_adam_step_clip(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2,
-                                  float eps, int step, const float* coef_dev, void* stream) {
-    return adam_step("ign_adam_step_clip", p, g, m, v, n, lr, beta1, beta2, eps, step, coef_dev, stream);
-}
-
-static int gather_flat(const char* who, bool acc, const void* const* src, const long long* off, const long long* n, int count,
-                       float* flat, void* stream) {
-    if (!src || !off || !n || !flat || count < 0) {
-        ign_set_error("%s: null pointer or negative count", who);
-        return IGN_E_ARG;
-    }
-    for (int base = 0; base < count; base += GATHER_MAX) {
-        GatherTable t;
-        const int m = count - base < GATHER_MAX ? count - base : GATHER_MAX;
-        long long big = 1;
-        for (int i = 0; i < m; ++i) {
-            t.src[i] = (const float*)src[base + i]; t.off[i] = off[base + i]; t.n[i] = n[base + i];
-            if (!t.src[i] || t.n[i] < 0) { ign_set_error("%s: entry %d is null / negative", who, base + i); return IGN_E_ARG; }
-            if (t.n[i] > big) big = t.n[i];
-        }
-        const long long bx = (big + 256 * 8 - 1) / (256 * 8);            // ~8 elements per thread for the largest entry
-        const dim3 grid((unsigned)(bx < 1 ? 1 : (bx > 1024 ? 1024 : bx)), (unsigned)m);
-        if (acc) {
-            IgnScopedTimer tm("gather_acc", (hipStream_t)stream);
-            hipLaunchKernelGGL(gather_flat_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, t, flat);
-        } else {
-            hipLaunchKernelGGL(gather_flat_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, t, flat);
-        }
-        int rc;
-        if ((rc = ign_check_launch("gather_flat_kernel"))) return rc;
-    }
-    return 0;
-}
-
-extern "C" int ign_gather_flat(const void* const* src, const long long* off, const long long* n, int count, float* flat,
-                               void* stream) {
-    return gather_flat("ign_gather_flat", false, src, off, n, count, flat, stream);
-}
-
-extern "C" int ign_gather_flat_acc(const void* const* src, const long long* off, const long long* n, int count, float* flat,
-                                   void* stream) {
-    return gather_flat("ign_gather_flat_acc", true, src, off, n, count, flat, stream);
-}
-
-static int adam_step_dev(const char* who, float* p, const float* g, float* m, float* v, long long n, float lr, float beta1,
-                         float beta2, float eps, int* step_dev, float* bc_dev, const float* coef_dev, void* stream) {
-    if (!p || !g || !m || !v || !step_dev || !bc_dev || n <= 0) {
-        ign_set_error("%s: null pointer or n <= 0", who);
-        return IGN_E_ARG;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, s, step_dev, bc_dev, beta1, beta2);
-    int rc;
-    if ((rc = ign_check_launch("adam_tick_kernel"))) return rc;
-    IgnScopedTimer tm("adam", s);
-    const long long blocks = (n / 4 + 256) / 256;
-    if (coef_dev)
-        hipLaunchKernelGGL(adam_dev_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, p, g, m, v, n, lr, beta1, beta2, eps, bc_dev,
-                           coef_dev);
-    else
-        hipLaunchKernelGGL(adam_dev_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, p, g, m, v, n, lr, beta1, beta2, eps, bc_dev,
-                           coef_dev);
-    return ign_check_launch("adam_dev_kernel");
-}
-
-extern "C" int ign_adam_step_dev(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2,
-                                 float eps, int* step_dev, float* bc_dev, void* stream) {
-    return adam_step_dev("ign_adam_step_dev", p, g, m, v, n, lr, beta1, beta2, eps, step_dev, bc_dev, nullptr, stream);
-}
-
-extern "C" int ign_adam_step_clip_dev(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2,
-                                      float eps, int* step_dev, float* bc_dev, const float* coef_dev, void* stream) {
-    return adam_step_dev("ign_adam_step_clip_dev", p, g, m, v, n, lr, beta1, beta2, eps, step_dev, bc_dev, coef_dev, stream);
-}
-
-extern "C" size_t ign_grad_norm_workspace_bytes(long long n) {
-    if (n <= 0) return 0;
-    return (size_t)(NORM_HDR + (n + NORM_SLICE - 1) / NORM_SLICE) * sizeof(float);
-}
-
-extern "C" int ign_grad_norm_clip(const float* g, long long n, float max_norm, float* out2, void* workspace, void* stream) {
-    if (!g || !out2 || !workspace || n <= 0) {
-        ign_set_error("ign_grad_norm_clip: null pointer or n <= 0");
-        return IGN_E_ARG;
-    }
-    if (((uintptr_t)g | (uintptr_t)workspace) & 15) {
-        ign_set_error("ign_grad_norm_clip: g and workspace must be 16-byte aligned");
-        return IGN_E_ARG;
-    }
-    const long long nparts = (n + NORM_SLICE - 1) / NORM_SLICE;
-    if (nparts > 0x7fffffffLL) { ign_set_error("ign_grad_norm_clip: n=%lld too large", n); return IGN_E_TOOBIG; }
-    IgnScopedTimer tm("grad_norm", (hipStream_t)stream);
-    hipLaunchKernelGGL(grad_norm_kernel, dim3((unsigned)nparts), dim3(256), 0, (hipStream_t)stream, g, n, max_norm, out2,
-                       (float*)workspace, (int)nparts);
-    return ign_check_launch("grad_norm_kernel");
-}
-
-extern "C" int ign_scale_flat(float* g, long long n, const float* coef_dev, void* stream) {
-    if (!g || !coef_dev || n <= 0) {
-        ign_set_error("ign_scale_flat: null pointer or n <= 0");
-        return IGN_E_ARG;
-    }
-    if ((uintptr_t)g & 15) {
-        ign_set_error("ign_scale_flat: g must be 16-byte aligned");
-        return IGN_E_ARG;
-    }
-    IgnScopedTimer tm("scale_flat", (hipStream_t)stream);
-    const long long blocks = (n / 4 + 256) / 256;
-    hipLaunchKernelGGL(scale_flat_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g, n, coef_dev);
-    return ign_check_launch("scale_flat_kernel");
 }
 
 // ------------------------------------------------------------------------------------------------ shapelet diversity

@@ -223,22 +223,29 @@ class Experiment(object):
                 if micro:
                     self.bucket.zero_grad()
             if micro == 0:
-                if self.bucket is not None:
-                    self.bucket.allreduce()
-                if self._flat_step:
-                    self.optimizer.step(max_norm=a.gradient_clip if a.gradient_clip > 0 else None)
-                else:
-                    if a.gradient_clip > 0:
-                        nn.utils.clip_grad_norm_(self.model.parameters(), max_norm=a.gradient_clip)
-                    self.optimizer.step()
-                if a.pos_weight:
-                    self.model.step()
-                if self.bucket is not None:
-                    self.bucket.zero_grad()
-                else:
-                    self.optimizer.zero_grad()
+                self._optimizer_step()
             losses.append(loss.detach())
         return losses, train_step
+
+    def _optimizer_step(self):
+        """The tail of an optimizer step, eager or captured (IGN/exp/experiment_classification.py:335-341): all-reduce, clipped Adam,
+        clamp, zero_grad."""
+        a = self.args
+        max_norm = a.gradient_clip if a.gradient_clip > 0 else None
+        if self.bucket is not None:
+            self.bucket.allreduce()
+        if self._flat_step:
+            self.optimizer.step(max_norm=max_norm)
+        else:
+            if max_norm is not None:
+                nn.utils.clip_grad_norm_(self.model.parameters(), max_norm=max_norm)
+            self.optimizer.step()
+        if a.pos_weight:
+            self.model.step()
+        if self.bucket is not None:
+            self.bucket.zero_grad()
+        else:
+            self.optimizer.zero_grad()
 
     def _train_loss(self, logits, info, label, beta, amp):
         """The training loss of one step (IGN/exp/experiment_classification.py:319-329); `beta` weighs InterpGN's SBM term."""
@@ -287,7 +294,6 @@ class Experiment(object):
         # max_norm is a kernel argument, constant over a run; the coefficient stays on the device, so a replay clips by the norm
         # of ITS gradients.
         K = a.gradient_accumulation_steps
-        max_norm = a.gradient_clip if a.gradient_clip > 0 else None
 
         def step_fn(batch_x, label, padding_mask, close=True):
             logits, info = self._forward(batch_x, padding_mask)
@@ -299,11 +305,7 @@ class Experiment(object):
                 self.bucket.gather(accumulate=True)
                 if not close:
                     return loss.detach()
-            self.bucket.allreduce()
-            self.optimizer.step(max_norm=max_norm)
-            if a.pos_weight:
-                self.model.step()
-            self.bucket.zero_grad()
+            self._optimizer_step()
             if K > 1:
                 self.bucket.clear()
             return loss.detach()

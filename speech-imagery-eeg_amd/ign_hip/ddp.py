@@ -8,8 +8,16 @@ over ranks with a single ``all_reduce`` (4.27 MB for IGN-default: a latency-boun
 instead of one per tensor) and divided by the world size.  BatchNorm statistics stay per-rank, like DataParallel.
 Device-agnostic on purpose: the gloo/CPU tests in tests/test_ddp_cpu.py run the same code.
 """
+import ctypes
+
 import torch
 import torch.distributed as dist
+
+from . import _lib
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr())
 
 
 class FlatParamBucket:
@@ -101,18 +109,13 @@ class FlatParamBucket:
                 else:
                     view.copy_(g)
             return
-        import ctypes
-        from . import _lib
         n = len(todo)
         src = (ctypes.c_void_p * n)(*[g.data_ptr() for g, _, _ in todo])
         off = (ctypes.c_longlong * n)(*[o for _, o, _ in todo])
         cnt = (ctypes.c_longlong * n)(*[g.numel() for g, _, _ in todo])
-        if accumulate or held:      # held: fresh gradients on top of a running sum (a cycle closed by a plain gather()) add as well
-            _lib.check(_lib.lib().ign_gather_flat_acc(src, off, cnt, n, ctypes.c_void_p(self.flat_grad.data_ptr()),
-                                                      _lib.stream()), "ign_gather_flat_acc")
-            return
-        _lib.check(_lib.lib().ign_gather_flat(src, off, cnt, n, ctypes.c_void_p(self.flat_grad.data_ptr()),
-                                              _lib.stream()), "ign_gather_flat")
+        # held: fresh gradients on top of a running sum (a cycle closed by a plain gather()) add as well
+        entry = "ign_gather_flat_acc" if accumulate or held else "ign_gather_flat"
+        _lib.check(getattr(_lib.lib(), entry)(src, off, cnt, n, _ptr(self.flat_grad), _lib.stream()), entry)
 
     def clear(self):
         """Zero the whole buffer (one fill) and forget every running sum: the state a new bucket starts in."""
@@ -123,7 +126,6 @@ class FlatParamBucket:
     def grad_norm(self, max_norm):
         """-> (2,) device tensor [||g||_2 over the flat buffer, min(1, max_norm / (norm + 1e-6))] of the gathered gradients: one
         ``ign_grad_norm_clip`` launch, no host synchronisation.  The tensor is the bucket's own and is rewritten by the next call."""
-        from . import _lib
         if not self.flat_grad.is_cuda:
             raise _lib.IgnError("FlatParamBucket.grad_norm runs on the GPU only")
         self.gather()
@@ -132,7 +134,6 @@ class FlatParamBucket:
     def _norm_buffers(self):
         """(out2, workspace) of ign_grad_norm_clip, allocated once; the workspace starts zero-filled (its ticket counter)."""
         if self._norm is None:
-            from . import _lib
             n = self.flat_grad.numel()
             nbytes = int(_lib.lib().ign_grad_norm_workspace_bytes(n))
             self._norm = (torch.zeros(2, device=self.flat_grad.device, dtype=torch.float32),
@@ -140,20 +141,15 @@ class FlatParamBucket:
         return self._norm
 
     def _norm_into(self, out2, max_norm):
-        import ctypes
-        from . import _lib
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr())
-        _lib.check(_lib.lib().ign_grad_norm_clip(ptr(self.flat_grad), self.flat_grad.numel(), float(max_norm), ptr(out2),
-                                                 ptr(self._norm_buffers()[1]), _lib.stream()), "ign_grad_norm_clip")
+        _lib.check(_lib.lib().ign_grad_norm_clip(_ptr(self.flat_grad), self.flat_grad.numel(), float(max_norm), _ptr(out2),
+                                                 _ptr(self._norm_buffers()[1]), _lib.stream()), "ign_grad_norm_clip")
         return out2
 
     def clip_(self, max_norm):
         """``clip_grad_norm_`` on the flat buffer: the norm launch plus one ``ign_scale_flat`` launch that multiplies the
         gradients themselves by the coefficient -> the norm before clipping, a device scalar (no host synchronisation)."""
-        import ctypes
-        from . import _lib
         out2 = self.grad_norm(max_norm)
-        _lib.check(_lib.lib().ign_scale_flat(ctypes.c_void_p(self.flat_grad.data_ptr()), self.flat_grad.numel(),
+        _lib.check(_lib.lib().ign_scale_flat(_ptr(self.flat_grad), self.flat_grad.numel(),
                                              ctypes.c_void_p(out2.data_ptr() + 4), _lib.stream()), "ign_scale_flat")
         return out2[0]
 
@@ -200,12 +196,10 @@ class FlatAdam(torch.optim.Optimizer):
     """
 
     def __init__(self, bucket, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, capturable=False):
-        from . import _lib
         ps = bucket.params
         if not ps[0].is_cuda:
             raise _lib.IgnError("FlatAdam runs on the GPU only")
         super().__init__(ps, dict(lr=lr, betas=betas, eps=eps))
-        self._lib = _lib
         self.bucket, self.lr, self.betas, self.eps = bucket, lr, betas, eps
         self.step_count = 0
         self.flat_param = torch.zeros_like(bucket.flat_grad)
@@ -238,40 +232,24 @@ class FlatAdam(torch.optim.Optimizer):
         """One Adam step.  ``max_norm`` > 0: gradient clipping as ``clip_grad_norm_(parameters, max_norm)`` in front of the step --
         one ``ign_grad_norm_clip`` launch leaves [norm, coefficient] in ``last_grad_norm`` / ``norm_dev`` on the device and the
         ``_clip`` Adam entry point reads every gradient times that coefficient (the gradients themselves are not rewritten)."""
-        import ctypes
         loss = closure() if closure is not None else None
         self.bucket.gather()
         self.step_count += 1
-        g = self.param_groups[0]
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr())
-        self._lib.PARAM_GENERATION[0] += 1           # the kernel rewrites the parameters through raw pointers
-        if max_norm is not None and max_norm > 0:
+        _lib.PARAM_GENERATION[0] += 1                # the kernel rewrites the parameters through raw pointers
+        clip = max_norm is not None and max_norm > 0
+        if clip:
             if self.norm_dev is None:
                 self.norm_dev = torch.zeros(2, device=self.flat_param.device, dtype=torch.float32)
                 self.last_grad_norm = self.norm_dev[0]
             self.bucket._norm_into(self.norm_dev, max_norm)
-            coef = ctypes.c_void_p(self.norm_dev.data_ptr() + 4)
-            if self.capturable:
-                self._lib.check(self._lib.lib().ign_adam_step_clip_dev(
-                    ptr(self.flat_param), ptr(self.bucket.flat_grad), ptr(self.exp_avg), ptr(self.exp_avg_sq),
-                    self.flat_param.numel(), g["lr"], g["betas"][0], g["betas"][1], g["eps"], ptr(self.step_dev), ptr(self.bc_dev),
-                    coef, self._lib.stream()), "ign_adam_step_clip_dev")
-                return loss
-            self._lib.check(self._lib.lib().ign_adam_step_clip(
-                ptr(self.flat_param), ptr(self.bucket.flat_grad), ptr(self.exp_avg), ptr(self.exp_avg_sq),
-                self.flat_param.numel(), g["lr"], g["betas"][0], g["betas"][1], g["eps"], self.step_count, coef,
-                self._lib.stream()), "ign_adam_step_clip")
-            return loss
-        if self.capturable:
-            self._lib.check(self._lib.lib().ign_adam_step_dev(
-                ptr(self.flat_param), ptr(self.bucket.flat_grad), ptr(self.exp_avg), ptr(self.exp_avg_sq),
-                self.flat_param.numel(), g["lr"], g["betas"][0], g["betas"][1], g["eps"], ptr(self.step_dev), ptr(self.bc_dev),
-                self._lib.stream()), "ign_adam_step_dev")
-            return loss
-        self._lib.check(self._lib.lib().ign_adam_step(
-            ptr(self.flat_param), ptr(self.bucket.flat_grad), ptr(self.exp_avg), ptr(self.exp_avg_sq),
-            self.flat_param.numel(), g["lr"], g["betas"][0], g["betas"][1], g["eps"], self.step_count,
-            self._lib.stream()), "ign_adam_step")
+        g = self.param_groups[0]
+        entry = "ign_adam_step" + ("_clip" if clip else "") + ("_dev" if self.capturable else "")
+        args = [_ptr(self.flat_param), _ptr(self.bucket.flat_grad), _ptr(self.exp_avg), _ptr(self.exp_avg_sq),
+                self.flat_param.numel(), g["lr"], g["betas"][0], g["betas"][1], g["eps"]]
+        args += [_ptr(self.step_dev), _ptr(self.bc_dev)] if self.capturable else [self.step_count]
+        if clip:
+            args.append(ctypes.c_void_p(self.norm_dev.data_ptr() + 4))          # the coefficient, out2[1] of the norm launch
+        _lib.check(getattr(_lib.lib(), entry)(*args, _lib.stream()), entry)
         return loss
 
     def zero_grad(self, set_to_none=False):

@@ -12,7 +12,7 @@ from conftest import parity
 
 pytestmark = pytest.mark.gpu
 
-# floats per stage-1 block of ign_grad_norm_clip (NORM_SLICE in csrc/ign_head.hip); the workspace is 4 header floats + one partial
+# floats per stage-1 block of ign_grad_norm_clip (NORM_SLICE in csrc/ign_optim.hip); the workspace is 4 header floats + one partial
 # per slice, which is how the test below pins the constant
 SLICE = 4096
 # 64: one aligned slot (one partial, mostly tail).  4160 = 4096 + 64: a second slice of 64 floats.  65 * 4096 - 3996: 65 partials
@@ -200,6 +200,72 @@ def test_clip_scales_the_gradients_themselves():
     for i, (p, q, v) in enumerate(zip(net.ps, ref.ps, bucket.views)):
         assert p.grad is v
         parity(f"clip_ grad {i}", p.grad, q.grad)
+
+
+# ---------------------------------------------------------------- the four Adam entry points, called directly
+ADAM_ENTRIES = ("ign_adam_step", "ign_adam_step_clip", "ign_adam_step_dev", "ign_adam_step_clip_dev")
+# tail only, tail of 3, no tail, tail of 1, the last lane of a block, exactly one block (the grid formula adds an empty one), one
+# element into the second block, several blocks plus a tail
+ADAM_NS = (1, 3, 4, 5, 1023, 1024, 1025, 4099)
+ADAM_BUF, ADAM_FULL = 4104, 4100                # 4100: no tail, every element goes through the 16-byte body
+ADAM_LR, ADAM_COEF = 5e-3, 0.37
+_adam_cache = {}
+
+
+def _adam_inputs():
+    """host (p, g, m, v) of ADAM_BUF floats, the same for every test"""
+    if "inputs" not in _adam_cache:
+        gen = torch.Generator().manual_seed(29)
+        _adam_cache["inputs"] = (torch.randn(ADAM_BUF, generator=gen), torch.randn(ADAM_BUF, generator=gen),
+                                 torch.randn(ADAM_BUF, generator=gen), torch.rand(ADAM_BUF, generator=gen))
+    return _adam_cache["inputs"]
+
+
+def _adam_run(lib, dev, entry, n, steps):
+    """`steps` calls of `entry` over the first n floats of fresh copies of the inputs -> (p, m, v) on the host"""
+    p, g, m, v = (t.to(dev) for t in _adam_inputs())
+    coef = torch.tensor([ADAM_COEF], device=dev)
+    step_dev, bc_dev = torch.zeros(1, device=dev, dtype=torch.int32), torch.zeros(2, device=dev)
+    for k in range(steps):
+        args = [_ptr(p), _ptr(g), _ptr(m), _ptr(v), n, ADAM_LR, 0.9, 0.999, 1e-8]
+        args += [_ptr(step_dev), _ptr(bc_dev)] if entry.endswith("_dev") else [k + 1]
+        if "_clip" in entry:
+            args.append(_ptr(coef))
+        lib.check(getattr(lib.lib(), entry)(*args, lib.stream()), entry)
+    if entry.endswith("_dev"):
+        assert int(step_dev) == steps
+    return p.cpu(), m.cpu(), v.cpu()
+
+
+@pytest.mark.parametrize("n", ADAM_NS)
+@pytest.mark.parametrize("entry", ADAM_ENTRIES)
+def test_adam_entry_over_n_is_the_prefix_of_the_full_run_and_writes_nothing_past_n(entry, n):
+    dev, lib = _dev(), _lib()
+    if entry not in _adam_cache:
+        _adam_cache[entry] = _adam_run(lib, dev, entry, ADAM_FULL, 1)
+    p0, _, m0, v0 = _adam_inputs()
+    for what, got, full, init in zip("pmv", _adam_run(lib, dev, entry, n, 1), _adam_cache[entry], (p0, m0, v0)):
+        assert torch.equal(got[:n], full[:n]), what
+        assert torch.equal(got[n:], init[n:]), what
+        assert not torch.equal(got[:n], init[:n]), what
+
+
+@pytest.mark.parametrize("n", ADAM_NS)
+@pytest.mark.parametrize("entry", ADAM_ENTRIES)
+def test_adam_entry_three_steps_against_torch_adam_in_float64(entry, n):
+    dev, lib = _dev(), _lib()
+    p0, g0, m0, v0 = _adam_inputs()
+    q = torch.nn.Parameter(p0[:n].double().clone())
+    ref = torch.optim.Adam([q], lr=ADAM_LR)
+    ref.state[q] = {"step": torch.tensor(0.0), "exp_avg": m0[:n].double().clone(), "exp_avg_sq": v0[:n].double().clone()}
+    coef = float(torch.tensor(ADAM_COEF, dtype=torch.float32)) if "_clip" in entry else 1.0
+    for _ in range(3):
+        q.grad = g0[:n].double() * coef
+        ref.step()
+    p = _adam_run(lib, dev, entry, n, 3)[0]
+    err = float((p[:n].double() - q.detach()).abs().max())
+    print(f"{entry} n={n}: max |hip - float64| = {err:.3e}")
+    assert err < 1e-5                           # the bound of test_clipped_flat_adam_against_..._in_float64
 
 
 # ---------------------------------------------------------------- accumulating gather

@@ -343,6 +343,29 @@ def test_abi_argument_errors_of_the_gemm_and_attention_entry_points():
         assert fn(p, p, p, p, p, p, p, p, None, p, 1, 8, 8, 1, 64, 512, 64, 512, 64, 512, 64, 0.1, None) == ARG
 
 
+@pytest.mark.parametrize("name", ["ign_adam_step", "ign_adam_step_clip", "ign_adam_step_dev", "ign_adam_step_clip_dev"])
+def test_adam_entry_points_refuse_a_parameter_pointer_that_is_not_16_byte_aligned(name):
+    """All four read and write 16 bytes at a time; the check precedes any launch, so the address is never dereferenced."""
+    import ctypes
+    from ign_hip import _lib
+    if not os.path.exists(_lib.lib_path()):
+        pytest.skip("libign_hip.so not built (run __graft_entry__.build())")
+    L = _lib.lib()
+    buf = (ctypes.c_float * 72)(*range(72))
+    base = (ctypes.addressof(buf) + 15) & ~15
+    at = lambda floats: ctypes.c_void_p(base + 4 * floats)
+    args = [at(1), at(16), at(32), at(48), 8, 5e-3, 0.9, 0.999, 1e-8]
+    args += [at(64), at(64)] if name.endswith("_dev") else [1]
+    if "_clip" in name:
+        args.append(at(64))
+    assert getattr(L, name)(*args, None) == -1001
+    err = L.ign_last_error()
+    assert err.startswith(name.encode() + b":") and b"16-byte aligned" in err
+    assert list(buf) == [float(i) for i in range(72)]
+    args[0] = None
+    assert getattr(L, name)(*args, None) == -1001 and L.ign_last_error().startswith(name.encode() + b": null pointer")
+
+
 @pytest.mark.parametrize("name", ["FCN", "ResNet", "PatchTST", "TimesNet", "Transformer", "EEGCNN"])
 def test_every_deep_expert_refuses_cpu_tensors(name):
     """No silent CPU path anywhere in the product models: a CPU tensor raises IgnError in every deep expert / baseline."""
