@@ -168,6 +168,25 @@ int ign_shapelet_bwd_input_bank(const float* xn_bct, int G, const float* const* 
                                 int B, int C, int T, const int* K, const int* L, const int* stride, float eps, int mode,
                                 void* stream);
 
+/* Shapelet initialisation from data: one Lloyd (k-means) step of one length group over a batch (csrc/ign_shapelet_kmeans.hip).
+ * The distance of shapelet (k, c) reads channel c only, so every channel clusters its own windows
+ * xn[b, c, t*stride : t*stride+L], over all (b, t < Tw), into the K centroids w_kcl[:, c, :]:
+ *   d[k] = (1/L) sum_j (x[t*stride+j] - w[k,c,j])^2   (direct differences, fp32),   a = argmin_k d[k]   (lowest k on ties)
+ *   sums_kcl[k,c,j] (+)= sum_{(b,t): a = k} x[b,c,t*stride+j]      counts_kc[k,c] (+)= #{(b,t): a = k}   (int32, exact)
+ *   inertia_c[c]    (+)= sum_{(b,t)} min_k d[k]                    assign (B,C,Tw) int32, nullable: a of every window
+ * accumulate = 0 overwrites sums / counts / inertia, 1 adds to them (a training set streamed batch by batch into one set of
+ * sums).  No atomics: per-slice partials and per-row counts are summed in a fixed order, so the outputs are bitwise repeatable.
+ * Domain: the forward's -- any B, C, T; 1 <= L <= T; stride, K >= 1; rows beyond its LDS staging return IGN_E_TOOBIG.  Nothing
+ * is launched on an error.  workspace: ign_shapelet_kmeans_workspace_bytes() bytes (0 for arguments outside the domain), no
+ * initialisation needed.
+ * ign_shapelet_kmeans_update: w_kcl[k,c,:] = sums_kcl[k,c,:] / counts_kc[k,c] where counts_kc[k,c] > 0; an empty cluster keeps
+ * its centroid bit for bit.  A cluster of one window becomes an exact copy of that window (the x == w case of IGN_TIE_EXACT).  */
+size_t ign_shapelet_kmeans_workspace_bytes(int B, int C, int T, int K, int L, int stride);
+int ign_shapelet_kmeans_step(const float* xn_bct, const float* w_kcl, int32_t* assign, float* sums_kcl, int32_t* counts_kc,
+                             float* inertia_c, void* workspace, int accumulate, int B, int C, int T, int K, int L, int stride,
+                             void* stream);
+int ign_shapelet_kmeans_update(float* w_kcl, const float* sums_kcl, const int32_t* counts_kc, int K, int C, int L, void* stream);
+
 /* Backward of ign_instnorm_fwd: gxn_bct (B,C,T) = dloss/dxn -> gx_btc (B,T,C) = dloss/dx in the loader's layout.  With
  * y = (x - mu) / (sigma + eps), sigma the unbiased std over T:
  *     gx_j = [ g_j - mean_T(g) - y_j * (sum_i g_i y_i) / (T - 1) * (sigma + eps) / sigma ] / (sigma + eps).

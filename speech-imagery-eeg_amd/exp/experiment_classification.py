@@ -90,6 +90,7 @@ class Experiment(object):
                                                                 (self.train_loader, self.val_loader, self.test_loader))
 
         self.model = self._build_model().to(self.device)
+        self._init_shapelets()          # --shapelet_init kmeans, on rank 0: before the flat bucket, whose broadcast carries it
         # On the GPU the step uses the flat path of bench.py: gradients are views into one buffer (a single RCCL all-reduce
         # under torch.distributed) and Adam is one ign_adam_step launch over the flat parameter buffer.
         self.bucket = None
@@ -113,6 +114,28 @@ class Experiment(object):
         print(f"Experiment: model={args.model} dnn={getattr(args, 'dnn_type', None)} device={self.device} "
               f"world={self.world} seq_len={args.seq_len} enc_in={args.enc_in} num_class={args.num_class} "
               f"train/val/test={len(self.train_data)}/{len(self.val_data)}/{len(self.test_data)}")
+
+    def _init_shapelets(self):
+        """--shapelet_init kmeans: the shapelets of an SBM / LTS / InterpGN model start as k-means centroids of the training
+        windows (utils/shapelet_init.py) instead of N(0,1).  Rank 0 only; not under --test_only.  The default does nothing."""
+        a = self.args
+        how = getattr(a, 'shapelet_init', 'normal')
+        if how == 'normal':
+            return
+        if how != 'kmeans':
+            raise ValueError(f"shapelet_init must be normal|kmeans, got {how!r}")
+        if a.model not in ('SBM', 'LTS', 'InterpGN'):
+            if self.rank == 0:
+                print(f"--shapelet_init kmeans: model {a.model} has no shapelets, nothing to initialise")
+            return
+        if getattr(a, 'test_only', False) or self.rank != 0:
+            return
+        from utils.shapelet_init import kmeans_init_
+        rep = kmeans_init_(self.model, self.train_loader, iters=getattr(a, 'shapelet_init_iters', 10),
+                           max_batches=getattr(a, 'shapelet_init_batches', 8), seed=max(int(getattr(a, 'seed', 0)), 0))
+        for g in rep["groups"]:
+            print(f"shapelet_init kmeans: length {g['length']} inertia {g['inertia'][0]:.6g} -> {g['inertia'][-1]:.6g} "
+                  f"({rep['iters']} iterations, {rep['batches']} batches) empty clusters {g['empty']}")
 
     def _load_data(self):
         self.train_data, self.train_loader = data_provider(self.args, flag="train")

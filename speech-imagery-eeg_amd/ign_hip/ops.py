@@ -335,6 +335,67 @@ def shapelet_bank(xn, weights, eps, mode=DIST_L1 | GATE_RBF, strides=None, thres
     return (P, D, Tstar) if return_tstar else (P, D)
 
 
+def _kmeans_stats(name, w, sums, counts, inertia):
+    """Check the statistics tensors of a k-means step against the centroids w (K,C,L): sums (K,C,L) fp32, counts (K,C) int32,
+    inertia (C) fp32, all contiguous on w's device."""
+    K, C, L = w.shape
+    _need_gpu(name, w, sums, inertia)
+    if not counts.is_cuda or counts.dtype != torch.int32:
+        raise _lib.IgnError(f"{name}: counts must be an int32 tensor on the GPU, got {counts.dtype} on {counts.device}")
+    for label, t, shape in (("sums", sums, (K, C, L)), ("counts", counts, (K, C)), ("inertia", inertia, (C,))):
+        if t is not None and (tuple(t.shape) != shape or not t.is_contiguous()):
+            raise _lib.IgnError(f"{name}: {label} must be a contiguous tensor of shape {shape}, got {tuple(t.shape)}")
+
+
+def shapelet_kmeans_step(xn, w, stride=1, sums=None, counts=None, inertia=None, return_assign=False):
+    """One Lloyd step of one length group over a batch (ign_shapelet_kmeans_step): every window xn[b, c, t*stride : t*stride+L]
+    of the instance-normalised (B,C,T) batch goes to the nearest (mean squared difference, lowest k on ties) of the K centroids
+    w[:, c, :] of its channel.  -> (sums (K,C,L), counts (K,C) int32, inertia (C))[, assign (B,C,Tw) int32]: the sum of the
+    windows of each cluster, its size, and the summed minimum distances per channel.  sums / counts / inertia None: allocated and
+    overwritten; given (all three): added to, for a training set streamed batch by batch.  Bitwise repeatable; no gradient."""
+    name = "shapelet_kmeans_step"
+    _need_gpu(name, xn, w)
+    given = [t is not None for t in (sums, counts, inertia)]
+    if any(given) and not all(given):
+        raise _lib.IgnError(f"{name}: pass sums, counts and inertia together (accumulate) or none of them (overwrite)")
+    if xn.dim() != 3 or w.dim() != 3 or w.shape[1] != xn.shape[1]:
+        raise _lib.IgnError(f"{name}: xn must be (B,C,T) and w (K,C,L) with the same C, got {tuple(xn.shape)} and {tuple(w.shape)}")
+    xn, wc = xn.detach().contiguous(), w.detach().contiguous()
+    B, C, T = xn.shape
+    K, _, Lw = wc.shape
+    stride = int(stride)
+    accumulate = all(given)
+    if not accumulate:
+        sums = torch.empty(K, C, Lw, device=xn.device, dtype=torch.float32)
+        counts = torch.empty(K, C, device=xn.device, dtype=torch.int32)
+        inertia = torch.empty(C, device=xn.device, dtype=torch.float32)
+    _kmeans_stats(name, wc, sums, counts, inertia)
+    L = _lib.lib()
+    nbytes = L.ign_shapelet_kmeans_workspace_bytes(B, C, T, K, Lw, stride)
+    work = torch.empty(max(nbytes, 4) // 4, device=xn.device, dtype=torch.int32)     # (0 bytes: the step call reports why)
+    assign = None
+    if return_assign and nbytes:
+        assign = torch.empty(B, C, (T - Lw) // stride + 1, device=xn.device, dtype=torch.int32)
+    _lib.check(L.ign_shapelet_kmeans_step(_ptr(xn), _ptr(wc), _ptr(assign), _ptr(sums), _ptr(counts), _ptr(inertia), _ptr(work),
+                                          1 if accumulate else 0, B, C, T, K, Lw, stride, _stream()), "ign_shapelet_kmeans_step")
+    return (sums, counts, inertia, assign) if return_assign else (sums, counts, inertia)
+
+
+def shapelet_kmeans_update(w, sums, counts):
+    """w[k,c,:] = sums[k,c,:] / counts[k,c] where counts > 0, in place and outside autograd (ign_shapelet_kmeans_update); an empty
+    cluster keeps its centroid bit for bit.  Returns w."""
+    name = "shapelet_kmeans_update"
+    if w.dim() != 3 or not w.is_contiguous():
+        raise _lib.IgnError(f"{name}: w must be a contiguous (K,C,L) tensor (it is written in place), got {tuple(w.shape)}")
+    _kmeans_stats(name, w, sums, counts, None)
+    K, C, Lw = w.shape
+    with torch.no_grad():
+        _lib.check(_lib.lib().ign_shapelet_kmeans_update(_ptr(w), _ptr(sums), _ptr(counts), K, C, Lw, _stream()),
+                   "ign_shapelet_kmeans_update")
+        _lib.PARAM_GENERATION[0] += 1        # parameter values changed behind autograd's back (see _lib.PARAM_GENERATION)
+    return w
+
+
 class SbmFn(torch.autograd.Function):
     """The shapelet bottleneck model behind the instance norm as ONE autograd node: shapelet bank (every length group) ->
     linear class head (optional) -> both regularisers (IGN/model/Shapelet.py:190-210, 217-230).

@@ -7,6 +7,8 @@ Differences, all repairs of fork defects listed in SURVEY section 0:
   * ``--data`` defaults to ``UEA`` and ``--data_root`` to ``./data/UEA_multivariate`` (the upstream defaults that
     survive as comments in IGN/run.py:68-69), so ``run_uea.sh`` -- which passes neither -- works (D2);
   * ``--data SYNTH`` (+ ``--synthetic n,C,T,classes``) is the synthetic CHISCO-shaped provider of the benchmark;
+  * ``--shapelet_init kmeans`` (+ ``--shapelet_init_iters``, ``--shapelet_init_batches``) starts the shapelets from k-means
+    centroids of the training windows instead of N(0,1); the default ``normal`` is the reference's initialisation;
   * ``--task_name regression --data Monash`` is the reference's regression twin (exp/experiment_regression.py), with the
     repairs R1-R3 of DESIGN 2.3;
   * multi-GPU is one process per GPU: ``python -m torch.distributed.run --nproc-per-node N run.py ...``.
@@ -79,6 +81,11 @@ def build_parser():
     p.add_argument("--distance_func", type=str, default='euclidean')
     p.add_argument("--beta_schedule", type=str, default='constant')
     p.add_argument("--memory_efficient", action="store_true")
+    p.add_argument("--shapelet_init", type=str, default='normal', choices=['normal', 'kmeans'],
+                   help="normal: N(0,1) shapelets as the reference; kmeans: k-means centroids of the training windows "
+                        "(utils/shapelet_init.py; SBM / LTS / InterpGN, before training)")
+    p.add_argument("--shapelet_init_iters", type=int, default=10, help="Lloyd iterations of --shapelet_init kmeans")
+    p.add_argument("--shapelet_init_batches", type=int, default=8, help="training batches --shapelet_init kmeans clusters")
     # experiment
     p.add_argument("--lr", type=float, default=5e-3)
     p.add_argument("--lr_decay", action="store_true")
