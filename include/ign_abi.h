@@ -195,6 +195,34 @@ int ign_shapelet_kmeans_update(float* w_kcl, const float* sums_kcl, const int32_
  * LDS tile limit of ign_instnorm_fwd applies (IGN_E_TOOBIG beyond it).                                                      */
 int ign_instnorm_bwd(const float* x_btc, const float* gxn_bct, float* gx_btc, int B, int T, int C, float eps, void* stream);
 
+/* Variable-length series (csrc/ign_shapelet_mask.hip; run.py --mask_padding).  A ragged batch arrives zero-padded at the end to
+ * (B,T,C) with len_b (B) int32 on the DEVICE: n_b = len_b[b] samples of row b are data (clamped to 0..T by the kernels).  The two
+ * passes below make the shapelet expert compute, for every sample, what it computes for that sample alone truncated to n_b.
+ *
+ * ign_instnorm_fwd_len: the length-aware twin of ign_instnorm_fwd.  Mean and unbiased std over x[b, :n_b, c]; (x - mean)/(std + eps)
+ * for t < n_b and exactly 0 for t >= n_b; n_b < 2: the whole row is 0.  No raw transpose and no amax (callers that need them call
+ * ign_instnorm_fwd on the padded batch).  Tile limit of ign_instnorm_fwd (IGN_E_TOOBIG beyond it).                               */
+int ign_instnorm_fwd_len(const float* x_btc, const int32_t* len_b, float* xn_bct, int B, int T, int C, float eps, void* stream);
+
+/* ign_shapelet_regate: runs AFTER ign_shapelet_fwd of the same group on xn_bct of ign_instnorm_fwd_len, on that call's outputs
+ * (same ld / col0 / K / L / stride / eps / mode; d_save is REQUIRED).  Sample b has Tw_b = (n_b - L)/stride + 1 valid windows
+ * (0 if n_b < L).  Per (b,c,k) row the pass recomputes p_out, dmin_out, tstar and zmu from d_save[.., t < Tw_b] with the forward's
+ * formulas (RBF: Z = sum exp(p_t), mu = sum exp(p_t) p_t / Z, p_out = max p; LTS: Z = sum exp(dmin - d_t), mu = sum e_t d_t / Z,
+ * p_out = sigmoid(thr - dmin); first index on ties) and overwrites d_save[.., t >= Tw_b] with 1e18f, the forward's value for
+ * slots past the end of a row, for which the coefficient of ign_shapelet_bwd / ign_shapelet_bwd_input is exactly 0 -- those
+ * kernels then yield the sum over samples of the gradients of the truncated problems, unchanged.
+ * Tw_b = 0: p_out = 0, dmin_out = 1e18f, tstar = -1, zmu = {1, 0}; the feature receives and sends no gradient.
+ * One wave per row, fixed-order reductions, no atomics: bitwise repeatable.  Any Tw.  The dist bits and IGN_TIE_EXACT of `mode` are
+ * validated and otherwise unused (the pass reads distances, whatever produced them).  Nothing is launched on an error.
+ * ign_shapelet_regate_bank: every group of a bank (tables of G <= 8 host entries, as ign_shapelet_fwd_bank), each validated before
+ * the first launch.                                                                                                              */
+int ign_shapelet_regate(float* d_save, const int32_t* len_b, const float* thr_kc, float* p_out, float* dmin_out, int ld, int col0,
+                        int32_t* tstar, float* zmu, int B, int C, int T, int K, int L, int stride, float eps, int mode,
+                        void* stream);
+int ign_shapelet_regate_bank(int G, float* const* d_save, const int32_t* len_b, const float* const* thr_kc, float* p_out,
+                             float* dmin_out, int ld, const int* col0, int32_t* const* tstar, float* const* zmu, int B, int C, int T,
+                             const int* K, const int* L, const int* stride, float eps, int mode, void* stream);
+
 /* Fused attention core softmax(scale * Q K^T) V, exact fp32 on the matrix cores (v_mfma_f32_32x32x2_f32), scores never
  * materialised.  Replaces IGN/layers/SelfAttention_Family.py:56-75 (FullAttention: no mask; dropout 0 here -- dropout p > 0
  * is ign_attn_*_dropout below) and the attention inside nn.TransformerEncoderLayer of IGN/model/eegcnn.py:219-228.

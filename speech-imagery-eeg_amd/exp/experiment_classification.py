@@ -124,6 +124,9 @@ class Experiment(object):
             return
         if how != 'kmeans':
             raise ValueError(f"shapelet_init must be normal|kmeans, got {how!r}")
+        if getattr(a, 'mask_padding', False):
+            raise ValueError("--shapelet_init kmeans with --mask_padding: k-means would cluster windows of the zero padding "
+                             "(there is no length-aware k-means step); use --shapelet_init normal")
         if a.model not in ('SBM', 'LTS', 'InterpGN'):
             if self.rank == 0:
                 print(f"--shapelet_init kmeans: model {a.model} has no shapelets, nothing to initialise")
@@ -287,6 +290,11 @@ class Experiment(object):
     # -- `--hipgraph`: the same step as above, captured once per (beta, lr) and replayed per batch ---------------------------------
     def _graph_eligible(self, amp):
         a = self.args
+        if getattr(a, 'mask_padding', False):
+            if getattr(a, 'hipgraph', False) and not getattr(self, '_mask_graph_notice', False):
+                self._mask_graph_notice = True
+                print("--mask_padding: the length-aware shapelet expert is not captured; --hipgraph ignored, training eagerly")
+            return False
         return (getattr(a, 'hipgraph', False) and self.device.type == 'cuda' and not amp and not self.distributed
                 and a.model in ('InterpGN', 'SBM', 'LTS') and self._flat_step and not self._attention_dropout_active())
 
@@ -522,6 +530,9 @@ class Experiment(object):
                                    accuracy=accuracy)
         if buf.p:
             res.p, res.d = host(buf.p), host(buf.d)
+            if getattr(a, 'mask_padding', False):
+                # ops.NO_WINDOW marks "no window": 0 for the score, which stays finite
+                res.d = torch.where(res.d >= ign_ops.NO_WINDOW / 10, torch.zeros_like(res.d), res.d)
             res.shapelet_preds = host(buf.shapelet_preds)
             sbm = self.model.sbm if a.model == 'InterpGN' else self.model
             res.w = sbm.output_layer.weight.detach().cpu()
@@ -531,6 +542,11 @@ class Experiment(object):
                 stride, length = sbm.match_layout()
                 res.t = host(buf.t)
                 res.match_start, res.match_len = res.t * stride.unsqueeze(0), length
+                if getattr(a, 'mask_padding', False):
+                    # t = -1: the sample is shorter than the shapelet, there is no match to locate
+                    none = res.t < 0
+                    res.match_start = torch.where(none, torch.full_like(res.match_start, -1), res.match_start)
+                    res.match_len = torch.where(none, torch.zeros_like(res.t), length.unsqueeze(0).expand_as(res.t))
             if a.model == 'InterpGN':
                 res.eta = host(buf.eta)
                 res.dnn_preds = host(buf.dnn_preds)

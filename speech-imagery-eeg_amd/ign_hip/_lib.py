@@ -157,6 +157,9 @@ SIGNATURES = {
     "ign_shapelet_kmeans_workspace_bytes": (sz, [ci, ci, ci, ci, ci, ci]),
     "ign_shapelet_kmeans_step": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]),
     "ign_shapelet_kmeans_update": (ci, [vp, vp, vp, ci, ci, ci, vp]),
+    "ign_instnorm_fwd_len": (ci, [vp, vp, vp, ci, ci, ci, cf, vp]),
+    "ign_shapelet_regate": (ci, [vp, vp, vp, vp, vp, ci, ci, vp, vp, ci, ci, ci, ci, ci, ci, cf, ci, vp]),
+    "ign_shapelet_regate_bank": (ci, [ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, cf, ci, vp]),
 }
 
 

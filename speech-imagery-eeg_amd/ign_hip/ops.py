@@ -16,6 +16,7 @@ LINEAR_WGRAD = "bf16x6"       # weight gradient of ops.linear on the split kerne
 GATE_RBF, GATE_LTS = 0x00, 0x10
 TIE_EXACT = 0x20              # IGN_TIE_EXACT: the L1 backward passes take sign(0) = 0 at x == w, as aten::sgn; travels inside `mode`
 HEAD_NMAX = 256               # IGN_HEAD_NMAX (include/ign_abi.h): widest class head of ign_head_* / ign_loss_*
+NO_WINDOW = 1e18             # Dmin of a feature without a valid window under `lengths` (IGN_NO_WINDOW, csrc/ign_shapelet_mask.hip); its Tstar is -1
 HEAD_WIDE_BMAX = 640          # batch bound of ign_head_bwd above 16 classes (one 16-class chunk of the logit gradient in 40 KB of LDS)
 
 
@@ -75,6 +76,35 @@ def _instance_norm(x_btc, want_raw, eps, input_bound):
     else:
         _lib.check(L.ign_instnorm_fwd(_ptr(x), _ptr(xn), _ptr(xt), B, T, C, eps, _stream()), "ign_instnorm_fwd")
     return xn, xt
+
+
+def _lengths(name, lengths, B):
+    """The per-sample lengths of a zero-padded batch as the kernels take them: a contiguous int32 (B) tensor on the GPU."""
+    if not torch.is_tensor(lengths) or not lengths.is_cuda or lengths.dtype != torch.int32 or tuple(lengths.shape) != (B,):
+        what = f"{lengths.dtype} {tuple(lengths.shape)} on {lengths.device}" if torch.is_tensor(lengths) else type(lengths).__name__
+        raise _lib.IgnError(f"{name}: lengths must be an int32 tensor of shape ({B},) on the GPU, got {what}")
+    return lengths.contiguous()
+
+
+def _no_input_grad_with_lengths(name, needs_grad):
+    if needs_grad:
+        raise _lib.IgnError(f"{name}: the input requires a gradient, but there is no length-aware ign_instnorm_bwd: input gradients "
+                            f"(saliency) run without `lengths`, on the padded batch")
+
+
+def instance_norm_len(x_btc, lengths, eps=1e-8):
+    """instance_norm for a batch zero-padded at the end: sample b has lengths[b] (int32, on the GPU) samples of data.  Mean and
+    unbiased std over x[b, :n_b] only; -> normalised (B,C,T) with exact zeros from n_b on (a row with n_b < 2 is all zeros).
+    No raw transpose, no input bound, no gradient (ign_instnorm_fwd_len)."""
+    name = "instance_norm_len"
+    _need_gpu(name, x_btc)
+    _no_input_grad_with_lengths(name, x_btc.requires_grad and torch.is_grad_enabled())
+    x = x_btc.detach().contiguous()
+    B, T, C = x.shape
+    lengths = _lengths(name, lengths, B)
+    xn = torch.empty(B, C, T, device=x.device, dtype=torch.float32)
+    _lib.check(_lib.lib().ign_instnorm_fwd_len(_ptr(x), _ptr(lengths), _ptr(xn), B, T, C, eps, _stream()), "ign_instnorm_fwd_len")
+    return xn
 
 
 class InstanceNormFn(torch.autograd.Function):
@@ -200,6 +230,21 @@ def _bank_fwd(bank, xn):
     return P, D
 
 
+def _bank_regate(bank, lengths, P, D):
+    """The length-aware pass behind _bank_fwd (ign_shapelet_regate): P, D and the record's arg-max windows, statistics and saved
+    distances become those of every sample truncated to lengths[b], in place."""
+    L = _lib.lib()
+    if bank.one_call:
+        _lib.check(L.ign_shapelet_regate_bank(
+            bank.G, bank.dsaves, _ptr(lengths), bank.thrs, _ptr(P), _ptr(D), bank.ld, bank.col0s, bank.tstars, bank.zmus,
+            bank.B, bank.C, bank.T, bank.Ks, bank.Ls, bank.Ss, bank.eps, bank.mode, _stream()), "ign_shapelet_regate_bank")
+    else:
+        for s in bank.groups:
+            _lib.check(L.ign_shapelet_regate(
+                _ptr(s.dsave), _ptr(lengths), _ptr(s.thr), _ptr(P), _ptr(D), bank.ld, s.col0, _ptr(s.tstar), _ptr(s.zmu),
+                bank.B, bank.C, bank.T, s.K, s.L, s.stride, bank.eps, bank.mode, _stream()), "ign_shapelet_regate")
+
+
 def _bank_wgrad(bank, xn, gP, P, D, gw_add=None, add_scale=None):
     """dloss/dw of every group (list of (K,C,L) tensors) from gP = dloss/dP (B, ld).  `gw_add[g]` / `add_scale` (a one-element
     device tensor): a batch-independent gradient of the same shapelets that the reduction launch adds as add_scale * gw_add[g]
@@ -263,18 +308,25 @@ def _threshold_grads(bank, gP, P):
     return [gt[s.col0:s.col0 + s.K * bank.C].view(1, s.K, bank.C) for s in bank.groups]
 
 
-def _node_forward(xn, others, params, G, eps, mode, strides, need_x, need_rest, gpu_name, grad_name):
+def _node_forward(xn, others, params, G, eps, mode, strides, need_x, need_rest, gpu_name, grad_name, lengths=None):
     """What the forwards of ShapeletBankFn and SbmFn share: unpack w_0..w_{G-1}[, thr_0..thr_{G-1}], refuse what the kernels do not
     take (`gpu_name` / `grad_name`: the node in a device / dtype error / in the input-gradient refusal; `others`: its further tensor inputs), build
-    the record and run the forward -> (xn, bank, P, D).  The distances are kept when the input alone needs a gradient."""
+    the record and run the forward -> (xn, bank, P, D).  The distances are kept when the input alone needs a gradient.
+    `lengths` (ShapeletBankLenFn): the record always keeps the distances, and the regate pass runs behind the forward."""
     ws = [w.contiguous() for w in params[:G]]
     thrs = [t.contiguous() for t in params[G:]] if (mode & GATE_LTS) else [None] * G
     _need_gpu(gpu_name, xn, *others, *ws, *[t for t in thrs if t is not None])
     xn = xn.contiguous()
     if need_x:
         _input_grad_supported(grad_name, mode)
-    bank = _Bank(xn, ws, thrs, eps, mode, strides, need_x or need_rest)
-    return (xn, bank, *_bank_fwd(bank, xn))
+    if lengths is None:
+        bank = _Bank(xn, ws, thrs, eps, mode, strides, need_x or need_rest)
+        return (xn, bank, *_bank_fwd(bank, xn))
+    lengths = _lengths(gpu_name, lengths, xn.shape[0])
+    bank = _Bank(xn, ws, thrs, eps, mode, strides, True)
+    P, D = _bank_fwd(bank, xn)
+    _bank_regate(bank, lengths, P, D)
+    return xn, bank, P, D
 
 
 def _node_backward(bank, xn, gP, P, D, need_x, need_params, gw_add=None, add_scale=None):
@@ -322,8 +374,36 @@ class ShapeletBankFn(torch.autograd.Function):
         return (gxn, None, None, None, None, *grads_w, *grads_t)
 
 
-def shapelet_bank(xn, weights, eps, mode=DIST_L1 | GATE_RBF, strides=None, thresholds=None, return_tstar=False):
-    """-> (P, Dmin) or, with return_tstar, (P, Dmin, Tstar): see ShapeletBankFn."""
+class ShapeletBankLenFn(torch.autograd.Function):
+    """ShapeletBankFn for a batch zero-padded at the end, `xn` from instance_norm_len with the same `lengths`: every sample is
+    matched as if it had been given alone, truncated to lengths[b] -- group g sees its first Tw_b = (n_b - L_g) // stride_g + 1
+    windows.  forward(xn, lengths, eps, mode, stride_list, n_groups, w_0..[, thr_0..]) -> (P, Dmin, Tstar); a feature without a
+    window (n_b < L_g) has P = 0, Dmin = NO_WINDOW, Tstar = -1 and neither receives nor sends a gradient.  The same forward and
+    backward kernels: the regate pass (_bank_regate) rewrites what the forward saved, so what autograd keeps (P, Dmin, the record)
+    is the regated state and the weight / threshold gradients are the sums of those of the truncated problems.  No input gradient."""
+
+    @staticmethod
+    def forward(ctx, xn, lengths, eps, mode, strides, n_groups, *params):
+        _no_input_grad_with_lengths("shapelet_bank", ctx.needs_input_grad[0])
+        xn, bank, P, D = _node_forward(xn, (), params, n_groups, eps, mode, strides, False, any(ctx.needs_input_grad[6:]),
+                                       gpu_name="shapelet_fwd", grad_name="shapelet_bank", lengths=lengths)
+        Tstar = bank.cat_tstar()
+        ctx.mark_non_differentiable(D, Tstar)
+        ctx.set_materialize_grads(False)
+        ctx.bank = bank
+        ctx.save_for_backward(xn, P, D, *(s.w for s in bank.groups), *(s.thr for s in bank.groups if s.thr is not None))
+        return P, D, Tstar
+
+    @staticmethod
+    def backward(ctx, gP, gD, gT):
+        xn, P, D = ctx.saved_tensors[:3]
+        _, grads_w, grads_t = _node_backward(ctx.bank, xn, gP, P, D, False, True)
+        return (None, None, None, None, None, None, *grads_w, *grads_t)
+
+
+def shapelet_bank(xn, weights, eps, mode=DIST_L1 | GATE_RBF, strides=None, thresholds=None, return_tstar=False, lengths=None):
+    """-> (P, Dmin) or, with return_tstar, (P, Dmin, Tstar): see ShapeletBankFn; with `lengths` (int32 (B) on the GPU; `xn` from
+    instance_norm_len): ShapeletBankLenFn."""
     G = len(weights)
     if (mode & 0xf) == DIST_PEARSON:
         # pearson_corrcoef centres both operands (Shapelet.py:11-19).  <x - mean x, w_c> == <x, w_c> for a centred w_c,
@@ -331,7 +411,10 @@ def shapelet_bank(xn, weights, eps, mode=DIST_L1 | GATE_RBF, strides=None, thres
         weights = [w - w.mean(dim=-1, keepdim=True) for w in weights]
     strides = strides or [1] * G
     params = list(weights) + (list(thresholds) if (mode & GATE_LTS) else [])
-    P, D, Tstar = ShapeletBankFn.apply(xn, eps, mode, tuple(strides), G, *params)
+    if lengths is None:
+        P, D, Tstar = ShapeletBankFn.apply(xn, eps, mode, tuple(strides), G, *params)
+    else:
+        P, D, Tstar = ShapeletBankLenFn.apply(xn, lengths, eps, mode, tuple(strides), G, *params)
     return (P, D, Tstar) if return_tstar else (P, D)
 
 

@@ -66,7 +66,7 @@ class InterpGN(nn.Module):
             # one stream, SBM first: its instance-norm pass hands the FCN expert the magnitude bound of the raw batch
             self.sbm.input_bound = isinstance(self.deep_model, FullyConvNetwork) and x.is_cuda and x.dtype == torch.float32 \
                 and not torch.is_autocast_enabled()
-            sbm_out, info = self.sbm(x)
+            sbm_out, info = self.sbm(x, x_mark_enc)
             return sbm_out, info, self.deep_model(x, x_mark_enc, x_dec, x_mark_dec, mask)
         self.sbm.input_bound = False                # two streams: the FCN expert is enqueued first and scans x itself
         main = torch.cuda.current_stream(x.device)
@@ -77,7 +77,7 @@ class InterpGN(nn.Module):
         with torch.cuda.stream(side):
             deep_out = self.deep_model(x, x_mark_enc, x_dec, x_mark_dec, mask)
         x.record_stream(side)
-        sbm_out, info = self.sbm(x)
+        sbm_out, info = self.sbm(x, x_mark_enc)
         main.wait_stream(side)
         deep_out.record_stream(main)
         return sbm_out, info, deep_out

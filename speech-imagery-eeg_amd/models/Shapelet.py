@@ -137,22 +137,35 @@ class ShapeBottleneckModel(nn.Module):
         self.dropout = nn.Dropout(p=configs.dropout)
         self.lambda_reg = configs.lambda_reg
         self.lambda_div = configs.lambda_div
+        # --mask_padding: a sample of a zero-padded (ragged) batch is normalised and matched over its own length only (forward)
+        self.mask_padding = bool(getattr(configs, "mask_padding", False))
 
     # set by InterpGN when a deep expert on the same stream consumes the raw batch through the fp16 GEMMs: the instance-norm
     # pass then also takes max |x| (ops.instance_norm), which spares that expert a pass of its own
     input_bound = False
 
     # -- hot path ---------------------------------------------------------------------------------
-    def shapelet_features(self, x, xn=None):
+    def shapelet_features(self, x, xn=None, lengths=None):
         """x (B,T,C) on the GPU -> (p, d_min) of every group, concatenated in the reference's order.
         `xn`: the instance-normalised (B,C,T) tensor if the caller already ran ign_instnorm_fwd (InterpGN does, to
-        share the transpose with the FCN expert)."""
-        if xn is None:
+        share the transpose with the FCN expert).
+        `lengths` (int32 (B) on the GPU): sample b is normalised and matched as x[b, :lengths[b]] alone (ops.instance_norm_len,
+        ops.ShapeletBankLenFn); a given `xn` is not used then."""
+        if lengths is not None:
+            xn = ops.instance_norm_len(x, lengths)
+        elif xn is None:
             xn, _ = ops.instance_norm(x, input_bound=self.input_bound)
         first = self.shapelets[0]
         thr = [s.threshold for s in self.shapelets] if first.gate == ops.GATE_LTS else None
         return ops.shapelet_bank(xn, [s.weights for s in self.shapelets], first.eps, first.mode(),
-                                 [s.stride for s in self.shapelets], thr, return_tstar=True)
+                                 [s.stride for s in self.shapelets], thr, return_tstar=True, lengths=lengths)
+
+    def padding_lengths(self, args):
+        """The lengths of a padded batch from the loader's (B,T) keep-mask (`args[0]` of forward; UEA's collate pads at the end, so
+        the mask is a length), on the device and without a host sync -- or None: the switch is off, or no mask came."""
+        if not self.mask_padding or not args or args[0] is None:
+            return None
+        return args[0].sum(1).to(torch.int32)
 
     def head(self, p):
         cls = self.configs.sbm_cls
@@ -200,11 +213,14 @@ class ShapeBottleneckModel(nn.Module):
         return out, ModelInfo(d=d, p=p, shapelet_preds=out, preds=out, loss=reg, t=t)
 
     def forward(self, x, *args, xn=None, **kwargs):
-        """-> (logits, ModelInfo).  ModelInfo.t (match locations) is filled in eval mode only: the training step never reads it."""
-        fused = self._fused_forward(x, xn)
+        """-> (logits, ModelInfo).  ModelInfo.t (match locations) is filled in eval mode only: the training step never reads it.
+        With mask_padding and a keep-mask in args[0] the expert honours each sample's length, on the un-fused route (bank node ->
+        head -> loss()); ModelInfo.t is then always filled, -1 where a sample is shorter than the shapelet (d = ops.NO_WINDOW)."""
+        lengths = self.padding_lengths(args)
+        fused = self._fused_forward(x, xn) if lengths is None else None
         if fused is not None:
             return fused
-        p, d, t = self.shapelet_features(x, xn)
+        p, d, t = self.shapelet_features(x, xn, lengths)
         out = self.head(p)
         return out, ModelInfo(d=d, p=p, shapelet_preds=out, preds=out, loss=self.loss().unsqueeze(0), t=t)
 

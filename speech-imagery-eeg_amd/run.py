@@ -9,6 +9,8 @@ Differences, all repairs of fork defects listed in SURVEY section 0:
   * ``--data SYNTH`` (+ ``--synthetic n,C,T,classes``) is the synthetic CHISCO-shaped provider of the benchmark;
   * ``--shapelet_init kmeans`` (+ ``--shapelet_init_iters``, ``--shapelet_init_batches``) starts the shapelets from k-means
     centroids of the training windows instead of N(0,1); the default ``normal`` is the reference's initialisation;
+  * ``--mask_padding`` makes the SBM / LTS expert normalise and match every sample of a ragged (zero-padded) batch over its own
+    length only; the default, off, is the reference's behaviour (the padding takes part);
   * ``--task_name regression --data Monash`` is the reference's regression twin (exp/experiment_regression.py), with the
     repairs R1-R3 of DESIGN 2.3;
   * multi-GPU is one process per GPU: ``python -m torch.distributed.run --nproc-per-node N run.py ...``.
@@ -86,6 +88,10 @@ def build_parser():
                         "(utils/shapelet_init.py; SBM / LTS / InterpGN, before training)")
     p.add_argument("--shapelet_init_iters", type=int, default=10, help="Lloyd iterations of --shapelet_init kmeans")
     p.add_argument("--shapelet_init_batches", type=int, default=8, help="training batches --shapelet_init kmeans clusters")
+    p.add_argument("--mask_padding", action="store_true",
+                   help="variable-length series: the SBM / LTS expert takes instance norm, shapelet matches and match locations over "
+                        "each sample's own length (the loader's padding mask) instead of over the zero padding.  Off: the "
+                        "reference's behaviour.  Trains eagerly (no --hipgraph); not with --shapelet_init kmeans")
     # experiment
     p.add_argument("--lr", type=float, default=5e-3)
     p.add_argument("--lr_decay", action="store_true")
@@ -130,8 +136,16 @@ def build_parser():
     return p
 
 
+def check_args(args):
+    """Combinations of flags that are refused before anything is built."""
+    if getattr(args, 'mask_padding', False) and getattr(args, 'shapelet_init', 'normal') == 'kmeans':
+        raise ValueError("--shapelet_init kmeans with --mask_padding: k-means would cluster windows of the zero padding "
+                         "(there is no length-aware k-means step); use --shapelet_init normal")
+
+
 def get_args(argv=None):
     args = build_parser().parse_args(argv)
+    check_args(args)
     args.root_path = args.data_root if args.data in ('EEG', 'EEG3', 'SYNTH') else f"{args.data_root}/{args.dataset}"
     args.is_training = True
     return args
