@@ -378,6 +378,17 @@ int ign_loss_fwd_bwd(const float* sbm, const float* dnn, const long long* labels
  * loss CE(out,y) + info.loss.mean() + beta*CE(sbm,y) of IGN/exp/experiment_classification.py:325-329 in one launch.        */
 int ign_loss_fwd_bwd_reg(const float* sbm, const float* dnn, const long long* labels, const float* reg, float* out, float* eta,
                          float* loss2, float* gsbm, float* gdnn, int B, int N, float beta, void* stream);
+/* The same tail under F.cross_entropy(z, y, weight=class_w, label_smoothing=eps, reduction='mean') for BOTH criteria, in one
+ * launch.  class_w: (N) positive finite floats, nullable = all ones; 0 <= label_smoothing < 1.  With D = sum_b w[y_b],
+ * W = sum_n w_n, p = softmax(z), lp = log p:
+ *   CEw = (1-eps) sum_b w[y_b] (-lp[b,y_b]) / D + (eps/N) sum_b sum_n w_n (-lp[b,n]) / D
+ *   dCEw/dz[b,n] = ( (1-eps) w[y_b] (p_n - [n = y_b]) + (eps/N) (p_n W - w_n) ) / D
+ * loss3 = {CEw(out), CEw(sbm), CEw(out) + beta*CEw(sbm) + reg[0]}; gsbm / gdnn through the gate as above.  D and W are summed
+ * inside the launch in a fixed order (no atomics: two calls agree bitwise); up to 16 classes out / eta are bitwise
+ * ign_gate_fwd's.  Labels outside [0, N) are clamped into it.  Limits and error codes as ign_loss_fwd_bwd_reg.            */
+int ign_loss_w_fwd_bwd_reg(const float* sbm, const float* dnn, const long long* labels, const float* class_w, const float* reg,
+                           float* out, float* eta, float* loss3, float* gsbm, float* gdnn, int B, int N, float beta,
+                           float label_smoothing, void* stream);
 
 /* Regression loss tail (IGN/exp/experiment_regression.py:59-76): CRPS of the softmax CDF over N bins against the step CDF
  * H_j = [edges[j] >= target] (compared in float64; edges may hold +-inf, a target on an edge counts as >=), batch mean, and

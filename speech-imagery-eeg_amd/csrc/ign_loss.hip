@@ -6,7 +6,8 @@
 //    Written ONCE, in the gate_* helpers, for every kernel of this file: the fused tails' mixture and eta are bitwise ign_gate_fwd's
 //    because they are the same source expressions (-ffp-contract=off).  A helper must keep its operation order and association.
 //  * CE tail    loss = CE(gate(s, d), y) + beta*CE(s, y) [+ reg] (batch means) and both logit gradients: one thread per row up to
-//    16 classes (ign_loss_kernel), one wave per row above (ign_loss_wide_kernel).
+//    16 classes (ign_loss_kernel), one wave per row above (ign_loss_wide_kernel).  With class weights and / or label smoothing:
+//    ign_loss_w_kernel / ign_loss_w_wide_kernel, the same two layouts behind an entry point of their own.
 //  * CRPS       p = softmax(z), F_j = sum_{i<=j} p_i, H_j = [edge_j >= y] (in float64); loss = mean_b sum_j (F_j - H_j)^2; per row
 //    r_j = F_j - H_j, q_i = (2/B) sum_{j>=i} r_j, dz_k = p_k (q_k - sum_i p_i q_i).  InterpGN's tail: CRPS in place of CE above.
 // The tails stay separate kernels: ign_loss_kernel adds the row terms per thread (rows t, t + 256, ...) and then over the threads,
@@ -301,6 +302,216 @@ __global__ void __launch_bounds__(LOSS_WAVES * 64) ign_loss_wide_kernel(const fl
     if (threadIdx.x == 0) write_loss3(loss2, tot[0], tot[1], invB, beta, reg);
 }
 
+// ------------------------------------------------------------------------------------------------ weighted, label-smoothed CE tail
+// The same tail under F.cross_entropy(z, y, weight=w, label_smoothing=eps, reduction='mean'), for both criteria.  With p = softmax(z),
+// D = sum_b w[y_b], W = sum_n w_n:
+//   CEw        = sum_b [ (1-eps) w[y_b] (lse_b - z[b,y_b]) + (eps/N) sum_n w_n (lse_b - z[b,n]) ] / D
+//   dCEw/dz_bn = ( (1-eps) w[y_b] (p_n - [n = y_b]) + (eps/N) (p_n W - w_n) ) / D
+// Separate kernels, so the unweighted ones above keep their bits; the gate is the same gate_* expressions in the same order.
+// D and W come from a pre-pass inside the launch (cew_prepass): no atomics, the same bits every call.
+struct CeW {
+    float keep, smooth, W, invD;       // 1 - eps, eps/N, sum_n w_n, 1 / sum_b w[y_b]
+};
+__device__ __forceinline__ int cew_label(long long y, int N) { return (int)(y < 0 ? 0 : y >= N ? N - 1 : y); }   // device data: clamped
+// one logit's gradient; wy = w[y_b], wn = w_n, hit = [n == y_b]
+__device__ __forceinline__ float cew_grad(const CeW& k, float wy, float p, float wn, bool hit) {
+    return (k.keep * wy * (p - (hit ? 1.f : 0.f)) + k.smooth * (p * k.W - wn)) * k.invD;
+}
+// one row's loss term before the division by D; nll = lse - z_y, smo = sum_n w_n (lse - z_n)
+__device__ __forceinline__ float cew_term(const CeW& k, float wy, float nll, float smo) { return k.keep * wy * nll + k.smooth * smo; }
+
+// Stages the class weights (null = ones) in the caller's LDS `wl` and returns {1 - eps, eps/N, W, 1/D} to every thread.  W is summed
+// in class order; D per thread over its rows t, t + blockDim, ... in ascending order, then over the threads in thread order (`red`:
+// blockDim floats of LDS, free again on return).
+__device__ __forceinline__ CeW cew_prepass(const float* __restrict__ cw, const long long* __restrict__ y, int B, int N, float eps,
+                                           float* wl, float* red) {
+    __shared__ float dw[2];
+    const int T = (int)blockDim.x;
+    for (int n = threadIdx.x; n < N; n += T) wl[n] = cw ? cw[n] : 1.f;
+    __syncthreads();
+    float part = 0.f;
+    for (int b = threadIdx.x; b < B; b += T) part += wl[cew_label(y[b], N)];
+    red[threadIdx.x] = part;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float D = 0.f, W = 0.f;
+        for (int i = 0; i < min(T, B); ++i) D += red[i];               // threads past the last row hold zeros
+        for (int n = 0; n < N; ++n) W += wl[n];
+        dw[0] = D;
+        dw[1] = W;
+    }
+    __syncthreads();
+    return CeW{1.f - eps, eps / (float)N, dw[1], 1.f / dw[0]};
+}
+
+// N <= 16: ign_loss_kernel's layout (thread <-> rows b, b + 256, ...; the two sums reduced through LDS in thread order)
+__global__ void __launch_bounds__(256) ign_loss_w_kernel(const float* __restrict__ s, const float* __restrict__ d,
+                                                         const long long* __restrict__ y, const float* __restrict__ cw,
+                                                         float* __restrict__ out, float* __restrict__ eta_out,
+                                                         float* __restrict__ loss3, float* __restrict__ gs, float* __restrict__ gd,
+                                                         int B, int N, float beta, float eps, const float* __restrict__ reg) {
+    __shared__ float red[2][256];
+    __shared__ float wl[LOSS_NMAX];
+    const CeW k = cew_prepass(cw, y, B, N, eps, wl, red[0]);
+    float ce_o = 0.f, ce_s = 0.f;
+    for (int b = threadIdx.x; b < B; b += 256) {
+        float sv[LOSS_NMAX], ov[LOSS_NMAX], q[LOSS_NMAX];
+        const float* sr = s + (long long)b * N;
+        const float* dr = d + (long long)b * N;
+        const int yb = cew_label(y[b], N);
+        const float wy = wl[yb];
+        for (int n = 0; n < N; ++n) sv[n] = sr[n];
+        float mx, z, z2;
+        row_stats<0>(sv, N, mx, z, z2, q);
+        const float G = gate_G(z, z2);
+        const float eta = gate_eta(N, G);
+        eta_out[b] = eta;
+        const float lse_s = mx + logf(z);
+        float mo = -INFINITY;
+        for (int n = 0; n < N; ++n) {
+            ov[n] = gate_mix(eta, sv[n], dr[n]);
+            out[(long long)b * N + n] = ov[n];
+            mo = fmaxf(mo, ov[n]);
+        }
+        float zo = 0.f;
+        for (int n = 0; n < N; ++n) zo += expf(ov[n] - mo);
+        const float lse_o = mo + logf(zo);
+        float smo_s = 0.f, smo_o = 0.f;
+        for (int n = 0; n < N; ++n) {
+            smo_s += wl[n] * (lse_s - sv[n]);
+            smo_o += wl[n] * (lse_o - ov[n]);
+        }
+        ce_s += cew_term(k, wy, lse_s - sv[yb], smo_s);
+        ce_o += cew_term(k, wy, lse_o - ov[yb], smo_o);
+        // gradients: g_out = dCEw(out)/dout ; through the gate ; + beta * dCEw(s)/ds
+        float dot = 0.f;
+        float go[LOSS_NMAX];
+        for (int n = 0; n < N; ++n) {
+            go[n] = cew_grad(k, wy, expf(ov[n] - mo) / zo, wl[n], n == yb);
+            dot += go[n] * (sv[n] - dr[n]);
+        }
+        const float c = gate_coef(N, dot);
+        for (int n = 0; n < N; ++n) {
+            const float qn = q[n] / z;
+            gs[(long long)b * N + n] = gate_ds(eta, go[n], c, qn, G) + beta * cew_grad(k, wy, qn, wl[n], n == yb);
+            gd[(long long)b * N + n] = gate_dd(eta, go[n]);
+        }
+    }
+    red[0][threadIdx.x] = ce_o;
+    red[1][threadIdx.x] = ce_s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float a = 0.f, b2 = 0.f;
+        for (int i = 0; i < 256; ++i) { a += red[0][i]; b2 += red[1][i]; }
+        write_loss3(loss3, a, b2, k.invD, beta, reg);
+    }
+}
+
+// 16 < N <= IGN_HEAD_NMAX: ign_loss_wide_kernel's layout (one wave per row, lanes over the classes in chunks of 64, row sums by
+// butterfly, the rows' loss terms added in ascending row order)
+__global__ void __launch_bounds__(LOSS_WAVES * 64) ign_loss_w_wide_kernel(const float* __restrict__ s, const float* __restrict__ d,
+                                                                          const long long* __restrict__ y,
+                                                                          const float* __restrict__ cw, float* __restrict__ out,
+                                                                          float* __restrict__ eta_out, float* __restrict__ loss3,
+                                                                          float* __restrict__ gs, float* __restrict__ gd, int B, int N,
+                                                                          float beta, float eps, const float* __restrict__ reg) {
+    __shared__ float ce[2][LOSS_TILE];
+    __shared__ float wl[IGN_HEAD_NMAX];
+    static_assert(LOSS_TILE >= LOSS_WAVES * 64, "cew_prepass borrows one row of `ce` for its per-thread sums");
+    const CeW k = cew_prepass(cw, y, B, N, eps, wl, ce[0]);
+    float tot[2] = {0.f, 0.f};                         // {CEw(out), CEw(s)} batch sums before / D, meaningful in thread 0
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int base = 0; base < B; base += LOSS_TILE) {
+        const int rows = min(LOSS_TILE, B - base);
+        for (int r = wave; r < rows; r += LOSS_WAVES) {
+            const int b = base + r;
+            const float* sr = s + (long long)b * N;
+            const float* dr = d + (long long)b * N;
+            const int yb = cew_label(y[b], N);
+            const float wy = wl[yb];
+            float sv[LOSS_KMAX], dv[LOSS_KMAX], q[LOSS_KMAX], ov[LOSS_KMAX], eo[LOSS_KMAX], wv[LOSS_KMAX];
+            float mx = -INFINITY;
+#pragma unroll
+            for (int kk = 0; kk < LOSS_KMAX; ++kk) {
+                const int n = kk * 64 + lane;
+                sv[kk] = n < N ? sr[n] : -INFINITY;
+                dv[kk] = n < N ? dr[n] : 0.f;
+                wv[kk] = n < N ? wl[n] : 0.f;
+                mx = fmaxf(mx, sv[kk]);
+            }
+            mx = wave_max(mx);
+            float z = 0.f, z2 = 0.f;
+#pragma unroll
+            for (int kk = 0; kk < LOSS_KMAX; ++kk) {
+                q[kk] = kk * 64 + lane < N ? expf(sv[kk] - mx) : 0.f;
+                z += q[kk];
+                z2 += q[kk] * q[kk];
+            }
+            z = wave_sum(z);
+            z2 = wave_sum(z2);
+            const float G = gate_G(z, z2);
+            const float eta = gate_eta(N, G);
+            if (lane == 0) eta_out[b] = eta;
+            float mo = -INFINITY, s_y = 0.f, o_y = 0.f;
+#pragma unroll
+            for (int kk = 0; kk < LOSS_KMAX; ++kk) {
+                const int n = kk * 64 + lane;
+                ov[kk] = gate_mix(eta, sv[kk], dv[kk]);
+                if (n < N) {
+                    out[(long long)b * N + n] = ov[kk];
+                    mo = fmaxf(mo, ov[kk]);
+                }
+                if (n == yb) { s_y = sv[kk]; o_y = ov[kk]; }
+            }
+            mo = wave_max(mo);
+            s_y = wave_sum(s_y);                  // exactly one lane holds the label's logits, the others add zeros
+            o_y = wave_sum(o_y);
+            float zo = 0.f;
+#pragma unroll
+            for (int kk = 0; kk < LOSS_KMAX; ++kk) {
+                eo[kk] = kk * 64 + lane < N ? expf(ov[kk] - mo) : 0.f;
+                zo += eo[kk];
+            }
+            zo = wave_sum(zo);
+            const float lse_s = mx + logf(z), lse_o = mo + logf(zo);
+            float smo_s = 0.f, smo_o = 0.f;
+#pragma unroll
+            for (int kk = 0; kk < LOSS_KMAX; ++kk)
+                if (kk * 64 + lane < N) {         // the padding lanes hold -inf logits
+                    smo_s += wv[kk] * (lse_s - sv[kk]);
+                    smo_o += wv[kk] * (lse_o - ov[kk]);
+                }
+            smo_s = wave_sum(smo_s);
+            smo_o = wave_sum(smo_o);
+            // gradients: g_out = dCEw(out)/dout ; through the gate ; + beta * dCEw(s)/ds
+            float dot = 0.f;
+#pragma unroll
+            for (int kk = 0; kk < LOSS_KMAX; ++kk) {
+                const int n = kk * 64 + lane;
+                eo[kk] = cew_grad(k, wy, eo[kk] / zo, wv[kk], n == yb);          // go
+                if (n < N) dot += eo[kk] * (sv[kk] - dv[kk]);
+            }
+            dot = wave_sum(dot);
+            const float c = gate_coef(N, dot);
+#pragma unroll
+            for (int kk = 0; kk < LOSS_KMAX; ++kk) {
+                const int n = kk * 64 + lane;
+                if (n < N) {
+                    const float qn = q[kk] / z;
+                    gs[(long long)b * N + n] = gate_ds(eta, eo[kk], c, qn, G) + beta * cew_grad(k, wy, qn, wv[kk], n == yb);
+                    gd[(long long)b * N + n] = gate_dd(eta, eo[kk]);
+                }
+            }
+            if (lane == 0) {
+                ce[0][r] = cew_term(k, wy, lse_o - o_y, smo_o);
+                ce[1][r] = cew_term(k, wy, lse_s - s_y, smo_s);
+            }
+        }
+        add_in_row_order(ce, rows, tot);
+    }
+    if (threadIdx.x == 0) write_loss3(loss3, tot[0], tot[1], k.invD, beta, reg);
+}
+
 // ------------------------------------------------------------------------------------------------ CRPS tails
 // One block of CRPS_THREADS threads, one thread per row (rows base + threadIdx.x of each tile).  Up to CRPS_NREG classes a
 // row lives in registers (loops fully unrolled, guarded by n < N); wider rows are read from global memory and the gradient
@@ -452,6 +663,28 @@ extern "C" int ign_loss_fwd_bwd_reg(const float* sbm, const float* dnn, const lo
 extern "C" int ign_loss_fwd_bwd(const float* sbm, const float* dnn, const long long* labels, float* out, float* eta, float* loss2,
                                 float* gsbm, float* gdnn, int B, int N, float beta, void* stream) {
     return ign_loss_fwd_bwd_reg(sbm, dnn, labels, nullptr, out, eta, loss2, gsbm, gdnn, B, N, beta, stream);
+}
+
+extern "C" int ign_loss_w_fwd_bwd_reg(const float* sbm, const float* dnn, const long long* labels, const float* class_w,
+                                      const float* reg, float* out, float* eta, float* loss3, float* gsbm, float* gdnn, int B, int N,
+                                      float beta, float label_smoothing, void* stream) {
+    if (!sbm || !dnn || !labels || !out || !eta || !loss3 || !gsbm || !gdnn || B <= 0 || N < 2) {
+        ign_set_error("ign_loss_w_fwd_bwd_reg: null pointer or bad dimension (B=%d N=%d, N <= %d)", B, N, IGN_HEAD_NMAX);
+        return IGN_E_ARG;
+    }
+    if (!(label_smoothing >= 0.f && label_smoothing < 1.f)) {
+        ign_set_error("ign_loss_w_fwd_bwd_reg: label_smoothing=%g outside [0, 1)", (double)label_smoothing);
+        return IGN_E_ARG;
+    }
+    if (N > IGN_HEAD_NMAX) { ign_set_error("ign_loss_w_fwd_bwd_reg: N=%d classes > %d", N, IGN_HEAD_NMAX); return IGN_E_UNSUP; }
+    const bool wide = N > LOSS_NMAX;
+    {
+        IgnScopedTimer tm("loss_w", (hipStream_t)stream);
+        hipLaunchKernelGGL(wide ? ign_loss_w_wide_kernel : ign_loss_w_kernel, dim3(1), dim3(wide ? LOSS_WAVES * 64 : 256), 0,
+                           (hipStream_t)stream, sbm, dnn, labels, class_w, out, eta, loss3, gsbm, gdnn, B, N, beta, label_smoothing,
+                           reg);
+    }
+    return ign_check_launch(wide ? "ign_loss_w_wide_kernel" : "ign_loss_w_kernel");
 }
 
 static bool crps_dims_ok(const char* name, int B, int N) {

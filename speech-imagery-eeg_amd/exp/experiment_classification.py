@@ -31,7 +31,7 @@ from models.FullyConvNet import FullyConvNetwork
 from models.InterpGN import InterpGN, dnn_dict
 from models.Shapelet import DistThresholdSBM, ShapeBottleneckModel
 from utils.shapelet_util import ClassificationResult
-from utils.tools import EarlyStopping, convert_to_hms, gini_coefficient  # noqa: F401
+from utils.tools import EarlyStopping, convert_to_hms, gini_coefficient, per_class_metrics  # noqa: F401
 
 
 def compute_beta(epoch, max_epoch, schedule='cosine'):
@@ -72,6 +72,7 @@ class Experiment(object):
         'DNN': get_dnn_model,
         'EEGCNN': get_eegcnn_model,
     }
+    class_weight, label_smoothing = None, 0.0       # the training criterion's options (_resolve_loss_options)
 
     def __init__(self, args):
         self.args = args
@@ -85,6 +86,7 @@ class Experiment(object):
 
         self._load_data()
         self._get_params_from_data()
+        self._resolve_loss_options()
         # host -> device double buffering (and, for raw CHISCO shards, the on-GPU standardise + transpose)
         self.train_loader, self.val_loader, self.test_loader = (self._prefetch(l) for l in
                                                                 (self.train_loader, self.val_loader, self.test_loader))
@@ -139,6 +141,23 @@ class Experiment(object):
         for g in rep["groups"]:
             print(f"shapelet_init kmeans: length {g['length']} inertia {g['inertia'][0]:.6g} -> {g['inertia'][-1]:.6g} "
                   f"({rep['iters']} iterations, {rep['batches']} batches) empty clusters {g['empty']}")
+
+    def _resolve_loss_options(self):
+        """--class_weight / --label_smoothing -> self.class_weight (None, or ONE float32 (num_class,) device tensor, allocated here
+        and never re-created, so a captured --hipgraph step replays it) and self.label_smoothing.  `balanced` counts the labels
+        of the FULL training set, before any rank sharding: every DDP rank holds the same vector.  The values are checked here,
+        once, on the host (positive, finite, one per class); ops.ign_loss trusts them.  Only the TRAINING criterion changes:
+        validation and test losses stay plain cross-entropy, so early stopping and every reported number stay comparable.
+        Under DDP and --gradient_accumulation_steps each rank / micro-batch takes its OWN weighted mean (divided by the sum of
+        the weights of its own labels); the gradients are then averaged / accumulated exactly as without weights -- what torch
+        DDP does with a weighted criterion."""
+        from utils.class_weight import check_loss_options, resolve_class_weight
+        spec, self.label_smoothing = check_loss_options(self.args, self.args.num_class)
+        w = resolve_class_weight(spec, self.train_data, self.args.num_class, notice=print if self.rank == 0 else None)
+        self.class_weight = None if w is None else w.to(self.device)
+        if w is not None and self.rank == 0:
+            print(f"class weights ({self.args.class_weight if spec == 'balanced' else 'given'}): "
+                  f"{[round(float(v), 4) for v in w]}")
 
     def _load_data(self):
         self.train_data, self.train_loader = data_provider(self.args, flag="train")
@@ -274,17 +293,20 @@ class Experiment(object):
             self.optimizer.zero_grad()
 
     def _train_loss(self, logits, info, label, beta, amp):
-        """The training loss of one step (IGN/exp/experiment_classification.py:319-329); `beta` weighs InterpGN's SBM term."""
+        """The training loss of one step (IGN/exp/experiment_classification.py:319-329); `beta` weighs InterpGN's SBM term.
+        Every cross-entropy of it takes the run's class weights and label smoothing (_resolve_loss_options)."""
         a = self.args
+        w, eps = self.class_weight, self.label_smoothing
         if a.model == 'InterpGN' and logits.is_cuda and not amp:
             # CE(mixture) + info.loss.mean() + beta*CE(sbm) and both logit gradients in one launch (ops.ign_loss)
             # instead of ~40 softmax / nll / mean kernels between the forward and the backward pass
-            return ign_ops.ign_loss(info.shapelet_preds, info.dnn_preds, label, beta, reg=info.loss)[0]
-        loss = F.cross_entropy(logits, label)
+            return ign_ops.ign_loss(info.shapelet_preds, info.dnn_preds, label, beta, reg=info.loss, class_weight=w,
+                                    label_smoothing=eps)[0]
+        loss = F.cross_entropy(logits, label, weight=w, label_smoothing=eps)
         if a.model != 'DNN':
             loss = loss + info.loss.mean()
         if a.model == 'InterpGN':
-            loss = loss + beta * F.cross_entropy(info.shapelet_preds, label)
+            loss = loss + beta * F.cross_entropy(info.shapelet_preds, label, weight=w, label_smoothing=eps)
         return loss
 
     # -- `--hipgraph`: the same step as above, captured once per (beta, lr) and replayed per batch ---------------------------------
@@ -522,12 +544,14 @@ class Experiment(object):
         predictions = logits.argmax(dim=1)
         accuracy = accuracy_score(predictions.numpy(), trues.numpy())
         test_loss = torch.cat(buf.loss).mean().item()
+        per_class = per_class_metrics(predictions, trues, a.num_class)
         if self.rank == 0:
             base = 100.0 / a.num_class
             print(f"Test: n={len(trues)} loss={test_loss:.6f} acc={accuracy:.4f} ({accuracy * 100:.2f}%; "
-                  f"random baseline {base:.2f}%)")
+                  f"random baseline {base:.2f}%) balanced_acc={per_class['balanced_accuracy']:.4f} "
+                  f"macro_f1={per_class['macro_f1']:.4f}")
         res = ClassificationResult(x_data=host(buf.x_data), trues=trues, preds=predictions, loss=test_loss,
-                                   accuracy=accuracy)
+                                   accuracy=accuracy, **per_class)
         if buf.p:
             res.p, res.d = host(buf.p), host(buf.d)
             if getattr(a, 'mask_padding', False):

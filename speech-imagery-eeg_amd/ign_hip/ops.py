@@ -1429,11 +1429,15 @@ def backward(loss):
         loss.backward()
 
 
-def _loss_tail(entry, sbm, dnn, crit, beta, reg):
+def _loss_tail(entry, sbm, dnn, crit, beta, reg, more=()):
     """The one launcher of the gated loss tails -> (loss3, out, eta, gsd): loss3[2] = criterion(gate(sbm, dnn)) + beta*criterion(sbm)
-    [+ reg], gsd (2, B, N) = its gradient w.r.t. (sbm, dnn) in one buffer.  `entry`: "ign_loss" (cross-entropy, crit = (labels,)) or
-    "ign_crps_loss" (CRPS, crit = (target, edges)); `crit` sits between `dnn` and `reg` in the entry point's signature."""
-    symbol = {"ign_loss": "ign_loss_fwd_bwd_reg", "ign_crps_loss": "ign_loss_crps_fwd_bwd_reg"}[entry]
+    [+ reg], gsd (2, B, N) = its gradient w.r.t. (sbm, dnn) in one buffer.  `entry`: "ign_loss" (cross-entropy, crit = (labels,)),
+    "ign_loss+w" (the weighted / label-smoothed cross-entropy, crit = (labels, class weights or None), more = (label_smoothing,);
+    reports as ign_loss) or "ign_crps_loss" (CRPS, crit = (target, edges)); `crit` sits between `dnn` and `reg` in the entry
+    point's signature, the numbers `more` between `beta` and the stream."""
+    symbol = {"ign_loss": "ign_loss_fwd_bwd_reg", "ign_loss+w": "ign_loss_w_fwd_bwd_reg",
+              "ign_crps_loss": "ign_loss_crps_fwd_bwd_reg"}[entry]
+    entry = entry.partition("+")[0]
     B, N = sbm.shape
     out = torch.empty_like(sbm)
     gsd = torch.empty(2, B, N, device=sbm.device, dtype=torch.float32)
@@ -1444,18 +1448,19 @@ def _loss_tail(entry, sbm, dnn, crit, beta, reg):
         if reg.numel() != 1:
             raise _lib.IgnError(f"{entry}: the regulariser must be one value, got {tuple(reg.shape)}")
     _lib.check(getattr(_lib.lib(), symbol)(_ptr(sbm), _ptr(dnn), *map(_ptr, crit), _ptr(reg), _ptr(out), _ptr(eta), _ptr(loss3),
-                                           _ptr(gsd[0]), _ptr(gsd[1]), B, N, float(beta), _stream()), symbol)
+                                           _ptr(gsd[0]), _ptr(gsd[1]), B, N, float(beta), *more, _stream()), symbol)
     return loss3, out, eta, gsd
 
 
-def _tail_forward(ctx, entry, sbm, dnn, prepare, crit, beta, reg):
+def _tail_forward(ctx, entry, sbm, dnn, prepare, crit, beta, reg, more=()):
     """What the forwards of IgnLossFn and IgnCrpsLossFn share -> (loss, out, eta); out / eta are reporting outputs.  `prepare`
     (_ce_inputs / _crps_inputs) checks the node's criterion arguments `crit` against the (B, N) logits and converts them."""
-    _need_gpu(entry, sbm, dnn, reg)
+    name = entry.partition("+")[0]
+    _need_gpu(name, sbm, dnn, reg)
     sbm, dnn = sbm.contiguous(), dnn.contiguous()
     if dnn.shape != sbm.shape:                        # the kernel reads B*N elements of each
-        raise _lib.IgnError(f"{entry}: expert logits {tuple(sbm.shape)} vs {tuple(dnn.shape)}")
-    loss3, out, eta, gsd = _loss_tail(entry, sbm, dnn, prepare(entry, sbm, *crit), beta, reg)
+        raise _lib.IgnError(f"{name}: expert logits {tuple(sbm.shape)} vs {tuple(dnn.shape)}")
+    loss3, out, eta, gsd = _loss_tail(entry, sbm, dnn, prepare(name, sbm, *crit), beta, reg, more)
     ctx.save_for_backward(gsd)
     ctx.n_crit, ctx.has_reg = len(crit), reg is not None
     ctx.mark_non_differentiable(out, eta)
@@ -1477,22 +1482,50 @@ def _ce_inputs(name, logits, y):
 
 
 class IgnLossFn(torch.autograd.Function):
-    """CE(gate(sbm, dnn), y) + beta * CE(sbm, y) [+ reg] with both logit gradients from one launch (_loss_tail)."""
+    """CE(gate(sbm, dnn), y) + beta * CE(sbm, y) [+ reg] with both logit gradients from one launch (_loss_tail).  The optional
+    `opts` = (class_weight, label_smoothing) after `reg` select the weighted / label-smoothed tail; they carry no gradient."""
 
     @staticmethod
-    def forward(ctx, sbm, dnn, y, beta, reg):
-        return _tail_forward(ctx, "ign_loss", sbm, dnn, _ce_inputs, (y,), beta, reg)
+    def forward(ctx, sbm, dnn, y, beta, reg, *opts):
+        ctx.n_opts = len(opts)
+        class_weight, label_smoothing = opts or (None, 0.0)
+        if class_weight is None and label_smoothing == 0.0:
+            return _tail_forward(ctx, "ign_loss", sbm, dnn, _ce_inputs, (y,), beta, reg)
+        return _tail_forward(ctx, "ign_loss+w", sbm, dnn, lambda name, logits, y: _ce_inputs(name, logits, y) + (class_weight,),
+                             (y,), beta, reg, (float(label_smoothing),))
 
     @staticmethod
     def backward(ctx, gl, gout, geta):
-        return _tail_backward(ctx, gl)
+        return _tail_backward(ctx, gl) + (None,) * ctx.n_opts
 
 
-def ign_loss(sbm_out, dnn_out, y, beta=1.0, reg=None):
+def _check_ce_options(name, logits, class_weight, label_smoothing):
+    """The host's refusals of ign_loss's options, before any device work.  The VALUES of the weights (positive, finite) are the
+    caller's to check where it builds them (utils.class_weight.check_weights): looking at them here would cost a sync per step."""
+    if not 0.0 <= label_smoothing < 1.0:
+        raise _lib.IgnError(f"{name}: label_smoothing={label_smoothing} outside [0, 1)")
+    if class_weight is None:
+        return
+    N = logits.shape[-1]
+    if not (torch.is_tensor(class_weight) and class_weight.dtype == torch.float32 and tuple(class_weight.shape) == (N,)
+            and class_weight.device == logits.device):
+        what = (f"{class_weight.dtype} {tuple(class_weight.shape)} on {class_weight.device}" if torch.is_tensor(class_weight)
+                else type(class_weight).__name__)
+        raise _lib.IgnError(f"{name}: class_weight must be a float32 ({N},) tensor on {logits.device}, got {what}")
+
+
+def ign_loss(sbm_out, dnn_out, y, beta=1.0, reg=None, class_weight=None, label_smoothing=0.0):
     """-> (CE(mix, y) + beta*CE(sbm, y) [+ reg], mix, eta); mix / eta are reporting outputs (no gradient flows through them).
     `reg`: the model's regulariser value (ModelInfo.loss, one element) -- added on the device inside the same launch, i.e. the
-    whole training loss of IGN/exp/experiment_classification.py:325-329 (its gradient passes straight through)."""
-    return IgnLossFn.apply(sbm_out.float(), dnn_out.float(), y, beta, reg)
+    whole training loss of IGN/exp/experiment_classification.py:325-329 (its gradient passes straight through).
+    `class_weight` (float32 (N,) on the logits' device, positive and finite) / `label_smoothing` (in [0, 1)): both CE terms become
+    F.cross_entropy(., y, weight=class_weight, label_smoothing=label_smoothing), still one launch (ign_loss_w_fwd_bwd_reg).  Without
+    them the call is today's node on today's entry point, bit for bit."""
+    if class_weight is None and label_smoothing == 0.0:
+        return IgnLossFn.apply(sbm_out.float(), dnn_out.float(), y, beta, reg)
+    _check_ce_options("ign_loss", sbm_out, class_weight, label_smoothing)
+    return IgnLossFn.apply(sbm_out.float(), dnn_out.float(), y, beta, reg, class_weight.contiguous() if class_weight is not None
+                           else None, float(label_smoothing))
 
 
 def _crps_inputs(name, logits, target, edges):

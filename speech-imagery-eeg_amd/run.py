@@ -11,6 +11,8 @@ Differences, all repairs of fork defects listed in SURVEY section 0:
     centroids of the training windows instead of N(0,1); the default ``normal`` is the reference's initialisation;
   * ``--mask_padding`` makes the SBM / LTS expert normalise and match every sample of a ragged (zero-padded) batch over its own
     length only; the default, off, is the reference's behaviour (the padding takes part);
+  * ``--class_weight none|balanced|w0,w1,...`` and ``--label_smoothing EPS`` turn the TRAINING cross-entropy into
+    ``F.cross_entropy(weight=, label_smoothing=)`` (InterpGN: still one fused launch); validation / test losses stay plain CE;
   * ``--task_name regression --data Monash`` is the reference's regression twin (exp/experiment_regression.py), with the
     repairs R1-R3 of DESIGN 2.3;
   * multi-GPU is one process per GPU: ``python -m torch.distributed.run --nproc-per-node N run.py ...``.
@@ -92,6 +94,10 @@ def build_parser():
                    help="variable-length series: the SBM / LTS expert takes instance norm, shapelet matches and match locations over "
                         "each sample's own length (the loader's padding mask) instead of over the zero padding.  Off: the "
                         "reference's behaviour.  Trains eagerly (no --hipgraph); not with --shapelet_init kmeans")
+    p.add_argument("--class_weight", type=str, default='none',
+                   help="class weights of the training cross-entropy: none; balanced = n / (classes present * count_c) from the "
+                        "training labels; or one positive value per class, w0,w1,...  Validation / test losses stay unweighted")
+    p.add_argument("--label_smoothing", type=float, default=0.0, help="label smoothing of the training cross-entropy, in [0, 1)")
     # experiment
     p.add_argument("--lr", type=float, default=5e-3)
     p.add_argument("--lr_decay", action="store_true")
@@ -141,6 +147,16 @@ def check_args(args):
     if getattr(args, 'mask_padding', False) and getattr(args, 'shapelet_init', 'normal') == 'kmeans':
         raise ValueError("--shapelet_init kmeans with --mask_padding: k-means would cluster windows of the zero padding "
                          "(there is no length-aware k-means step); use --shapelet_init normal")
+    from utils.class_weight import check_loss_options
+    check_loss_options(args, _num_class_from_flags(args))
+
+
+def _num_class_from_flags(args):
+    """The class count where the flags alone fix it (SYNTH, the 3-class CHISCO fold), else None: the dataset decides, and Experiment
+    repeats the check of an explicit --class_weight list against it."""
+    if getattr(args, 'data', None) == 'SYNTH':
+        return int((getattr(args, 'synthetic', None) or "8192,122,1000,3").split(',')[3])
+    return 3 if getattr(args, 'data', None) == 'EEG3' else None
 
 
 def get_args(argv=None):

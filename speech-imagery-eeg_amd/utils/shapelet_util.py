@@ -43,3 +43,10 @@ class ClassificationResult:
     t: Optional[torch.Tensor] = None
     match_start: Optional[torch.Tensor] = None      # (n, G*K*C) first sample of the best-matching window
     match_len: Optional[torch.Tensor] = None        # (G*K*C,)   shapelet length per column
+    # extension: per-class test metrics (utils.tools.per_class_metrics) -- what plain accuracy hides on a skewed label set
+    confusion: Optional[torch.Tensor] = None        # (N, N) int64, rows = true class, columns = predicted class
+    recall: Optional[torch.Tensor] = None           # (N,)
+    precision: Optional[torch.Tensor] = None        # (N,)
+    f1: Optional[torch.Tensor] = None               # (N,)
+    balanced_accuracy: Optional[float] = None       # mean recall over the classes with test samples
+    macro_f1: Optional[float] = None

@@ -54,3 +54,25 @@ def gini_coefficient(w):
         n = len(x)
         vals.append((2 * np.sum(np.arange(1, n + 1) * x)) / (n * x.sum()) - (n + 1) / n)
     return float(np.mean(vals))
+
+
+def per_class_metrics(preds, trues, num_class):
+    """Per-class test metrics from predicted and true labels -> dict: `confusion` (N, N) int64, rows = true, columns = predicted;
+    `recall`, `precision`, `f1` (N,) float64; `balanced_accuracy` = the mean recall over the classes that HAVE true samples;
+    `macro_f1` = the mean F1 over all N classes.  A 0/0 (recall of a class without samples, precision of a class never predicted,
+    F1 of a class with neither) counts as 0."""
+    preds = torch.as_tensor(preds).reshape(-1).long()
+    trues = torch.as_tensor(trues).reshape(-1).long()
+    N = int(num_class)
+    confusion = torch.bincount(trues * N + preds, minlength=N * N).reshape(N, N)
+    hit = confusion.diag().double()
+    n_true, n_pred = confusion.sum(1).double(), confusion.sum(0).double()
+
+    def ratio(num, den):
+        return torch.where(den > 0, num / den.clamp(min=1), torch.zeros_like(num))
+
+    recall, precision = ratio(hit, n_true), ratio(hit, n_pred)
+    f1 = ratio(2 * hit, n_true + n_pred)
+    seen = n_true > 0
+    return dict(confusion=confusion, recall=recall, precision=precision, f1=f1,
+                balanced_accuracy=float(recall[seen].mean()) if bool(seen.any()) else 0.0, macro_f1=float(f1.mean()))
