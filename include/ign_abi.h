@@ -223,6 +223,32 @@ int ign_shapelet_regate_bank(int G, float* const* d_save, const int32_t* len_b, 
                              float* dmin_out, int ld, const int* col0, int32_t* const* tstar, float* const* zmu, int B, int C, int T,
                              const int* K, const int* L, const int* stride, float eps, int mode, void* stream);
 
+/* Augmentation (csrc/ign_augment.hip; run.py --augment): the training batch x (B,T,C) -> out (B,T,C), one launch, out of place
+ * (x == out: IGN_E_ARG; the buffers must not overlap), no workspace, no atomics, bitwise repeatable.  len_b (B) int32 on the DEVICE
+ * or NULL (every sample has T steps); n = len_b[b] clamped to 0..T.
+ *   out[b,t,c] = keepC[b,c] * keepT[b,t] * (a[b,c] * x[b, (t - s_b) mod n, c] + sigma * n[b,t,c])   for t <  n
+ *   out[b,t,c] = x[b,t,c]                                                                          for t >= n (padding: no noise)
+ * The rule (csrc/ign_augment.h, the one definition the kernel, host code and the numpy restatement utils/augment.py share): every
+ * draw is Philox4x32-10 (Random123 constants) under key = seed (low word first); the last counter word tags the kind of draw and
+ * every transform reads its own word, so a draw depends on (seed, b), (seed, b, c) or (seed, b, t, c) only -- not on the launch
+ * geometry, on B, or on which transforms are on.
+ *   per sample, counter (b, 0, 0, 0) -> x0, x1, x2:
+ *     shift      S = min(floor(shift * n), n - 1), s_b = x0 mod (2 S + 1) - S (modulo bias below (2 S + 1) / 2^32 < 2^-20 up to
+ *                T = 2047);
+ *     time mask  M = min(floor(time_mask * n), n), m = x1 mod (M + 1), start = x2 mod (n - m + 1), keepT = 0 in [start, start + m);
+ *   per channel, counter (b, c, 0, 1) -> x0, x1:
+ *     gain       a = 1 + scale * (2 u - 1), u = (x0 >> 8) * 2^-24.  The SBM's instance norm cancels a per-channel gain; the term is
+ *                for the FCN / ResNet / EEG-CNN / Transformer side;
+ *     electrode  keepC <=> (x1 & 0xffff) >= chan_thr, chan_thr = round(p * 65536) as for attention dropout; nothing is rescaled;
+ *   noise, counter (e >> 2, 0, b, 2) with e = t * C + c: four consecutive flat indices share a call; Box-Muller on
+ *     u1 = ((w0 >> 8) + 1) * 2^-24, u2 = (w1 >> 8) * 2^-24 with the precise logf / sqrtf / sincosf: (x0, x1) -> elements 0, 1 of the
+ *     quad, (x2, x3) -> elements 2, 3.  sigma == 0 skips the noise path; the other terms are separate fp32 roundings (no fma), so a
+ *     float32 restatement is then bitwise equal.
+ * n = 0 copies the row; n = 1 forces S = M = 0.  shift, scale, time_mask in [0, 1), chan_thr < 65536, sigma finite and >= 0, T >= 1,
+ * else IGN_E_ARG; C > 8192 or T * C >= 2^31 - 65536: IGN_E_TOOBIG.  Nothing is launched on an error.                              */
+int ign_augment_btc(const float* x_btc, float* out_btc, const int32_t* len_b, int B, int T, int C, unsigned long long seed,
+                    float shift, float scale, float sigma, unsigned chan_thr, float time_mask, void* stream);
+
 /* Fused attention core softmax(scale * Q K^T) V, exact fp32 on the matrix cores (v_mfma_f32_32x32x2_f32), scores never
  * materialised.  Replaces IGN/layers/SelfAttention_Family.py:56-75 (FullAttention: no mask; dropout 0 here -- dropout p > 0
  * is ign_attn_*_dropout below) and the attention inside nn.TransformerEncoderLayer of IGN/model/eegcnn.py:219-228.

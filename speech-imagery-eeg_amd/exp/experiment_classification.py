@@ -87,6 +87,7 @@ class Experiment(object):
         self._load_data()
         self._get_params_from_data()
         self._resolve_loss_options()
+        self._resolve_augment()
         # host -> device double buffering (and, for raw CHISCO shards, the on-GPU standardise + transpose)
         self.train_loader, self.val_loader, self.test_loader = (self._prefetch(l) for l in
                                                                 (self.train_loader, self.val_loader, self.test_loader))
@@ -158,6 +159,31 @@ class Experiment(object):
         if w is not None and self.rank == 0:
             print(f"class weights ({self.args.class_weight if spec == 'balanced' else 'given'}): "
                   f"{[round(float(v), 4) for v in w]}")
+
+    def _resolve_augment(self):
+        """--augment -> self._augment_spec (None when off: the training loops then do nothing extra -- no launch, no mask sum, no
+        seed arithmetic, no generator use) and the base seed of utils.augment.step_seed: --seed when it is >= 0, else torch's
+        initial seed (reading it does not advance the generator)."""
+        from utils.augment import parse_augment
+        spec = parse_augment(getattr(self.args, 'augment', None))
+        self._augment_spec = spec if spec.active else None
+        if self._augment_spec is not None:
+            seed = int(getattr(self.args, 'seed', -1))
+            self._augment_base = seed if seed >= 0 else int(torch.initial_seed())
+            if self.rank == 0:
+                print(f"augment: {', '.join(f'{k}={v:g}' for k, v in spec._asdict().items() if v)}")
+
+    def _augment(self, batch_x, padding_mask, train_step):
+        """The training batch of step `train_step`, augmented on the device in one launch (ops.augment; seed = step_seed(base, rank,
+        step), so ranks draw different augmentations and the eager and captured loops the same ones).  Each sample is shifted,
+        masked and noised inside its own length -- the keep-mask's row sum, taken on the device without a host sync; an all-ones
+        mask gives what no lengths give.  Training only: validation, test, saliency and the k-means initialisation never call it."""
+        if self._augment_spec is None:
+            return batch_x
+        from utils.augment import step_seed
+        lengths = padding_mask.sum(1).to(torch.int32)
+        return ign_ops.augment(batch_x.contiguous(), step_seed(self._augment_base, self.rank, train_step), lengths=lengths,
+                               **self._augment_spec._asdict())
 
     def _load_data(self):
         self.train_data, self.train_loader = data_provider(self.args, flag="train")
@@ -254,6 +280,7 @@ class Experiment(object):
         for batch_x, label, padding_mask in self.train_loader:
             train_step += 1
             batch_x, label, padding_mask = self._to_device(batch_x, label, padding_mask)
+            batch_x = self._augment(batch_x, padding_mask, train_step)
             with torch.autocast(device_type=self.device.type, dtype=torch.bfloat16, enabled=amp):
                 logits, info = self._forward(batch_x, padding_mask)
                 loss = self._train_loss(logits, info, label, compute_beta(epoch, a.train_epochs, a.beta_schedule), amp)
@@ -373,6 +400,7 @@ class Experiment(object):
         for batch_x, label, padding_mask in self.train_loader:
             train_step += 1
             batch_x, label, padding_mask = self._to_device(batch_x, label, padding_mask)
+            batch_x = self._augment(batch_x, padding_mask, train_step)      # outside the graph: its static input takes this batch
             kind, fn = ('close', step_fn) if train_step % K == 0 else ('micro', micro_fn)
             if batch_x.shape[0] != a.batch_size:                  # ragged last batch: eager
                 losses.append(fn(batch_x, label, padding_mask).clone())

@@ -161,6 +161,7 @@ SIGNATURES = {
     "ign_shapelet_regate": (ci, [vp, vp, vp, vp, vp, ci, ci, vp, vp, ci, ci, ci, ci, ci, ci, cf, ci, vp]),
     "ign_shapelet_regate_bank": (ci, [ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, cf, ci, vp]),
     "ign_loss_w_fwd_bwd_reg": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, cf, cf, vp]),
+    "ign_augment_btc": (ci, [vp, vp, vp, ci, ci, ci, ctypes.c_ulonglong, cf, cf, cf, ctypes.c_uint, cf, vp]),
 }
 
 

@@ -165,6 +165,44 @@ def standardise_nct_to_btc(x_nct, eps=1e-8):
     return out
 
 
+def augment(x, seed, *, lengths=None, shift=0.0, scale=0.0, noise=0.0, channel_drop=0.0, time_mask=0.0):
+    """Training augmentation of a contiguous fp32 (B,T,C) batch on the GPU -> a new tensor (ign_augment_btc; the rule is
+    csrc/ign_augment.h, restated in utils/augment.py): a circular shift by up to `shift` * length, a per-channel gain in
+    1 +- `scale`, Gaussian noise of standard deviation `noise`, electrode dropout at rate `channel_drop` (no rescaling) and one
+    masked time span of up to `time_mask` * length per sample.  `lengths`: int32 (B,) on the GPU -- everything happens inside each
+    sample's own length and the padding is copied through; None: every sample has T steps.  `seed`: a 64-bit host integer; the
+    same seed gives the same output to the bit.  Rates lie in [0, 1), `noise` >= 0.
+    Refused for an input that requires a gradient (a training batch never does) and during graph capture (the seed is a host
+    value: a replay would repeat one augmentation)."""
+    name = "augment"
+    _need_gpu(name, x)
+    if x.dim() != 3 or not x.is_contiguous():
+        raise _lib.IgnError(f"{name}: expected a contiguous (B,T,C) tensor, got shape {tuple(x.shape)} strides {x.stride()}")
+    if x.requires_grad:
+        raise _lib.IgnError(f"{name}: the input requires a gradient; augmentation acts on data (there is no backward pass)")
+    if torch.cuda.is_current_stream_capturing():
+        raise _lib.IgnError(f"{name} inside a hipGraph capture: the per-call seed would be frozen into the graph (augment the batch "
+                            f"before the captured step)")
+    for what, v in (("shift", shift), ("scale", scale), ("time_mask", time_mask)):
+        if not 0.0 <= ctypes.c_float(v).value < 1.0:
+            raise ValueError(f"{name}: {what} = {v} outside [0, 1)")
+    if not 0.0 <= ctypes.c_float(noise).value < float("inf"):
+        raise ValueError(f"{name}: noise = {noise} must be finite and >= 0")
+    try:
+        thr = dropout_threshold(channel_drop)[0]               # the keep rule of attention dropout: halfword >= round(p * 65536)
+    except ValueError:
+        raise ValueError(f"{name}: channel_drop = {channel_drop} outside [0, 1)") from None
+    B, T, C = x.shape
+    out = torch.empty_like(x)
+    if B == 0:
+        return out
+    if lengths is not None:
+        lengths = _lengths(name, lengths, B)
+    _lib.check(_lib.lib().ign_augment_btc(_ptr(x), _ptr(out), _ptr(lengths), B, T, C, int(seed) & 0xFFFFFFFFFFFFFFFF, shift, scale,
+                                          noise, thr, time_mask, _stream()), "ign_augment_btc")
+    return out
+
+
 def _tables(G):
     return ctypes.c_void_p * G, ctypes.c_int * G
 

@@ -13,6 +13,9 @@ Differences, all repairs of fork defects listed in SURVEY section 0:
     length only; the default, off, is the reference's behaviour (the padding takes part);
   * ``--class_weight none|balanced|w0,w1,...`` and ``--label_smoothing EPS`` turn the TRAINING cross-entropy into
     ``F.cross_entropy(weight=, label_smoothing=)`` (InterpGN: still one fused launch); validation / test losses stay plain CE;
+  * ``--augment shift=0.1,scale=0.1,noise=0.05,chan_drop=0.1,time_mask=0.1`` (any subset) augments every TRAINING batch on the
+    device in one fused launch: circular shift, per-channel gain, Gaussian noise, electrode dropout, one masked time span, each
+    inside the sample's own length; validation / test never augment; the default ``none`` changes nothing;
   * ``--task_name regression --data Monash`` is the reference's regression twin (exp/experiment_regression.py), with the
     repairs R1-R3 of DESIGN 2.3;
   * multi-GPU is one process per GPU: ``python -m torch.distributed.run --nproc-per-node N run.py ...``.
@@ -98,6 +101,11 @@ def build_parser():
                    help="class weights of the training cross-entropy: none; balanced = n / (classes present * count_c) from the "
                         "training labels; or one positive value per class, w0,w1,...  Validation / test losses stay unweighted")
     p.add_argument("--label_smoothing", type=float, default=0.0, help="label smoothing of the training cross-entropy, in [0, 1)")
+    p.add_argument("--augment", type=str, default='none',
+                   help="training-batch augmentation on the device, one fused launch per step: none, or a comma list of "
+                        "shift=R (circular shift by up to R * length), scale=R (per-channel gain in 1 +- R; the SBM's instance norm "
+                        "cancels it, the DNN experts see it), noise=SIGMA (Gaussian), chan_drop=P (electrodes zeroed, no rescaling), "
+                        "time_mask=R (one zeroed span of up to R * length per sample); rates in [0, 1).  Reproducible from --seed")
     # experiment
     p.add_argument("--lr", type=float, default=5e-3)
     p.add_argument("--lr_decay", action="store_true")
@@ -149,6 +157,8 @@ def check_args(args):
                          "(there is no length-aware k-means step); use --shapelet_init normal")
     from utils.class_weight import check_loss_options
     check_loss_options(args, _num_class_from_flags(args))
+    from utils.augment import parse_augment
+    parse_augment(getattr(args, 'augment', None))
 
 
 def _num_class_from_flags(args):
