@@ -68,6 +68,32 @@ int ign_transpose_btc_to_bct(const float* x_btc, float* out_bct, int B, int T, i
 int ign_standardise_nct_to_btc(const float* x_nct, float* out_btc, float* stats_ws, int B, int C, int T, float eps,
                                void* stream);
 
+/* EEG preprocessing in front of the standardisation (csrc/ign_eeg_preprocess.hip; run.py --eeg_preprocess): raw (B,Cin,Tin)
+ * recordings -> centred FIR filter, decimate by q, crop / zero-pad to (Tout,Cout), standardise, transpose -> out (B,Tout,Cout).
+ * What the reference's loader does on the CPU with scipy.signal.decimate(ftype='fir', zero_phase=True) and its channel / time
+ * fitting (IGN/data_factory/eeg_processor.py:258-381), here for a whole batch in front of the per-sample statistics.
+ *   taps (M) fp32 on the DEVICE, M odd, R = (M-1)/2;  x~ = the row extended by R samples: zeros (IGN_EDGE_ZERO) or mirrored
+ *   about the end samples, x~[-i] = x[i], x~[Tin-1+i] = x[Tin-1-i] (IGN_EDGE_REFLECT, numpy pad 'reflect'; needs R <= Tin-1);
+ *   f[n] = sum_k taps[k] * x~[n*q + R - k],  n < Td = ceil(Tin/q)     (a convolution, centred: zero-phase for symmetric taps)
+ *   Tv = min(Td, Tout); per (b, c < min(Cin,Cout)): mean and unbiased std of f[0..Tv-1] in two sweeps;
+ *   out[b,t,c] = (f[t] - mean) / (std + eps) for t < Tv; exactly 0 for Tv <= t < Tout and for Cin <= c < Cout.
+ * In reflect mode with M > 1 the kernel filters x - x[b,c,0] (a constant passes reflect-extended filtering up to the factor
+ * sum(taps) and the standardisation removes it): the same value, without the recording's offset in the fp32 products.  M = 1 extends
+ * nothing and takes no pivot; the statistics run in ign_standardise_nct_to_btc's order, so taps {1} with Cout = Cin, Tout = Tin give
+ * that entry point's output bit for bit.  Fixed summation order, no
+ * atomics: two calls give the same bits.  Nothing outside [0,Tin) of a row is read; taps longer than the row are legal in zero mode.
+ * ws: ign_eeg_preprocess_ws_bytes() bytes (B * min(Cin,Cout) * Tv floats; 0 for arguments the launcher refuses).
+ * IGN_E_ARG: null pointer, non-positive dimension, M even or > IGN_EEG_MAX_TAPS, q outside 1..IGN_EEG_MAX_DECIMATE, unknown edge,
+ * reflect with R >= Tin, Tv < 2.  IGN_E_TOOBIG: a row whose phase-split image and filtered copy exceed 64 KB of LDS
+ * ((Tin + M - 1 + q*4 + Tv) floats), or B > 65535.  Nothing is launched on an error.                                          */
+#define IGN_EDGE_REFLECT     0
+#define IGN_EDGE_ZERO        1
+#define IGN_EEG_MAX_TAPS     1023
+#define IGN_EEG_MAX_DECIMATE 16
+size_t ign_eeg_preprocess_ws_bytes(int B, int Cin, int Tin, int M, int q, int Cout, int Tout);
+int ign_eeg_preprocess_nct_to_btc(const float* x_nct, const float* taps, float* out_btc, float* ws, int B, int Cin, int Tin, int M,
+                                  int q, int edge, int Cout, int Tout, float eps, void* stream);
+
 /* Shapelet transform of ONE length group: sliding-window distance + gate, never materialising (B,Tw,K,C,L).
  * Replaces IGN/model/Shapelet.py:60-84 (GATE_RBF) / :96-111 (GATE_LTS).   Tw = (T-L)/stride + 1.
  *   xn_bct   (B,C,T)    normalised input

@@ -1,0 +1,229 @@
+// On-device EEG preprocessing in front of the standardisation (run.py --eeg_preprocess; ops.eeg_preprocess; the numpy restatement
+// is utils/eeg_filter.py:preprocess_numpy): raw (B, Cin, Tin) recordings -> zero-phase FIR filter, decimate by q, crop / zero-pad
+// to (Tout, Cout), per-row standardise over the valid part, transpose to the loader's (B, Tout, Cout).
+//
+//   x~      the row extended by R = (M-1)/2 samples on each side: zeros, or the reflection about the end samples (numpy 'reflect')
+//   f[n]    = sum_k h[k] * x~[n*q + R - k],  n < Td = ceil(Tin / q)            a centred convolution: no delay
+//   out     = (f[t] - mean) / (std + eps) over t < Tv = min(Td, Tout), unbiased std in two sweeps; exact zeros elsewhere
+//
+// In reflect mode the row is filtered as x - x[0]: a constant is a fixed point of reflect-extended filtering up to the factor sum(h)
+// and the standardisation removes it, so the value is the same while the fp32 products no longer carry the 1e4 uV offset.  With a
+// single tap (R = 0) nothing is extended and no pivot is taken: the pass is then the arithmetic of ign_standardise_nct_to_btc, in its
+// order, so taps {1} without cropping give that kernel's output bit for bit (an identity spec is the default path).
+//
+// pass 1, one 256-thread workgroup per (b, c < min(Cin, Cout)) row.  The extended row X[i] = x~[i - R] is staged in LDS split by
+// phase, Xp[m] = X[m*q + p], so that the decimated convolution becomes q plain correlations (the polyphase form)
+//       f[n] = sum_p sum_i h[2R - p - i*q] * Xp[n + i]
+// in which every lane reads one phase array at n + const.  A lane owns EP_J = 5 consecutive outputs and walks the sub-taps in
+// blocks of EP_U = 8: 12 LDS values feed 40 fmaf, and the lane stride of 5 dwords is conflict-free on the 32 banks (4 would be
+// 4-way).  The taps are wave-uniform scalar loads.  f stays in LDS for the two statistics sweeps, which wave 0 runs in the order of
+// std_rowstats_kernel (lane-strided sums, then the butterfly: fixed order, no atomics), and leaves standardised as one coalesced line
+// of the workspace.
+// pass 2, the 64 (t) x 32 (c) LDS transpose of std_apply_transpose_kernel with Tv / Cv as the source extent and Tout / Cout as the
+// destination's: padding rows and extra channels are written as zeros, 128-byte writes along c.
+//
+// LDS of pass 1: q * Lp + Tv floats with Lp = ceil((Tin + 2R) / q) + EP_J - 1  (20 KB at Tin = 2000, M = 1023, q = 1; 17 KB at
+// Tin = 1651, M = 1023); rows beyond 64 KB are refused (IGN_E_TOOBIG).  No thread reads outside [0, Tin) of its row: the staging
+// loop is the only reader of x and maps every extended index into the row or to a literal zero.
+#include "ign_common.h"
+
+namespace {
+constexpr int EP_THREADS = 256, EP_J = 5, EP_U = 8;
+constexpr size_t EP_LDS_MAX = 64 * 1024;
+
+struct EpPlan {
+    int R, Td, Tv, Cv, Lp;
+    size_t lds;
+};
+
+EpPlan ep_plan(int Cin, int Tin, int M, int q, int Cout, int Tout) {
+    EpPlan p;
+    p.R = (M - 1) / 2;
+    p.Td = (Tin + q - 1) / q;
+    p.Tv = p.Td < Tout ? p.Td : Tout;
+    p.Cv = Cin < Cout ? Cin : Cout;
+    p.Lp = (Tin + 2 * p.R + q - 1) / q + EP_J - 1;
+    p.lds = ((size_t)q * p.Lp + (size_t)(p.Tv > 0 ? p.Tv : 0)) * sizeof(float);
+    return p;
+}
+
+}  // namespace
+
+__global__ void __launch_bounds__(EP_THREADS) eeg_filter_standardise_kernel(const float* __restrict__ x, const float* __restrict__ h,
+                                                                            float* __restrict__ ws, int Cin, int Tin, int M, int q,
+                                                                            int reflect, int Cv, int Tv, int Lp, float eps) {
+    extern __shared__ __attribute__((aligned(16))) float ep_lds[];
+    __shared__ float stat[2];                          // mean, 1 / (std + eps)
+    float* xp = ep_lds;                                // q phase arrays of Lp floats
+    float* fs = ep_lds + (size_t)q * Lp;               // the filtered row, Tv floats
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x / Cv, c = blockIdx.x - b * Cv;
+    const float* xr = x + ((size_t)b * Cin + c) * Tin;
+    const int R2 = M - 1, R = R2 >> 1, next = Tin + R2;
+    const float pivot = (reflect && R > 0) ? xr[0] : 0.f;
+
+    // the extended row, phase-split: coalesced reads of the row itself, halo indices folded back into [0, Tin) or left zero
+    for (int i = tid; i < next; i += EP_THREADS) {
+        int src = i - R;
+        float v = 0.f;
+        if (reflect) {
+            if (src < 0) src = -src;                   // R <= Tin - 1: one fold is enough on either side
+            if (src >= Tin) src = 2 * (Tin - 1) - src;
+            v = xr[src] - pivot;
+        } else if (src >= 0 && src < Tin) {
+            v = xr[src];
+        }
+        const int m = i / q;
+        xp[(i - m * q) * Lp + m] = v;
+    }
+    // the tail of every phase array (what the last lane's spare outputs touch) is zero
+    for (int s = tid; s < q * Lp; s += EP_THREADS) {
+        const int p = s / Lp, m = s - p * Lp;
+        if (m * q + p >= next) xp[s] = 0.f;
+    }
+    __syncthreads();
+
+    const int wave0 = __builtin_amdgcn_readfirstlane(tid & ~63);
+    for (int base = 0; base < Tv; base += EP_THREADS * EP_J) {
+        if (base + wave0 * EP_J >= Tv) continue;       // a wave without outputs in this sweep (wave-uniform)
+        const int n0 = base + tid * EP_J;
+        const int nr = n0 < Tv ? n0 : 0;               // spare lanes recompute the first outputs and store nothing
+        float acc[EP_J];
+#pragma unroll
+        for (int j = 0; j < EP_J; ++j) acc[j] = 0.f;
+        for (int p = 0; p < q && p <= R2; ++p) {
+            const float* xq = xp + p * Lp + nr;
+            const float* g = h + (R2 - p);             // sub-tap i of phase p is g[-i * q]
+            const int np = (R2 - p) / q + 1;
+            int i0 = 0;
+            for (; i0 + EP_U <= np; i0 += EP_U) {
+                float v[EP_U + EP_J - 1];
+#pragma unroll
+                for (int u = 0; u < EP_U + EP_J - 1; ++u) v[u] = xq[i0 + u];
+#pragma unroll
+                for (int u = 0; u < EP_U; ++u) {
+                    const float hv = g[-(i0 + u) * q];
+#pragma unroll
+                    for (int j = 0; j < EP_J; ++j) acc[j] = fmaf(hv, v[u + j], acc[j]);
+                }
+            }
+            for (; i0 < np; ++i0) {
+                const float hv = g[-i0 * q];
+#pragma unroll
+                for (int j = 0; j < EP_J; ++j) acc[j] = fmaf(hv, xq[i0 + j], acc[j]);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < EP_J; ++j)
+            if (n0 + j < Tv) fs[n0 + j] = acc[j];
+    }
+    __syncthreads();
+
+    // mean and unbiased standard deviation in two sweeps over LDS (no E[x^2] - E[x]^2), by wave 0 in std_rowstats_kernel's order
+    if (tid < 64) {
+        float s = 0.f;
+        for (int t = tid; t < Tv; t += 64) s += fs[t];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        const float mu = s / (float)Tv;
+        float v = 0.f;
+        for (int t = tid; t < Tv; t += 64) {
+            const float dv = fs[t] - mu;
+            v = fmaf(dv, dv, v);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        if (tid == 0) {
+            stat[0] = mu;
+            stat[1] = 1.f / (sqrtf(v / (float)(Tv - 1)) + eps);                        // ddof = 1, eps outside the sqrt
+        }
+    }
+    __syncthreads();
+    const float mean = stat[0], rstd = stat[1];
+    float* wr = ws + (size_t)blockIdx.x * Tv;
+    for (int t = tid; t < Tv; t += EP_THREADS) wr[t] = (fs[t] - mean) * rstd;
+}
+
+// ws (B, Cv, Tv) standardised rows -> out (B, Tout, Cout); zeros for t >= Tv and c >= Cv
+__global__ void __launch_bounds__(256) eeg_fit_transpose_kernel(const float* __restrict__ ws, float* __restrict__ out, int Cv, int Tv,
+                                                                int Cout, int Tout) {
+    __shared__ float tile[32][65];
+    const int b = blockIdx.z, c0 = blockIdx.y * 32, t0 = blockIdx.x * 64;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int cc = w * 8 + i, c = c0 + cc, t = t0 + lane;
+        tile[cc][lane] = (c < Cv && t < Tv) ? ws[((size_t)b * Cv + c) * Tv + t] : 0.f;
+    }
+    __syncthreads();
+    const int cc = threadIdx.x & 31, tr = threadIdx.x >> 5;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int tl = tr * 8 + i, t = t0 + tl, c = c0 + cc;
+        if (t < Tout && c < Cout) out[((size_t)b * Tout + t) * Cout + c] = tile[cc][tl];
+    }
+}
+
+static const char* ep_check(const char* who, int B, int Cin, int Tin, int M, int q, int edge, int Cout, int Tout, bool need_edge) {
+    if (B <= 0 || Cin <= 0 || Tin <= 0 || Cout <= 0 || Tout <= 0) {
+        ign_set_error("%s: non-positive dimension (B=%d Cin=%d Tin=%d Cout=%d Tout=%d)", who, B, Cin, Tin, Cout, Tout);
+        return "dim";
+    }
+    if (M < 1 || (M & 1) == 0 || M > IGN_EEG_MAX_TAPS) {
+        ign_set_error("%s: M=%d taps; the centred filter needs an odd count in 1..%d", who, M, IGN_EEG_MAX_TAPS);
+        return "taps";
+    }
+    if (q < 1 || q > IGN_EEG_MAX_DECIMATE) {
+        ign_set_error("%s: decimation factor q=%d outside 1..%d", who, q, IGN_EEG_MAX_DECIMATE);
+        return "q";
+    }
+    if (!need_edge) return nullptr;
+    if (edge != IGN_EDGE_REFLECT && edge != IGN_EDGE_ZERO) {
+        ign_set_error("%s: edge=%d is neither IGN_EDGE_REFLECT nor IGN_EDGE_ZERO", who, edge);
+        return "edge";
+    }
+    if (edge == IGN_EDGE_REFLECT && (M - 1) / 2 >= Tin) {
+        ign_set_error("%s: reflect extension by R=%d needs a row of at least R+1 samples, Tin=%d", who, (M - 1) / 2, Tin);
+        return "reflect";
+    }
+    return nullptr;
+}
+
+extern "C" size_t ign_eeg_preprocess_ws_bytes(int B, int Cin, int Tin, int M, int q, int Cout, int Tout) {
+    if (ep_check("ign_eeg_preprocess_ws_bytes", B, Cin, Tin, M, q, 0, Cout, Tout, false)) return 0;
+    const EpPlan p = ep_plan(Cin, Tin, M, q, Cout, Tout);
+    return (size_t)B * p.Cv * p.Tv * sizeof(float);
+}
+
+extern "C" int ign_eeg_preprocess_nct_to_btc(const float* x_nct, const float* taps, float* out_btc, float* ws, int B, int Cin, int Tin,
+                                             int M, int q, int edge, int Cout, int Tout, float eps, void* stream) {
+    static const char* who = "ign_eeg_preprocess_nct_to_btc";
+    if (!x_nct || !taps || !out_btc || !ws) {
+        ign_set_error("%s: null pointer", who);
+        return IGN_E_ARG;
+    }
+    if (ep_check(who, B, Cin, Tin, M, q, edge, Cout, Tout, true)) return IGN_E_ARG;
+    const EpPlan p = ep_plan(Cin, Tin, M, q, Cout, Tout);
+    if (p.Tv < 2) {
+        ign_set_error("%s: Tv = min(ceil(Tin/q), Tout) = %d; the unbiased std needs Tv >= 2 (Tin=%d q=%d Tout=%d)", who, p.Tv, Tin, q,
+                      Tout);
+        return IGN_E_ARG;
+    }
+    if (p.lds > EP_LDS_MAX) {
+        ign_set_error("%s: a row of Tin=%d with M=%d taps needs %zu bytes of LDS, more than %zu", who, Tin, M, p.lds, EP_LDS_MAX);
+        return IGN_E_TOOBIG;
+    }
+    if (B > 65535 || (long long)B * p.Cv > 0x7fffffffLL) {
+        ign_set_error("%s: B=%d exceeds the launch grid (65535 samples per call)", who, B);
+        return IGN_E_TOOBIG;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    IgnScopedTimer tm("eeg_preprocess", s);
+    hipLaunchKernelGGL(eeg_filter_standardise_kernel, dim3((unsigned)(B * p.Cv)), dim3(EP_THREADS), p.lds, s, x_nct, taps, ws, Cin, Tin,
+                       M, q, edge == IGN_EDGE_REFLECT ? 1 : 0, p.Cv, p.Tv, p.Lp, eps);
+    int rc;
+    if ((rc = ign_check_launch("eeg_filter_standardise_kernel"))) return rc;
+    hipLaunchKernelGGL(eeg_fit_transpose_kernel, dim3((Tout + 63) / 64, (Cout + 31) / 32, B), dim3(256), 0, s, ws, out_btc, p.Cv, p.Tv,
+                       Cout, Tout);
+    return ign_check_launch("eeg_fit_transpose_kernel");
+}

@@ -62,8 +62,12 @@ def data_provider(args, flag, bin_edges=None):
     elif args.data in ('EEG', 'EEG3'):
         # on a GPU the items stay RAW and the batch is standardised + transposed on the device (device_prefetch.py)
         raw = bool(getattr(args, 'device_standardise', torch.cuda.is_available()))
+        from utils.eeg_filter import parse_eeg_preprocess
+        pre = parse_eeg_preprocess(getattr(args, 'eeg_preprocess', None))
+        extra = dict(preprocess=pre, target_channels=getattr(args, 'target_channels', None),
+                     target_timepoints=getattr(args, 'target_timepoints', None)) if pre.active else {}
         data_set = Data(root_path=args.root_path, flag=flag, test_size=getattr(args, 'test_size', 0.2),
-                        val_size=getattr(args, 'val_size', 0.1), raw=raw)
+                        val_size=getattr(args, 'val_size', 0.1), raw=raw, **extra)
     else:
         data_set = Data(root_path=args.root_path, flag=flag)
 
@@ -82,6 +86,8 @@ def data_provider(args, flag, bin_edges=None):
                         num_workers=args.num_workers, drop_last=False, pin_memory=torch.cuda.is_available(),
                         collate_fn=collate_raw if raw else (lambda b: collate_fn(b, max_len=max_len)))
     loader.device_transform = 'standardise_raw' if raw else None
+    if raw and getattr(data_set, 'pre', None) is not None:          # --eeg_preprocess: the resolved spec travels with the loader
+        loader.device_transform, loader.eeg_preprocess = 'eeg_preprocess', data_set.pre
     return data_set, loader
 
 

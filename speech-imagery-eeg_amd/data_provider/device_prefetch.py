@@ -5,7 +5,8 @@ per-item CPU normalisation in the DataLoader workers become the bottleneck (a 25
 over PCIe Gen5, and ~0.5 ms of CPU z-scoring per sample).  ``DevicePrefetcher`` wraps any DataLoader of the batch contract
 ``(X, y, mask)``: batch i+1 is pinned and copied on a side HIP stream while batch i trains; an optional ``transform`` runs
 on that stream too -- for the CHISCO shards the loader ships RAW (B,C,T) microvolt tensors and the per-sample
-standardisation + transpose happen on the GPU (``ops.standardise_nct_to_btc``).  On a CPU device it is a pass-through.
+standardisation + transpose happen on the GPU (``ops.standardise_nct_to_btc``; with ``--eeg_preprocess`` the filter, decimation
+and fitting in front of it too: ``ops.eeg_preprocess``).  On a CPU device it is a pass-through.
 """
 import torch
 
@@ -16,6 +17,21 @@ def standardise_raw_batch(batch):
     x, y, _ = batch
     xs = ops.standardise_nct_to_btc(x.float())
     return xs, y, torch.ones(xs.shape[0], xs.shape[1], device=xs.device, dtype=torch.bool)
+
+
+def preprocess_raw_batch(pre, device):
+    """transform for raw loaders under --eeg_preprocess, built once per loader: `pre` is the data set's resolved spec
+    (utils.eeg_filter.Resolved); its taps go to the device here, once.  (X[B,Cin,Tin], y, None) ->
+    (X[B,Tout,Cout] filtered, decimated, fitted and standardised, y, mask[B,Tout] = t < Tv)."""
+    from ign_hip import ops
+    taps = torch.as_tensor(pre.taps, dtype=torch.float32).to(device)
+    kw = dict(decimate=pre.q, edge=pre.edge, channels=pre.Cout, timepoints=pre.Tout)
+
+    def transform(batch):
+        x, y, _ = batch
+        xs, mask = ops.eeg_preprocess(x.float(), taps, **kw)
+        return xs, y, mask
+    return transform
 
 
 class DevicePrefetcher:

@@ -69,7 +69,8 @@ def split_indices(n, flag, test_size=0.2, val_size=0.1, seed=42):
 class EEGNpyDataset(Dataset):
     num_label_classes = 39
 
-    def __init__(self, root_path, flag='train', label_map=None, test_size=0.2, val_size=0.1, mmap=True, raw=False, **_):
+    def __init__(self, root_path, flag='train', label_map=None, test_size=0.2, val_size=0.1, mmap=True, raw=False,
+                 preprocess=None, target_channels=None, target_timepoints=None, **_):
         self.raw = bool(raw)      # True: items are RAW (C,T) recordings; the batch is standardised on the GPU instead
         xp, yp = os.path.join(root_path, "X.npy"), os.path.join(root_path, "y.npy")
         if not (os.path.exists(xp) and os.path.exists(yp)):
@@ -86,6 +87,15 @@ class EEGNpyDataset(Dataset):
         self.X, self.y, self.idx = X, y, idx
         self.enc_in, self.seq_len = int(X.shape[1]), int(X.shape[2])
         self.num_classes = int(y.max()) + 1 if label_map is None else len(set(label_map.values()))
+        self.pre = None           # --eeg_preprocess: filter / decimate / fit in front of the standardisation (utils/eeg_filter.py)
+        if preprocess is not None:
+            from utils.eeg_filter import parse_eeg_preprocess, resolve
+            spec = parse_eeg_preprocess(preprocess)
+            if spec.active:
+                # the models are built for what the items become: Tout time steps of Cout channels
+                self.pre = resolve(spec, self.enc_in, self.seq_len, target_channels, target_timepoints,
+                                   notice=print if flag == 'train' else None)
+                self.enc_in, self.seq_len = self.pre.Cout, self.pre.Tout
 
     def __len__(self):
         return len(self.idx)
@@ -94,8 +104,13 @@ class EEGNpyDataset(Dataset):
         j = self.idx[i]
         x = np.asarray(self.X[j], dtype=np.float32)
         y = torch.tensor([self.y[j]], dtype=torch.int64)
-        if self.raw:              # device pipeline: data_provider.device_prefetch.standardise_raw_batch does the rest
+        if self.raw:              # device pipeline: data_provider.device_prefetch does the rest on the batch
             return torch.from_numpy(np.ascontiguousarray(x)), y
+        if self.pre is not None:  # (Tv, Cout): collate_fn(max_len=seq_len) pads the time axis and builds the mask
+            from utils.eeg_filter import preprocess_numpy
+            p = self.pre
+            return torch.from_numpy(preprocess_numpy(x, p.taps.astype(np.float32), p.q, p.edge, p.Cout, p.Tout)
+                                    .astype(np.float32)), y
         return torch.from_numpy(per_sample_standardise(x).T.copy()), y
 
 

@@ -23,7 +23,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from data_provider.data_factory import data_provider
-from data_provider.device_prefetch import DevicePrefetcher, standardise_raw_batch
+from data_provider.device_prefetch import DevicePrefetcher, preprocess_raw_batch, standardise_raw_batch
 from ign_hip import ddp as ign_ddp
 from ign_hip import ops as ign_ops
 from ign_hip.ddp import FlatAdam, FlatParamBucket
@@ -197,7 +197,10 @@ class Experiment(object):
                 dist.broadcast(buf.data, src=src)
 
     def _prefetch(self, loader):
-        transform = standardise_raw_batch if getattr(loader, 'device_transform', None) == 'standardise_raw' else None
+        kind = getattr(loader, 'device_transform', None)
+        transform = standardise_raw_batch if kind == 'standardise_raw' else None
+        if kind == 'eeg_preprocess':                    # --eeg_preprocess: filter, decimate, fit, then the same standardisation
+            transform = preprocess_raw_batch(loader.eeg_preprocess, self.device)
         if self.device.type != 'cuda' and transform is None:
             return loader
         return DevicePrefetcher(loader, self.device, transform=transform)

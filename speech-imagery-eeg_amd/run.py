@@ -16,6 +16,10 @@ Differences, all repairs of fork defects listed in SURVEY section 0:
   * ``--augment shift=0.1,scale=0.1,noise=0.05,chan_drop=0.1,time_mask=0.1`` (any subset) augments every TRAINING batch on the
     device in one fused launch: circular shift, per-channel gain, Gaussian noise, electrode dropout, one masked time span, each
     inside the sample's own length; validation / test never augment; the default ``none`` changes nothing;
+  * ``--eeg_preprocess band=8:30,decimate=2,fit`` (``--data EEG`` / ``EEG3``; any subset of sfreq=F, band=LO:HI, decimate=Q, taps=M,
+    edge=reflect|zero, fit) filters the raw CHISCO shards with a zero-phase FIR band-pass, decimates them and, with ``fit``, crops /
+    zero-pads them to ``--target_channels`` x ``--target_timepoints`` in front of the standardisation -- on the device in the
+    prefetcher (two HIP passes), in numpy on the CPU item path; the default ``none`` changes nothing and leaves ``--target_*`` inert;
   * ``--task_name regression --data Monash`` is the reference's regression twin (exp/experiment_regression.py), with the
     repairs R1-R3 of DESIGN 2.3;
   * multi-GPU is one process per GPU: ``python -m torch.distributed.run --nproc-per-node N run.py ...``.
@@ -106,6 +110,13 @@ def build_parser():
                         "shift=R (circular shift by up to R * length), scale=R (per-channel gain in 1 +- R; the SBM's instance norm "
                         "cancels it, the DNN experts see it), noise=SIGMA (Gaussian), chan_drop=P (electrodes zeroed, no rescaling), "
                         "time_mask=R (one zeroed span of up to R * length per sample); rates in [0, 1).  Reproducible from --seed")
+    p.add_argument("--eeg_preprocess", type=str, default='none',
+                   help="--data EEG / EEG3: preprocessing of the raw shards in front of the standardisation, on the device: none, or a "
+                        "comma list of sfreq=F (Hz, default 500), band=LO:HI (Hz, either side may be empty), decimate=Q, taps=M "
+                        "(odd, <= 1023; default 20Q+1 when only decimating, else 3.3*sfreq/lowest edge), edge=reflect|zero, and fit "
+                        "(output shape --target_channels x --target_timepoints, cropped / zero-padded and masked; without it "
+                        "channels x ceil(T/Q)).  A zero-phase Hamming windowed-sinc FIR filter; an upper edge above sfreq/(2Q) is "
+                        "refused")
     # experiment
     p.add_argument("--lr", type=float, default=5e-3)
     p.add_argument("--lr_decay", action="store_true")
@@ -159,6 +170,9 @@ def check_args(args):
     check_loss_options(args, _num_class_from_flags(args))
     from utils.augment import parse_augment
     parse_augment(getattr(args, 'augment', None))
+    from utils.eeg_filter import parse_eeg_preprocess
+    if parse_eeg_preprocess(getattr(args, 'eeg_preprocess', None)).active and getattr(args, 'data', None) not in ('EEG', 'EEG3'):
+        raise ValueError(f"--eeg_preprocess filters the raw CHISCO shards (--data EEG / EEG3), not --data {args.data}")
 
 
 def _num_class_from_flags(args):
