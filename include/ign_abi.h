@@ -94,6 +94,25 @@ size_t ign_eeg_preprocess_ws_bytes(int B, int Cin, int Tin, int M, int q, int Co
 int ign_eeg_preprocess_nct_to_btc(const float* x_nct, const float* taps, float* out_btc, float* ws, int B, int Cin, int Tin, int M,
                                   int q, int edge, int Cout, int Tout, float eps, void* stream);
 
+/* The same pass for a filter bank (run.py --eeg_preprocess bank=... / envelope; ops.eeg_filterbank; numpy restatement
+ * utils/eeg_filter.py:filterbank_numpy): nb bands with one common odd M, taps (nb,M) and optional quadrature taps quad (nb,M), both
+ * fp32 on the DEVICE.  Per band j and row (b,c), with x~, the reflect pivot, R, q, Td, Tv as above:
+ *   a_j[n] = sum_k taps[j,k] * x~[n*q + R - k]          (the arithmetic of ign_eeg_preprocess_nct_to_btc, in its order)
+ *   quad == NULL:  f_j = a_j;   else  b_j[n] = the same sum with quad[j,k],  f_j[n] = sqrtf(fmaf(a_j[n], a_j[n], b_j[n] * b_j[n]))
+ *   f_j[0..Tv-1] standardised, cropped and zero-padded as above.
+ * out (B,Tout,nb*Cout) is BAND-MAJOR: channel j*Cout + c is electrode c of band j; every band block is cropped / zero-padded to Cout
+ * electrodes on its own (exact zeros for c >= min(Cin,Cout) and for t >= Tv).  Without quad, block j is what
+ * ign_eeg_preprocess_nct_to_btc returns for taps[j], bit for bit.  The extended row is staged once per (b,c) and every band runs
+ * over it; fixed summation order, no atomics: two calls give the same bits.
+ * ws: ign_eeg_filterbank_ws_bytes() bytes (B * nb * min(Cin,Cout) * Tv floats; 0 for arguments the launcher refuses).
+ * IGN_E_ARG: nb outside 1..IGN_EEG_MAX_BANDS, quad with IGN_EDGE_ZERO (without the pivot the recording's offset times sum(taps[j])
+ * enters the square root and the standardisation cannot remove it), quad with M == 1, and everything the one-band launcher refuses.
+ * IGN_E_TOOBIG as above (the LDS need does not depend on nb).  Nothing is launched on an error.                                */
+#define IGN_EEG_MAX_BANDS 8
+size_t ign_eeg_filterbank_ws_bytes(int B, int Cin, int Tin, int M, int nb, int q, int Cout, int Tout);
+int ign_eeg_filterbank_nct_to_btc(const float* x_nct, const float* taps, const float* quad, float* out_btc, float* ws, int B, int Cin,
+                                  int Tin, int M, int nb, int q, int edge, int Cout, int Tout, float eps, void* stream);
+
 /* Shapelet transform of ONE length group: sliding-window distance + gate, never materialising (B,Tw,K,C,L).
  * Replaces IGN/model/Shapelet.py:60-84 (GATE_RBF) / :96-111 (GATE_LTS).   Tw = (T-L)/stride + 1.
  *   xn_bct   (B,C,T)    normalised input

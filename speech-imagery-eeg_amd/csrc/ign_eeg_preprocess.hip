@@ -25,6 +25,13 @@
 // LDS of pass 1: q * Lp + Tv floats with Lp = ceil((Tin + 2R) / q) + EP_J - 1  (20 KB at Tin = 2000, M = 1023, q = 1; 17 KB at
 // Tin = 1651, M = 1023); rows beyond 64 KB are refused (IGN_E_TOOBIG).  No thread reads outside [0, Tin) of its row: the staging
 // loop is the only reader of x and maps every extended index into the row or to a literal zero.
+//
+// The filter bank (ign_eeg_filterbank_nct_to_btc; ops.eeg_filterbank; utils/eeg_filter.py:filterbank_numpy) is the same pass for nb <= 8
+// bands with one common M: the row is staged once and every band's taps (nb, M) run over it -- the same tap walk, statistics and
+// output line per band, so block j of the band-major output (B, Tout, nb * Cout) is the one-band result for taps[j] bit for bit.  With
+// quadrature taps a second accumulator set runs over the same LDS values and the band's output is sqrtf(fmaf(a, a, b * b)) before the
+// statistics (reflect mode only: the pivot keeps the recording's offset, which the standardisation could not remove from under a
+// square root, out of a).  LDS does not depend on nb; the workspace rows are (b, j, c).
 #include "ign_common.h"
 
 namespace {
@@ -49,20 +56,11 @@ EpPlan ep_plan(int Cin, int Tin, int M, int q, int Cout, int Tout) {
 
 }  // namespace
 
-__global__ void __launch_bounds__(EP_THREADS) eeg_filter_standardise_kernel(const float* __restrict__ x, const float* __restrict__ h,
-                                                                            float* __restrict__ ws, int Cin, int Tin, int M, int q,
-                                                                            int reflect, int Cv, int Tv, int Lp, float eps) {
-    extern __shared__ __attribute__((aligned(16))) float ep_lds[];
-    __shared__ float stat[2];                          // mean, 1 / (std + eps)
-    float* xp = ep_lds;                                // q phase arrays of Lp floats
-    float* fs = ep_lds + (size_t)q * Lp;               // the filtered row, Tv floats
-    const int tid = threadIdx.x;
-    const int b = blockIdx.x / Cv, c = blockIdx.x - b * Cv;
-    const float* xr = x + ((size_t)b * Cin + c) * Tin;
-    const int R2 = M - 1, R = R2 >> 1, next = Tin + R2;
-    const float pivot = (reflect && R > 0) ? xr[0] : 0.f;
-
-    // the extended row, phase-split: coalesced reads of the row itself, halo indices folded back into [0, Tin) or left zero
+// The three steps of pass 1, shared by the one-band kernel and the filter bank (always inlined: one arithmetic, one order).
+// ep_stage_row: the extended row, phase-split: coalesced reads of the row itself, halo indices folded back into [0, Tin) or left
+// zero; the tail of every phase array (what the last lane's spare outputs touch) is zero.  The caller's barrier follows.
+__device__ __forceinline__ void ep_stage_row(const float* __restrict__ xr, float* xp, int Tin, int R, int next, int q, int Lp,
+                                             int reflect, float pivot, int tid) {
     for (int i = tid; i < next; i += EP_THREADS) {
         int src = i - R;
         float v = 0.f;
@@ -76,24 +74,29 @@ __global__ void __launch_bounds__(EP_THREADS) eeg_filter_standardise_kernel(cons
         const int m = i / q;
         xp[(i - m * q) * Lp + m] = v;
     }
-    // the tail of every phase array (what the last lane's spare outputs touch) is zero
     for (int s = tid; s < q * Lp; s += EP_THREADS) {
         const int p = s / Lp, m = s - p * Lp;
         if (m * q + p >= next) xp[s] = 0.f;
     }
-    __syncthreads();
+}
 
+// ep_filter_row: f[0..Tv-1] of one tap set into fs, EP_J outputs per lane, sub-taps in blocks of EP_U.  With QUAD a second
+// accumulator set runs the quadrature taps hq over the same LDS values and fs gets sqrtf(fmaf(a, a, b * b)).  Reads xp, writes fs.
+template <bool QUAD>
+__device__ __forceinline__ void ep_filter_row(const float* xp, float* fs, const float* __restrict__ h, const float* __restrict__ hq,
+                                              int q, int R2, int Lp, int Tv, int tid) {
     const int wave0 = __builtin_amdgcn_readfirstlane(tid & ~63);
     for (int base = 0; base < Tv; base += EP_THREADS * EP_J) {
         if (base + wave0 * EP_J >= Tv) continue;       // a wave without outputs in this sweep (wave-uniform)
         const int n0 = base + tid * EP_J;
         const int nr = n0 < Tv ? n0 : 0;               // spare lanes recompute the first outputs and store nothing
-        float acc[EP_J];
+        float acc[EP_J], bcc[EP_J];
 #pragma unroll
-        for (int j = 0; j < EP_J; ++j) acc[j] = 0.f;
+        for (int j = 0; j < EP_J; ++j) acc[j] = bcc[j] = 0.f;
         for (int p = 0; p < q && p <= R2; ++p) {
             const float* xq = xp + p * Lp + nr;
             const float* g = h + (R2 - p);             // sub-tap i of phase p is g[-i * q]
+            const float* gq = QUAD ? hq + (R2 - p) : nullptr;
             const int np = (R2 - p) / q + 1;
             int i0 = 0;
             for (; i0 + EP_U <= np; i0 += EP_U) {
@@ -105,21 +108,33 @@ __global__ void __launch_bounds__(EP_THREADS) eeg_filter_standardise_kernel(cons
                     const float hv = g[-(i0 + u) * q];
 #pragma unroll
                     for (int j = 0; j < EP_J; ++j) acc[j] = fmaf(hv, v[u + j], acc[j]);
+                    if (QUAD) {
+                        const float qv = gq[-(i0 + u) * q];
+#pragma unroll
+                        for (int j = 0; j < EP_J; ++j) bcc[j] = fmaf(qv, v[u + j], bcc[j]);
+                    }
                 }
             }
             for (; i0 < np; ++i0) {
                 const float hv = g[-i0 * q];
 #pragma unroll
                 for (int j = 0; j < EP_J; ++j) acc[j] = fmaf(hv, xq[i0 + j], acc[j]);
+                if (QUAD) {
+                    const float qv = gq[-i0 * q];
+#pragma unroll
+                    for (int j = 0; j < EP_J; ++j) bcc[j] = fmaf(qv, xq[i0 + j], bcc[j]);
+                }
             }
         }
 #pragma unroll
         for (int j = 0; j < EP_J; ++j)
-            if (n0 + j < Tv) fs[n0 + j] = acc[j];
+            if (n0 + j < Tv) fs[n0 + j] = QUAD ? sqrtf(fmaf(acc[j], acc[j], bcc[j] * bcc[j])) : acc[j];
     }
-    __syncthreads();
+}
 
-    // mean and unbiased standard deviation in two sweeps over LDS (no E[x^2] - E[x]^2), by wave 0 in std_rowstats_kernel's order
+// ep_row_stats: mean and unbiased standard deviation in two sweeps over LDS (no E[x^2] - E[x]^2), by wave 0 in
+// std_rowstats_kernel's order; stat = {mean, 1 / (std + eps)}.  Between the caller's two barriers.
+__device__ __forceinline__ void ep_row_stats(const float* fs, float* stat, int Tv, float eps, int tid) {
     if (tid < 64) {
         float s = 0.f;
         for (int t = tid; t < Tv; t += 64) s += fs[t];
@@ -138,10 +153,66 @@ __global__ void __launch_bounds__(EP_THREADS) eeg_filter_standardise_kernel(cons
             stat[1] = 1.f / (sqrtf(v / (float)(Tv - 1)) + eps);                        // ddof = 1, eps outside the sqrt
         }
     }
+}
+
+__global__ void __launch_bounds__(EP_THREADS) eeg_filter_standardise_kernel(const float* __restrict__ x, const float* __restrict__ h,
+                                                                            float* __restrict__ ws, int Cin, int Tin, int M, int q,
+                                                                            int reflect, int Cv, int Tv, int Lp, float eps) {
+    extern __shared__ __attribute__((aligned(16))) float ep_lds[];
+    __shared__ float stat[2];                          // mean, 1 / (std + eps)
+    float* xp = ep_lds;                                // q phase arrays of Lp floats
+    float* fs = ep_lds + (size_t)q * Lp;               // the filtered row, Tv floats
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x / Cv, c = blockIdx.x - b * Cv;
+    const float* xr = x + ((size_t)b * Cin + c) * Tin;
+    const int R2 = M - 1, R = R2 >> 1, next = Tin + R2;
+    const float pivot = (reflect && R > 0) ? xr[0] : 0.f;
+
+    ep_stage_row(xr, xp, Tin, R, next, q, Lp, reflect, pivot, tid);
+    __syncthreads();
+    ep_filter_row<false>(xp, fs, h, nullptr, q, R2, Lp, Tv, tid);
+    __syncthreads();
+    ep_row_stats(fs, stat, Tv, eps, tid);
     __syncthreads();
     const float mean = stat[0], rstd = stat[1];
     float* wr = ws + (size_t)blockIdx.x * Tv;
     for (int t = tid; t < Tv; t += EP_THREADS) wr[t] = (fs[t] - mean) * rstd;
+}
+
+// The filter bank: the row is staged once, then every band's taps run over it.  Three barriers per band:
+//   A  after the tap walk: fs of band j is complete before wave 0 sums it;
+//   B  after the statistics: stat of band j is visible before the line is written out;
+//   C  at the head of band j + 1: every thread has read fs of band j (its part of the output line) before any lane overwrites it
+//      with band j + 1.  stat needs no barrier of its own: wave 0 writes band j + 1's after A of that band, which every thread
+//      reaches only after it has read band j's.  xp is read-only after the staging barrier.
+// Rows of the workspace are (b, j, c): band-major inside a sample, as the output's channels are.
+template <bool QUAD>
+__global__ void __launch_bounds__(EP_THREADS) eeg_filterbank_kernel(const float* __restrict__ x, const float* __restrict__ h,
+                                                                    const float* __restrict__ hq, float* __restrict__ ws, int Cin,
+                                                                    int Tin, int M, int nb, int q, int reflect, int Cv, int Tv, int Lp,
+                                                                    float eps) {
+    extern __shared__ __attribute__((aligned(16))) float ep_lds[];
+    __shared__ float stat[2];
+    float* xp = ep_lds;
+    float* fs = ep_lds + (size_t)q * Lp;
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x / Cv, c = blockIdx.x - b * Cv;
+    const float* xr = x + ((size_t)b * Cin + c) * Tin;
+    const int R2 = M - 1, R = R2 >> 1, next = Tin + R2;
+    const float pivot = (reflect && R > 0) ? xr[0] : 0.f;
+
+    ep_stage_row(xr, xp, Tin, R, next, q, Lp, reflect, pivot, tid);
+    __syncthreads();
+    for (int j = 0; j < nb; ++j) {
+        if (j > 0) __syncthreads();                                                    // C
+        ep_filter_row<QUAD>(xp, fs, h + (size_t)j * M, QUAD ? hq + (size_t)j * M : nullptr, q, R2, Lp, Tv, tid);
+        __syncthreads();                                                               // A
+        ep_row_stats(fs, stat, Tv, eps, tid);
+        __syncthreads();                                                               // B
+        const float mean = stat[0], rstd = stat[1];
+        float* wr = ws + (((size_t)b * nb + j) * Cv + c) * Tv;
+        for (int t = tid; t < Tv; t += EP_THREADS) wr[t] = (fs[t] - mean) * rstd;
+    }
 }
 
 // ws (B, Cv, Tv) standardised rows -> out (B, Tout, Cout); zeros for t >= Tv and c >= Cv
@@ -161,6 +232,29 @@ __global__ void __launch_bounds__(256) eeg_fit_transpose_kernel(const float* __r
     for (int i = 0; i < 8; ++i) {
         const int tl = tr * 8 + i, t = t0 + tl, c = c0 + cc;
         if (t < Tout && c < Cout) out[((size_t)b * Tout + t) * Cout + c] = tile[cc][tl];
+    }
+}
+
+// ws (B, nb, Cv, Tv) -> out (B, Tout, nb * Cout), band-major: destination channel cd = j * Cout + c; a 32-channel tile may
+// straddle band blocks, so j and c are per lane
+__global__ void __launch_bounds__(256) eeg_bank_transpose_kernel(const float* __restrict__ ws, float* __restrict__ out, int nb, int Cv,
+                                                                 int Tv, int Cout, int Tout) {
+    __shared__ float tile[32][65];
+    const int b = blockIdx.z, c0 = blockIdx.y * 32, t0 = blockIdx.x * 64;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int Ctot = nb * Cout;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int cc = w * 8 + i, cd = c0 + cc, t = t0 + lane;
+        const int j = cd / Cout, c = cd - j * Cout;
+        tile[cc][lane] = (cd < Ctot && c < Cv && t < Tv) ? ws[(((size_t)b * nb + j) * Cv + c) * Tv + t] : 0.f;
+    }
+    __syncthreads();
+    const int cc = threadIdx.x & 31, tr = threadIdx.x >> 5;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int tl = tr * 8 + i, t = t0 + tl, cd = c0 + cc;
+        if (t < Tout && cd < Ctot) out[((size_t)b * Tout + t) * Ctot + cd] = tile[cc][tl];
     }
 }
 
@@ -226,4 +320,69 @@ extern "C" int ign_eeg_preprocess_nct_to_btc(const float* x_nct, const float* ta
     hipLaunchKernelGGL(eeg_fit_transpose_kernel, dim3((Tout + 63) / 64, (Cout + 31) / 32, B), dim3(256), 0, s, ws, out_btc, p.Cv, p.Tv,
                        Cout, Tout);
     return ign_check_launch("eeg_fit_transpose_kernel");
+}
+
+static bool ep_bank_check(const char* who, int nb) {
+    if (nb < 1 || nb > IGN_EEG_MAX_BANDS) {
+        ign_set_error("%s: nb=%d bands outside 1..%d", who, nb, IGN_EEG_MAX_BANDS);
+        return false;
+    }
+    return true;
+}
+
+extern "C" size_t ign_eeg_filterbank_ws_bytes(int B, int Cin, int Tin, int M, int nb, int q, int Cout, int Tout) {
+    static const char* who = "ign_eeg_filterbank_ws_bytes";
+    if (!ep_bank_check(who, nb) || ep_check(who, B, Cin, Tin, M, q, 0, Cout, Tout, false)) return 0;
+    const EpPlan p = ep_plan(Cin, Tin, M, q, Cout, Tout);
+    return (size_t)B * nb * p.Cv * p.Tv * sizeof(float);
+}
+
+extern "C" int ign_eeg_filterbank_nct_to_btc(const float* x_nct, const float* taps, const float* quad, float* out_btc, float* ws,
+                                             int B, int Cin, int Tin, int M, int nb, int q, int edge, int Cout, int Tout, float eps,
+                                             void* stream) {
+    static const char* who = "ign_eeg_filterbank_nct_to_btc";
+    if (!x_nct || !taps || !out_btc || !ws) {
+        ign_set_error("%s: null pointer", who);
+        return IGN_E_ARG;
+    }
+    if (!ep_bank_check(who, nb)) return IGN_E_ARG;
+    if (ep_check(who, B, Cin, Tin, M, q, edge, Cout, Tout, true)) return IGN_E_ARG;
+    if (quad && edge == IGN_EDGE_ZERO) {
+        ign_set_error("%s: quadrature taps (envelope) with IGN_EDGE_ZERO: without the reflect pivot the recording's offset enters "
+                      "the square root", who);
+        return IGN_E_ARG;
+    }
+    if (quad && M == 1) {
+        ign_set_error("%s: quadrature taps (envelope) with M=1: a single tap has no quadrature pair", who);
+        return IGN_E_ARG;
+    }
+    const EpPlan p = ep_plan(Cin, Tin, M, q, Cout, Tout);
+    if (p.Tv < 2) {
+        ign_set_error("%s: Tv = min(ceil(Tin/q), Tout) = %d; the unbiased std needs Tv >= 2 (Tin=%d q=%d Tout=%d)", who, p.Tv, Tin, q,
+                      Tout);
+        return IGN_E_ARG;
+    }
+    if (p.lds > EP_LDS_MAX) {
+        ign_set_error("%s: a row of Tin=%d with M=%d taps needs %zu bytes of LDS, more than %zu", who, Tin, M, p.lds, EP_LDS_MAX);
+        return IGN_E_TOOBIG;
+    }
+    if (B > 65535 || (long long)B * p.Cv > 0x7fffffffLL) {
+        ign_set_error("%s: B=%d exceeds the launch grid (65535 samples per call)", who, B);
+        return IGN_E_TOOBIG;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    IgnScopedTimer tm("eeg_filterbank", s);
+    const dim3 grid((unsigned)(B * p.Cv));
+    const int reflect = edge == IGN_EDGE_REFLECT ? 1 : 0;
+    if (quad)
+        hipLaunchKernelGGL(eeg_filterbank_kernel<true>, grid, dim3(EP_THREADS), p.lds, s, x_nct, taps, quad, ws, Cin, Tin, M, nb, q,
+                           reflect, p.Cv, p.Tv, p.Lp, eps);
+    else
+        hipLaunchKernelGGL(eeg_filterbank_kernel<false>, grid, dim3(EP_THREADS), p.lds, s, x_nct, taps, (const float*)nullptr, ws, Cin,
+                           Tin, M, nb, q, reflect, p.Cv, p.Tv, p.Lp, eps);
+    int rc;
+    if ((rc = ign_check_launch("eeg_filterbank_kernel"))) return rc;
+    hipLaunchKernelGGL(eeg_bank_transpose_kernel, dim3((Tout + 63) / 64, (nb * Cout + 31) / 32, B), dim3(256), 0, s, ws, out_btc, nb,
+                       p.Cv, p.Tv, Cout, Tout);
+    return ign_check_launch("eeg_bank_transpose_kernel");
 }

@@ -197,6 +197,39 @@ def eeg_preprocess(x_nct, taps, *, decimate=1, edge="reflect", channels=None, ti
     return out, mask
 
 
+def eeg_filterbank(x_nct, taps, quad=None, *, decimate=1, edge="reflect", channels=None, timepoints=None, eps=1e-8):
+    """Raw (B,Cin,Tin) recordings -> (out (B,Tout,nb*Cout), mask (B,Tout) bool) on the GPU (ign_eeg_filterbank_nct_to_btc; the rule
+    is restated in utils/eeg_filter.py:filterbank_numpy): eeg_preprocess for the nb bands `taps` (nb, M) at once -- the extended row
+    is staged once and every band runs over it.  The output is band-major: channel j * Cout + c is electrode c of band j, each
+    band block cropped / zero-padded to `channels` electrodes on its own, and without `quad` block j is eeg_preprocess(x, taps[j],
+    ...) bit for bit.  With `quad` (nb, M), the quadrature taps of utils.eeg_filter.design_quadrature, every band's output is its
+    envelope sqrt(a^2 + b^2) before the standardisation; that needs edge='reflect' and M > 1."""
+    name = "eeg_filterbank"
+    _need_gpu(name, x_nct, taps, quad)
+    if x_nct.dim() != 3 or taps.dim() != 2:
+        raise _lib.IgnError(f"{name}: expected x (B,Cin,Tin) and taps (nb,M), got {tuple(x_nct.shape)} and {tuple(taps.shape)}")
+    if quad is not None and tuple(quad.shape) != tuple(taps.shape):
+        raise _lib.IgnError(f"{name}: quad {tuple(quad.shape)} does not have the shape of taps {tuple(taps.shape)}")
+    if edge not in ("reflect", "zero"):
+        raise ValueError(f"{name}: edge={edge!r} is neither 'reflect' nor 'zero'")
+    x, h = x_nct.contiguous(), taps.contiguous()
+    g = None if quad is None else quad.contiguous()
+    B, Cin, Tin = x.shape
+    nb, M = h.shape
+    q = int(decimate)
+    Td = -(-Tin // q) if q >= 1 else 0
+    Cout = Cin if channels is None else int(channels)
+    Tout = Td if timepoints is None else int(timepoints)
+    L = _lib.lib()
+    out = torch.empty(B, max(Tout, 0), max(nb * Cout, 0), device=x.device, dtype=torch.float32)
+    ws = torch.empty(L.ign_eeg_filterbank_ws_bytes(B, Cin, Tin, M, nb, q, Cout, Tout) // 4 or 1, device=x.device, dtype=torch.float32)
+    _lib.check(L.ign_eeg_filterbank_nct_to_btc(_ptr(x), _ptr(h), None if g is None else _ptr(g), _ptr(out), _ptr(ws), B, Cin, Tin, M,
+                                               nb, q, EDGE_REFLECT if edge == "reflect" else EDGE_ZERO, Cout, Tout, eps, _stream()),
+               "ign_eeg_filterbank_nct_to_btc")
+    mask = (torch.arange(Tout, device=x.device) < min(Td, Tout)).unsqueeze(0).expand(B, Tout).contiguous()
+    return out, mask
+
+
 def augment(x, seed, *, lengths=None, shift=0.0, scale=0.0, noise=0.0, channel_drop=0.0, time_mask=0.0):
     """Training augmentation of a contiguous fp32 (B,T,C) batch on the GPU -> a new tensor (ign_augment_btc; the rule is
     csrc/ign_augment.h, restated in utils/augment.py): a circular shift by up to `shift` * length, a per-channel gain in

@@ -20,6 +20,9 @@ Differences, all repairs of fork defects listed in SURVEY section 0:
     edge=reflect|zero, fit) filters the raw CHISCO shards with a zero-phase FIR band-pass, decimates them and, with ``fit``, crops /
     zero-pads them to ``--target_channels`` x ``--target_timepoints`` in front of the standardisation -- on the device in the
     prefetcher (two HIP passes), in numpy on the CPU item path; the default ``none`` changes nothing and leaves ``--target_*`` inert;
+    ``bank=4:8+8:13+13:30+30:45`` (1 to 8 bands instead of ``band=``) makes a filter bank in the same two passes: every band of every
+    electrode is a channel of its own, band-major (``enc_in`` = bands x electrodes; ``fit`` counts ``--target_channels`` per band),
+    and ``envelope`` turns every band into its band-power envelope (needs ``edge=reflect`` and both edges of every band);
   * ``--task_name regression --data Monash`` is the reference's regression twin (exp/experiment_regression.py), with the
     repairs R1-R3 of DESIGN 2.3;
   * multi-GPU is one process per GPU: ``python -m torch.distributed.run --nproc-per-node N run.py ...``.
@@ -116,7 +119,11 @@ def build_parser():
                         "(odd, <= 1023; default 20Q+1 when only decimating, else 3.3*sfreq/lowest edge), edge=reflect|zero, and fit "
                         "(output shape --target_channels x --target_timepoints, cropped / zero-padded and masked; without it "
                         "channels x ceil(T/Q)).  A zero-phase Hamming windowed-sinc FIR filter; an upper edge above sfreq/(2Q) is "
-                        "refused")
+                        "refused.  bank=LO:HI+LO:HI+... (1 to 8 bands, instead of band=; one tap count for all) gives a filter bank: "
+                        "band-major channels, channel j*C + c is electrode c of band j, and fit then means --target_channels "
+                        "electrodes per band; envelope replaces every band by its amplitude envelope (Hilbert-pair FIR; needs "
+                        "edge=reflect and both edges of every band; band=LO:HI,envelope is a bank of one band).  --augment sees the "
+                        "bank's channels: its chan_drop drops single band channels, not whole electrodes")
     # experiment
     p.add_argument("--lr", type=float, default=5e-3)
     p.add_argument("--lr_decay", action="store_true")

@@ -1,0 +1,357 @@
+"""Host side of the EEG filter bank (--eeg_preprocess bank=... / envelope; no device): the grammar, the quadrature designer, the
+envelope of a sinusoid, the numpy rule against the one-band rule and its fp32 restatement against float64, resolve(), the data
+set's CPU item path, the ABI of the two entry points with the launcher's refusals on fake pointers, and run.py's texts.  The GPU
+side is tests/test_gpu_eeg_filterbank.py."""
+import ctypes
+import os
+import re
+from argparse import Namespace
+
+import numpy as np
+import pytest
+import torch
+
+from eeg_filterbank_cases import CASES, SFREQ, F as _F, case
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+E_ARG, E_TOOBIG = -1001, -1003
+SYMBOLS = ("ign_eeg_filterbank_ws_bytes", "ign_eeg_filterbank_nct_to_btc")
+BANK4 = ((4.0, 8.0), (8.0, 13.0), (13.0, 30.0), (30.0, 45.0))
+
+
+# ---------------------------------------------------------------- the spec
+def test_bank_grammar():
+    F = _F()
+    S = F.EEGPreprocessSpec
+    s = F.parse_eeg_preprocess("bank=4:8+8:13+13:30+30:45,decimate=2,fit")
+    assert s == S(decimate=2, fit=True, bank=BANK4) and s.active and not s.envelope
+    e = F.parse_eeg_preprocess("bank=4:8+8:13+13:30+30:45,decimate=2,fit,envelope")
+    assert e == S(decimate=2, fit=True, bank=BANK4, envelope=True) and e.active
+    assert F.parse_eeg_preprocess("envelope, bank=13:30+8:13+8:30").bank == ((13.0, 30.0), (8.0, 13.0), (8.0, 30.0))   # order kept, overlap
+    assert F.parse_eeg_preprocess("band=8:13,envelope") == S(bank=((8.0, 13.0),), envelope=True)       # a bank of one band
+    assert F.parse_eeg_preprocess("bank=8:13").bank == ((8.0, 13.0),) and F.parse_eeg_preprocess("bank=8:13").active
+    assert F.parse_eeg_preprocess("bank=:8+30:") == S(bank=((None, 8.0), (30.0, None)))                 # either side may be empty
+    assert F.parse_eeg_preprocess("bank=0:8+8:13").bank == ((None, 8.0), (8.0, 13.0))                    # a lower edge of 0 Hz is no edge
+    assert F.parse_eeg_preprocess("bank=8:13+13:125,decimate=2").bank[1] == (13.0, 125.0)                # exactly sfreq / (2 Q)
+    assert F.parse_eeg_preprocess("bank=8:13+13:30,taps=101,edge=zero") == S(taps=101, edge="zero", bank=((8.0, 13.0), (13.0, 30.0)))
+    assert F.parse_eeg_preprocess(e) is e
+    # neither bank= nor envelope: today's spec, field for field
+    for text in ("band=8:30,decimate=2,fit", "decimate=3", "sfreq=250,band=1:40,taps=101,edge=zero", "none", "fit"):
+        t = F.parse_eeg_preprocess(text)
+        assert t.bank is None and not t.envelope and t == S(*t[:7])
+    assert S() == S(sfreq=500.0, lo=None, hi=None, decimate=1, taps=None, edge="reflect", fit=False)
+    assert not S().active
+
+
+@pytest.mark.parametrize("text", [
+    "bank=8:13,band=8:13",                        # exclude each other
+    "bank=8:13+13:30,envelope,edge=zero",         # no pivot: the offset would enter the square root
+    "band=8:13,envelope,edge=zero",
+    "bank=8:13+13:,envelope",                     # an open-ended band has no envelope
+    "bank=:8+8:13,envelope", "band=:40,envelope", "envelope", "decimate=2,envelope",
+    "bank=" + "+".join(f"{4 * i}:{4 * i + 4}" for i in range(1, 10)),     # nine bands
+    "bank=8:13+13:130,decimate=2",                # aliases
+    "bank=8:13+30:13",                            # empty band
+    "bank=8:13+:",                                # nothing to filter
+    "bank=8:13+13", "bank=8:13+", "bank=", "bank=8:x", "bank", "envelope=1", "bank=8:13;13:30",   # malformed
+    "bank=8:13,bank=13:30",                       # repeated
+    "band=8:13,envelope,taps=1",
+])
+def test_bank_spec_errors(text):
+    with pytest.raises(ValueError, match="--eeg_preprocess"):
+        _F().parse_eeg_preprocess(text)
+
+
+def test_bank_tap_count_is_common_and_follows_the_lowest_edge(capsys):
+    F = _F()
+    n = lambda text: F.default_numtaps(F.parse_eeg_preprocess(text))       # noqa: E731
+    assert n("bank=4:8+8:13+13:30+30:45,decimate=2") == 413                 # 3.3 * 500 / 4 = 412.5, as band=4:40
+    assert n("bank=30:45+8:13") == 207                                      # the lowest edge over all bands, whatever the order
+    assert n("bank=8:13+13:30,taps=101") == 101
+    assert n("bank=:8+30:") == 207
+    assert capsys.readouterr().out == ""
+    assert n("bank=0.5:4+4:8") == 1023
+    assert "capped at 1023" in capsys.readouterr().out
+
+
+# ---------------------------------------------------------------- design
+@pytest.mark.parametrize("lo,hi,M", [(4.0, 8.0, 413), (8.0, 13.0, 207), (13.0, 30.0, 101), (30.0, 45.0, 41), (8.0, 30.0, 3)])
+def test_quadrature_design(lo, hi, M):
+    F = _F()
+    g = F.design_quadrature(SFREQ, lo, hi, M)
+    assert g.dtype == np.float64 and g.shape == (M,) and g[(M - 1) // 2] == 0.0
+    assert np.abs(g + g[::-1]).max() <= 1e-16                               # antisymmetric
+    assert abs(g.sum()) <= 1e-15                                            # a constant does not pass
+    # the formula, with the in-phase design's own scale factor (not a sum of its own)
+    m = np.arange(M) - (M - 1) // 2
+    left, right = 2 * lo / SFREQ, 2 * hi / SFREQ
+    win = 0.54 + 0.46 * np.cos(np.linspace(-np.pi, np.pi, M))
+    h_raw = (right * np.sinc(right * m) - left * np.sinc(left * m)) * win
+    scale = np.sum(h_raw * np.cos(np.pi * m * 0.5 * (left + right)))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        want = np.where(m == 0, 0.0, (np.cos(np.pi * left * m) - np.cos(np.pi * right * m)) / (np.pi * m)) * win / scale
+    assert np.abs(g - want).max() <= 1e-15
+    assert np.abs(F.design_fir(SFREQ, lo, hi, M) - h_raw / scale).max() <= 1e-15
+    with pytest.raises(ValueError):
+        F.design_quadrature(SFREQ, lo, hi, M + 1)
+
+
+@pytest.mark.parametrize("q", [1, 2])
+def test_envelope_of_a_sinusoid_is_its_amplitude(q):
+    """Amplitude 3 at the band centre, M = 413, reflect edge: at every output more than R input samples from either end the
+    envelope is within 2e-3 relative of 3 (the Hamming design's pass-band ripple at the centre; worst at 4:8, 1.0e-3)."""
+    F = _F()
+    M, T = 413, 2000
+    R = (M - 1) // 2
+    t = np.arange(T) / SFREQ
+    worst = {}
+    for lo, hi in BANK4:
+        x = 3.0 * np.sin(2 * np.pi * 0.5 * (lo + hi) * t + 0.3)[None, None, :]
+        H, G = F.design_fir(SFREQ, lo, hi, M)[None], F.design_quadrature(SFREQ, lo, hi, M)[None]
+        e = F.filterbank_numpy(x, H, G, q, "reflect", standardise=False)[0, :, 0]
+        n = np.arange(len(e)) * q
+        inner = (n > R) & (n < T - 1 - R)
+        assert inner.sum() > 500 // q
+        worst[(lo, hi)] = float(np.abs(e[inner] / 3.0 - 1).max())
+    print(f"envelope of a sinusoid, q={q}: worst relative error per band {worst}")
+    assert max(worst.values()) <= 2e-3, worst
+
+
+# ---------------------------------------------------------------- the rule in numpy
+def test_block_j_of_the_bank_is_the_one_band_rule_exactly():
+    F = _F()
+    for label in ("B_crop_pad", "D_channel_crop"):
+        k = case(label, False)
+        x, H, q, Cout, Tout = k["x"], k["H"], k["q"], k["Cout"], k["Tout"]
+        got = F.filterbank_numpy(x, H, None, q, "reflect", Cout, Tout)
+        assert got.dtype == np.float64 and got.shape == (x.shape[0], k["Tv"], k["nb"] * Cout)
+        for j in range(k["nb"]):
+            assert np.array_equal(got[..., j * Cout:(j + 1) * Cout], F.preprocess_numpy(x, H[j], q, "reflect", Cout, Tout)), (label, j)
+            assert np.array_equal(k["ref64"][:, :k["Tv"], j * Cout:(j + 1) * Cout], got[..., j * Cout:(j + 1) * Cout])
+        zero = F.filterbank_numpy(x, H, None, q, "zero", Cout, Tout)
+        assert np.array_equal(zero[..., :Cout], F.preprocess_numpy(x, H[0], q, "zero", Cout, Tout))
+        raw = F.filterbank_numpy(x, H, None, q, "reflect", Cout, Tout, standardise=False)
+        assert np.array_equal(raw[..., Cout:2 * Cout], F.preprocess_numpy(x, H[1], q, "reflect", Cout, Tout, standardise=False))
+    x, H, G = k["x"], k["H"], case("D_channel_crop", True)["G"]
+    for bad in (dict(edge="zero"), dict(taps=H[:, :1], quad=G[:, :1]), dict(quad=G[:2]), dict(taps=np.zeros((9, 5)), quad=None),
+                dict(taps=H[0], quad=None)):
+        kw = dict(taps=H, quad=G, edge="reflect")
+        kw.update(bad)
+        with pytest.raises(ValueError):
+            F.filterbank_numpy(x, kw["taps"], kw["quad"], 1, kw["edge"])
+
+
+def test_envelope_blocks_are_standardised_envelopes():
+    F = _F()
+    k = case("B_crop_pad", True)
+    x, H, G, q, Cout, Tv, Cv = k["x"], k["H"], k["G"], k["q"], k["Cout"], k["Tv"], k["Cv"]
+    for j in range(k["nb"]):
+        a = F.filter_decimate(x, H[j], q, "reflect")[..., :Cv, :Tv]
+        b = F.filter_decimate(x, G[j], q, "reflect")[..., :Cv, :Tv]
+        e = np.sqrt(a * a + b * b)
+        z = (e - e.mean(-1, keepdims=True)) / (e.std(-1, ddof=1, keepdims=True) + 1e-8)
+        blk = k["ref64"][:, :, j * Cout:(j + 1) * Cout]
+        assert np.abs(blk[:, :Tv, :Cv] - z.transpose(0, 2, 1)).max() < 1e-12
+        assert (blk[:, Tv:] == 0).all() and (blk[:, :, Cv:] == 0).all()
+    # the fp32 form is sqrtf(fmaf(a, a, b * b)): b * b rounded, a * a exact, one rounding of the sum
+    a, b = np.float32(3.0000002), np.float32(4.0000005)
+    want = np.sqrt(np.float32(float(a) * float(a) + float(np.float32(b * b))))
+    assert F.envelope_of(a, b, np.float32) == want and F.envelope_of(a, b, np.float32).dtype == np.float32
+    assert F.envelope_of(3.0, 4.0) == 5.0
+
+
+@pytest.mark.parametrize("label", list(CASES))
+@pytest.mark.parametrize("envelope", [False, True], ids=["plain", "envelope"])
+def test_fp32_restatement_stays_near_float64(label, envelope):
+    """conftest's 'elem' criterion at 1e-4, on the case table of the GPU tests (worst measured 7.1e-6, envelope of case C)."""
+    k = case(label, envelope)
+    r32, r64 = k["ref32"].astype(np.float64), k["ref64"]
+    assert k["ref32"].dtype == np.float32 and r32.shape == r64.shape == (k["x"].shape[0], k["Tout"], k["nb"] * k["Cout"])
+    err = float((np.abs(r32 - r64) / (1.0 + np.abs(r64))).max())
+    print(f"{label} {'envelope' if envelope else 'plain'}: fp32 restatement against float64 {err:.3e}")
+    assert err <= 1e-4
+
+
+# ---------------------------------------------------------------- resolve
+def test_resolve_bank():
+    F = _F()
+    r = F.resolve("bank=4:8+8:13+13:30+30:45,decimate=2,fit", 122, 1651, 64, 500)
+    assert isinstance(r, F.ResolvedBank) and not isinstance(r, F.Resolved)
+    assert r.taps.shape == (4, 413) and r.taps.dtype == np.float64 and r.quad is None
+    assert r[2:] == (2, "reflect", 64, 500, 500, BANK4) and r.channels == 256        # fit: 64 electrodes PER BAND
+    for j, (lo, hi) in enumerate(BANK4):
+        assert np.array_equal(r.taps[j], F.design_fir(500.0, lo, hi, 413))
+    e = F.resolve("bank=4:8+8:13+13:30+30:45,decimate=2,envelope", 12, 900)
+    assert e.quad.shape == e.taps.shape == (4, 413) and e[2:7] == (2, "reflect", 12, 450, 450) and e.channels == 48
+    assert np.array_equal(e.quad[2], F.design_quadrature(500.0, 13.0, 30.0, 413))
+    assert F.bank_channel(e, 0) == (0, (4.0, 8.0), 0) and F.bank_channel(e, 11) == (0, (4.0, 8.0), 11)
+    assert F.bank_channel(e, 12) == (1, (8.0, 13.0), 0) and F.bank_channel(e, 47) == (3, (30.0, 45.0), 11)
+    for bad in (-1, 48):
+        with pytest.raises(IndexError):
+            F.bank_channel(e, bad)
+    o = F.resolve("bank=:8+30:,decimate=2,taps=41", 6, 100)                  # an open upper edge is sfreq / (2 Q) when decimating
+    assert o.bands == ((None, 8.0), (30.0, 125.0)) and np.array_equal(o.taps[1], F.design_fir(500.0, 30.0, 125.0, 41))
+    one = F.resolve("band=8:13,envelope,taps=41", 6, 100)
+    assert isinstance(one, F.ResolvedBank) and one.taps.shape == one.quad.shape == (1, 41) and one.channels == 6
+    # a spec without bank= / envelope resolves as it always did
+    r1 = F.resolve("band=8:30,decimate=2,fit", 122, 1651, 64, 500)
+    assert isinstance(r1, F.Resolved) and len(r1) == 6 and r1[1:] == (2, "reflect", 64, 500, 500)
+    with pytest.raises(ValueError, match="reflect"):
+        F.resolve("bank=8:13+13:30", 12, 100)                               # 207 taps reflect 103 samples of 100
+    assert F.resolve("bank=8:13+13:30,edge=zero", 12, 100).taps.shape == (2, 207)
+    with pytest.raises(ValueError, match="valid time step"):
+        F.resolve("bank=8:13+13:30,taps=21,decimate=2,fit", 12, 200, 8, 1)
+    with pytest.raises(ValueError, match="target"):
+        F.resolve("bank=8:13+13:30,taps=21,fit", 12, 100)
+
+
+# ---------------------------------------------------------------- the loader
+def _shards(tmp_path, n=50, C=12, T=200):
+    rng = np.random.RandomState(1)
+    X = (rng.randn(n, C, T) * 30 + 500).astype(np.float32)
+    np.save(tmp_path / "X.npy", X)
+    np.save(tmp_path / "y.npy", rng.randint(0, 39, size=n))
+    return X
+
+
+def _ns(tmp_path, **kw):
+    base = dict(task_name="classification", data="EEG3", root_path=str(tmp_path), batch_size=16, num_workers=0, seed=0,
+                target_channels=8, target_timepoints=120)
+    base.update(kw)
+    return Namespace(**base)
+
+
+@pytest.mark.parametrize("envelope", [False, True], ids=["plain", "envelope"])
+def test_dataset_reports_the_bank_shape_and_its_cpu_items_follow_the_rule(tmp_path, envelope):
+    import speech_imagery_eeg_amd  # noqa: F401
+    from data_provider.data_factory import data_provider
+    F = _F()
+    X = _shards(tmp_path)
+    spec = "bank=8:13+13:30+30:45,decimate=2,taps=41,fit" + (",envelope" if envelope else "")
+    ds, loader = data_provider(_ns(tmp_path, device_standardise=False, eeg_preprocess=spec), "test")
+    assert isinstance(ds.pre, F.ResolvedBank) and (ds.pre.quad is not None) == envelope
+    assert (ds.enc_in, ds.seq_len, ds.pre.Tv, ds.pre.Cout) == (3 * 8, 120, 100, 8) and loader.device_transform is None
+    x0, y0 = ds[0]
+    assert x0.shape == (100, 24) and x0.dtype == torch.float32 and y0.shape == (1,)
+    p = ds.pre
+    want = F.filterbank_numpy(X[ds.idx[0]], p.taps.astype(np.float32), None if p.quad is None else p.quad.astype(np.float32), 2,
+                              "reflect", 8, 120)
+    assert np.abs(x0.numpy() - want).max() < 1e-6
+    xb, yb, mask = next(iter(loader))
+    assert xb.shape == (10, 120, 24) and mask.shape == (10, 120) and bool(mask[:, :100].all()) and not bool(mask[:, 100:].any())
+    assert bool((xb[:, 100:] == 0).all())
+    v = xb[:, :100].double()
+    assert float(v.mean(dim=1).abs().max()) < 1e-6 and float((v.std(dim=1, unbiased=True) - 1).abs().max()) < 1e-6
+    # a raw data set ships raw items and hands the resolved bank to the loader
+    ds, loader = data_provider(_ns(tmp_path, device_standardise=True, eeg_preprocess=spec), "train")
+    assert ds[0][0].shape == (12, 200) and (ds.seq_len, ds.enc_in) == (120, 24)
+    assert loader.device_transform == "eeg_preprocess" and loader.eeg_preprocess is ds.pre
+    # without fit: every electrode of every band, Td time steps
+    ds, _ = data_provider(_ns(tmp_path, device_standardise=False, eeg_preprocess="bank=8:13+13:30,taps=41,decimate=2"), "val")
+    assert (ds.enc_in, ds.seq_len) == (24, 100) and ds[0][0].shape == (100, 24)
+
+
+# ---------------------------------------------------------------- ABI
+def _lib_or_skip():
+    import speech_imagery_eeg_amd  # noqa: F401
+    from ign_hip import _lib
+    if not os.path.exists(_lib.lib_path()):
+        pytest.skip("libign_hip.so not built")
+    return _lib.lib()
+
+
+def test_filterbank_symbols_are_declared_bound_and_exported():
+    import speech_imagery_eeg_amd  # noqa: F401
+    from ign_hip import _lib
+    F = _F()
+    text = open(os.path.join(ROOT, "include", "ign_abi.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    for name in SYMBOLS:
+        m = re.search(rf"\b{name}\s*\(([^;]*)\)\s*;", hdr)
+        assert m, name
+        assert name in _lib.SIGNATURES, name
+        assert len(_lib.SIGNATURES[name][1]) == m.group(1).count(",") + 1, name        # one ctypes entry per C parameter
+    assert _lib.SIGNATURES[SYMBOLS[0]][0] is ctypes.c_size_t
+    assert re.search(rf"#define IGN_EEG_MAX_BANDS\s+{F.MAX_BANDS}\b", hdr) and F.MAX_BANDS == 8
+    if not os.path.exists(_lib.lib_path()):
+        pytest.skip("libign_hip.so not built")
+    h = ctypes.CDLL(_lib.lib_path())
+    for name in SYMBOLS:
+        assert hasattr(h, name), name
+
+
+def _p(v):
+    return ctypes.c_void_p(v)
+
+
+def _args(**kw):
+    a = dict(x=_p(16), taps=_p(32), quad=None, out=_p(48), ws=_p(64), B=2, Cin=4, Tin=60, M=21, nb=3, q=2, edge=0, Cout=4, Tout=30,
+             eps=1e-8, stream=None)
+    a.update(kw)
+    return list(a.values())
+
+
+@pytest.mark.parametrize("kw,rc,msg", [
+    (dict(nb=0), E_ARG, b"bands outside 1..8"),
+    (dict(nb=9), E_ARG, b"bands outside 1..8"),
+    (dict(quad=_p(80), edge=1), E_ARG, b"IGN_EDGE_ZERO"),
+    (dict(quad=_p(80), M=1), E_ARG, b"M=1"),
+    (dict(x=None), E_ARG, b"null pointer"),
+    (dict(taps=None), E_ARG, b"null pointer"),
+    (dict(out=None), E_ARG, b"null pointer"),
+    (dict(ws=None), E_ARG, b"null pointer"),
+    (dict(B=0), E_ARG, b"non-positive dimension"),
+    (dict(Cout=0), E_ARG, b"non-positive dimension"),
+    (dict(M=20), E_ARG, b"odd count in 1..1023"),
+    (dict(M=1025, edge=1), E_ARG, b"odd count in 1..1023"),
+    (dict(q=17), E_ARG, b"decimation factor q=17 outside 1..16"),
+    (dict(edge=2), E_ARG, b"neither IGN_EDGE_REFLECT nor IGN_EDGE_ZERO"),
+    (dict(M=121), E_ARG, b"reflect extension by R=60"),
+    (dict(Tout=1), E_ARG, b"needs Tv >= 2"),
+    (dict(Tin=20000, M=1023), E_TOOBIG, b"bytes of LDS"),
+    (dict(B=65536), E_TOOBIG, b"launch grid"),
+])
+def test_filterbank_launcher_refusals_need_no_device(kw, rc, msg):
+    h = _lib_or_skip()
+    assert h.ign_eeg_filterbank_nct_to_btc(*_args(**kw)) == rc
+    assert msg in h.ign_last_error(), h.ign_last_error()
+
+
+def test_filterbank_workspace_bytes():
+    h = _lib_or_skip()
+    # B * nb * min(Cin, Cout) * Tv floats
+    assert h.ign_eeg_filterbank_ws_bytes(2, 4, 60, 21, 3, 2, 4, 30) == 2 * 3 * 4 * 30 * 4
+    assert h.ign_eeg_filterbank_ws_bytes(3, 70, 131, 61, 8, 3, 64, 100) == 3 * 8 * 64 * 44 * 4
+    assert h.ign_eeg_filterbank_ws_bytes(256, 122, 2000, 413, 4, 2, 122, 1000) == 256 * 4 * 122 * 1000 * 4
+    assert h.ign_eeg_filterbank_ws_bytes(2, 4, 60, 21, 1, 2, 4, 30) == h.ign_eeg_preprocess_ws_bytes(2, 4, 60, 21, 2, 4, 30)
+    for bad in ((2, 4, 60, 21, 0, 2, 4, 30), (2, 4, 60, 21, 9, 2, 4, 30), (2, 4, 60, 20, 3, 2, 4, 30), (0, 4, 60, 21, 3, 2, 4, 30)):
+        assert h.ign_eeg_filterbank_ws_bytes(*bad) == 0
+
+
+def test_ops_filterbank_refuses_host_tensors():
+    import speech_imagery_eeg_amd  # noqa: F401
+    from ign_hip import ops
+    from ign_hip._lib import IgnError
+    with pytest.raises(IgnError, match="no CPU fallback"):
+        ops.eeg_filterbank(torch.zeros(1, 2, 8), torch.ones(2, 1))
+    with pytest.raises(IgnError, match="no CPU fallback"):
+        ops.eeg_filterbank(torch.zeros(1, 2, 8), torch.ones(2, 3), torch.ones(2, 3))
+
+
+# ---------------------------------------------------------------- run.py
+def test_flag_texts_name_the_bank_and_the_envelope():
+    import speech_imagery_eeg_amd  # noqa: F401
+    import run
+    F = _F()
+    p = run.build_parser()
+    act = {a.option_strings[0]: a for a in p._actions if a.option_strings}["--eeg_preprocess"]
+    assert act.default == "none"
+    for word in ("bank=", "envelope"):
+        assert word in act.help and word in run.__doc__, word
+    assert "chan_drop" in act.help                                           # --augment sees nb * Cout channels
+    a = run.get_args(["--data", "EEG3", "--eeg_preprocess", "bank=4:8+8:13+13:30+30:45,decimate=2,fit,envelope"])
+    assert F.parse_eeg_preprocess(a.eeg_preprocess).envelope
+    with pytest.raises(ValueError, match="EEG3"):
+        run.get_args(["--data", "UEA", "--eeg_preprocess", "bank=8:13+13:30"])
+    with pytest.raises(ValueError, match="--eeg_preprocess"):
+        run.get_args(["--data", "EEG", "--eeg_preprocess", "bank=8:13,band=8:13"])
