@@ -68,46 +68,44 @@ int ign_transpose_btc_to_bct(const float* x_btc, float* out_bct, int B, int T, i
 int ign_standardise_nct_to_btc(const float* x_nct, float* out_btc, float* stats_ws, int B, int C, int T, float eps,
                                void* stream);
 
-/* EEG preprocessing in front of the standardisation (csrc/ign_eeg_preprocess.hip; run.py --eeg_preprocess): raw (B,Cin,Tin)
- * recordings -> centred FIR filter, decimate by q, crop / zero-pad to (Tout,Cout), standardise, transpose -> out (B,Tout,Cout).
- * What the reference's loader does on the CPU with scipy.signal.decimate(ftype='fir', zero_phase=True) and its channel / time
- * fitting (IGN/data_factory/eeg_processor.py:258-381), here for a whole batch in front of the per-sample statistics.
- *   taps (M) fp32 on the DEVICE, M odd, R = (M-1)/2;  x~ = the row extended by R samples: zeros (IGN_EDGE_ZERO) or mirrored
- *   about the end samples, x~[-i] = x[i], x~[Tin-1+i] = x[Tin-1-i] (IGN_EDGE_REFLECT, numpy pad 'reflect'; needs R <= Tin-1);
- *   f[n] = sum_k taps[k] * x~[n*q + R - k],  n < Td = ceil(Tin/q)     (a convolution, centred: zero-phase for symmetric taps)
- *   Tv = min(Td, Tout); per (b, c < min(Cin,Cout)): mean and unbiased std of f[0..Tv-1] in two sweeps;
- *   out[b,t,c] = (f[t] - mean) / (std + eps) for t < Tv; exactly 0 for Tv <= t < Tout and for Cin <= c < Cout.
+/* EEG preprocessing in front of the standardisation (csrc/ign_eeg_preprocess.hip; run.py --eeg_preprocess; numpy restatement
+ * utils/eeg_filter.py:filterbank_numpy): raw (B,Cin,Tin) recordings -> nb centred FIR filters of one common length, decimate by q,
+ * crop / zero-pad every band to (Tout,Cout), standardise, transpose -> out (B,Tout,nb*Cout).  What the reference's loader does on the
+ * CPU with scipy.signal.decimate(ftype='fir', zero_phase=True) and its channel / time fitting (IGN/data_factory/eeg_processor.py:
+ * 258-381), here for a whole batch and several bands in front of the per-sample statistics.  One rule, one launcher; the four entry
+ * points below differ only in what they fix.
+ *   taps (nb,M) and optional quadrature taps quad (nb,M), fp32 on the DEVICE, M odd, R = (M-1)/2;  x~ = the row extended by R
+ *   samples: zeros (IGN_EDGE_ZERO) or mirrored about the end samples, x~[-i] = x[i], x~[Tin-1+i] = x[Tin-1-i] (IGN_EDGE_REFLECT,
+ *   numpy pad 'reflect'; needs R <= Tin-1).  Per band j and row (b, c < min(Cin,Cout)):
+ *   a_j[n] = sum_k taps[j,k] * x~[n*q + R - k],  n < Td = ceil(Tin/q)   (a convolution, centred: zero-phase for symmetric taps)
+ *   quad == NULL:  f_j = a_j;   else  b_j[n] = the same sum with quad[j,k],  f_j[n] = sqrtf(fmaf(a_j[n], a_j[n], b_j[n] * b_j[n]))
+ *   Tv = min(Td, Tout); mean and unbiased std of f_j[0..Tv-1] in two sweeps;
+ *   out[b,t,j*Cout+c] = (f_j[t] - mean) / (std + eps) for t < Tv; exactly 0 for Tv <= t < Tout and for Cin <= c < Cout.
+ * out is BAND-MAJOR: channel j*Cout + c is electrode c of band j; every band block is cropped / zero-padded to Cout electrodes on its
+ * own.  The extended row is staged once per (b,c) and every band runs over it with the same tap walk, so block j does not depend on
+ * the other bands: without quad it is the bank of one for taps[j], bit for bit.
  * In reflect mode with M > 1 the kernel filters x - x[b,c,0] (a constant passes reflect-extended filtering up to the factor
- * sum(taps) and the standardisation removes it): the same value, without the recording's offset in the fp32 products.  M = 1 extends
- * nothing and takes no pivot; the statistics run in ign_standardise_nct_to_btc's order, so taps {1} with Cout = Cin, Tout = Tin give
- * that entry point's output bit for bit.  Fixed summation order, no
- * atomics: two calls give the same bits.  Nothing outside [0,Tin) of a row is read; taps longer than the row are legal in zero mode.
- * ws: ign_eeg_preprocess_ws_bytes() bytes (B * min(Cin,Cout) * Tv floats; 0 for arguments the launcher refuses).
- * IGN_E_ARG: null pointer, non-positive dimension, M even or > IGN_EEG_MAX_TAPS, q outside 1..IGN_EEG_MAX_DECIMATE, unknown edge,
- * reflect with R >= Tin, Tv < 2.  IGN_E_TOOBIG: a row whose phase-split image and filtered copy exceed 64 KB of LDS
- * ((Tin + M - 1 + q*4 + Tv) floats), or B > 65535.  Nothing is launched on an error.                                          */
+ * sum(taps[j]) and the standardisation removes it): the same value, without the recording's offset in the fp32 products.  M = 1
+ * extends nothing and takes no pivot; the statistics run in ign_standardise_nct_to_btc's order, so nb = 1, taps {1} with Cout = Cin,
+ * Tout = Tin give that entry point's output bit for bit.  Fixed summation order, no atomics: two calls give the same bits.  Nothing
+ * outside [0,Tin) of a row is read; taps longer than the row are legal in zero mode.
+ * ws: ign_eeg_filterbank_ws_bytes() bytes (B * nb * min(Cin,Cout) * Tv floats; 0 for arguments the launcher refuses).
+ * IGN_E_ARG: null pointer, nb outside 1..IGN_EEG_MAX_BANDS, non-positive dimension, M even or > IGN_EEG_MAX_TAPS, q outside
+ * 1..IGN_EEG_MAX_DECIMATE, unknown edge, reflect with R >= Tin, quad with IGN_EDGE_ZERO (without the pivot the recording's offset
+ * times sum(taps[j]) enters the square root and the standardisation cannot remove it), quad with M == 1, Tv < 2.  IGN_E_TOOBIG: a row
+ * whose phase-split image and filtered copy exceed 64 KB of LDS ((Tin + M - 1 + q*4 + Tv) floats, whatever nb), or B > 65535.
+ * Nothing is launched on an error; the error text names the entry point that was called.                                      */
 #define IGN_EDGE_REFLECT     0
 #define IGN_EDGE_ZERO        1
 #define IGN_EEG_MAX_TAPS     1023
 #define IGN_EEG_MAX_DECIMATE 16
+/* One band: the bank of one.  taps (M); the same as the entry points below with nb = 1 and quad = NULL, out (B,Tout,Cout),
+ * ws B * min(Cin,Cout) * Tv floats.                                                                                            */
 size_t ign_eeg_preprocess_ws_bytes(int B, int Cin, int Tin, int M, int q, int Cout, int Tout);
 int ign_eeg_preprocess_nct_to_btc(const float* x_nct, const float* taps, float* out_btc, float* ws, int B, int Cin, int Tin, int M,
                                   int q, int edge, int Cout, int Tout, float eps, void* stream);
 
-/* The same pass for a filter bank (run.py --eeg_preprocess bank=... / envelope; ops.eeg_filterbank; numpy restatement
- * utils/eeg_filter.py:filterbank_numpy): nb bands with one common odd M, taps (nb,M) and optional quadrature taps quad (nb,M), both
- * fp32 on the DEVICE.  Per band j and row (b,c), with x~, the reflect pivot, R, q, Td, Tv as above:
- *   a_j[n] = sum_k taps[j,k] * x~[n*q + R - k]          (the arithmetic of ign_eeg_preprocess_nct_to_btc, in its order)
- *   quad == NULL:  f_j = a_j;   else  b_j[n] = the same sum with quad[j,k],  f_j[n] = sqrtf(fmaf(a_j[n], a_j[n], b_j[n] * b_j[n]))
- *   f_j[0..Tv-1] standardised, cropped and zero-padded as above.
- * out (B,Tout,nb*Cout) is BAND-MAJOR: channel j*Cout + c is electrode c of band j; every band block is cropped / zero-padded to Cout
- * electrodes on its own (exact zeros for c >= min(Cin,Cout) and for t >= Tv).  Without quad, block j is what
- * ign_eeg_preprocess_nct_to_btc returns for taps[j], bit for bit.  The extended row is staged once per (b,c) and every band runs
- * over it; fixed summation order, no atomics: two calls give the same bits.
- * ws: ign_eeg_filterbank_ws_bytes() bytes (B * nb * min(Cin,Cout) * Tv floats; 0 for arguments the launcher refuses).
- * IGN_E_ARG: nb outside 1..IGN_EEG_MAX_BANDS, quad with IGN_EDGE_ZERO (without the pivot the recording's offset times sum(taps[j])
- * enters the square root and the standardisation cannot remove it), quad with M == 1, and everything the one-band launcher refuses.
- * IGN_E_TOOBIG as above (the LDS need does not depend on nb).  Nothing is launched on an error.                                */
+/* The rule above in full (run.py --eeg_preprocess bank=... / envelope; ops.eeg_filterbank).                                    */
 #define IGN_EEG_MAX_BANDS 8
 size_t ign_eeg_filterbank_ws_bytes(int B, int Cin, int Tin, int M, int nb, int q, int Cout, int Tout);
 int ign_eeg_filterbank_nct_to_btc(const float* x_nct, const float* taps, const float* quad, float* out_btc, float* ws, int B, int Cin,

@@ -6,7 +6,7 @@ over PCIe Gen5, and ~0.5 ms of CPU z-scoring per sample).  ``DevicePrefetcher`` 
 ``(X, y, mask)``: batch i+1 is pinned and copied on a side HIP stream while batch i trains; an optional ``transform`` runs
 on that stream too -- for the CHISCO shards the loader ships RAW (B,C,T) microvolt tensors and the per-sample
 standardisation + transpose happen on the GPU (``ops.standardise_nct_to_btc``; with ``--eeg_preprocess`` the filter, decimation
-and fitting in front of it too: ``ops.eeg_preprocess``, or ``ops.eeg_filterbank`` for a ``bank=`` / ``envelope`` spec).  On a CPU device it is a pass-through.
+and fitting in front of it too: ``ops.eeg_filterbank``, a one-band spec as the bank of one).  On a CPU device it is a pass-through.
 """
 import torch
 
@@ -21,25 +21,17 @@ def standardise_raw_batch(batch):
 
 def preprocess_raw_batch(pre, device):
     """transform for raw loaders under --eeg_preprocess, built once per loader: `pre` is the data set's resolved spec
-    (utils.eeg_filter.Resolved); its taps go to the device here, once.  (X[B,Cin,Tin], y, None) ->
-    (X[B,Tout,Cout] filtered, decimated, fitted and standardised, y, mask[B,Tout] = t < Tv).  A ResolvedBank (bank= / envelope)
-    sends both tap tensors and runs ops.eeg_filterbank: X[B,Tout,nb*Cout], band-major."""
+    (utils.eeg_filter.Resolved or ResolvedBank; one band is the bank of one); its taps go to the device here, once.
+    (X[B,Cin,Tin], y, None) -> (X[B,Tout,nb*Cout] filtered, decimated, fitted and standardised, band-major, y,
+    mask[B,Tout] = t < Tv)."""
     from ign_hip import ops
-    from utils.eeg_filter import ResolvedBank
-    taps = torch.as_tensor(pre.taps, dtype=torch.float32).to(device)
+    taps = torch.as_tensor(pre.taps2d, dtype=torch.float32).to(device)
+    quad = None if pre.quad is None else torch.as_tensor(pre.quad, dtype=torch.float32).to(device)
     kw = dict(decimate=pre.q, edge=pre.edge, channels=pre.Cout, timepoints=pre.Tout)
-    if isinstance(pre, ResolvedBank):
-        quad = None if pre.quad is None else torch.as_tensor(pre.quad, dtype=torch.float32).to(device)
-
-        def bank_transform(batch):
-            x, y, _ = batch
-            xs, mask = ops.eeg_filterbank(x.float(), taps, quad, **kw)
-            return xs, y, mask
-        return bank_transform
 
     def transform(batch):
         x, y, _ = batch
-        xs, mask = ops.eeg_preprocess(x.float(), taps, **kw)
+        xs, mask = ops.eeg_filterbank(x.float(), taps, quad, **kw)
         return xs, y, mask
     return transform
 

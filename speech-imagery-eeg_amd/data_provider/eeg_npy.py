@@ -95,8 +95,8 @@ class EEGNpyDataset(Dataset):
                 # the models are built for what the items become: Tout time steps of Cout channels
                 self.pre = resolve(spec, self.enc_in, self.seq_len, target_channels, target_timepoints,
                                    notice=print if flag == 'train' else None)
-                # a bank (ResolvedBank) has nb * Cout channels, band-major
-                self.enc_in, self.seq_len = getattr(self.pre, 'channels', self.pre.Cout), self.pre.Tout
+                # a bank has nb * Cout channels, band-major; one band is the bank of one
+                self.enc_in, self.seq_len = self.pre.channels, self.pre.Tout
 
     def __len__(self):
         return len(self.idx)
@@ -108,13 +108,10 @@ class EEGNpyDataset(Dataset):
         if self.raw:              # device pipeline: data_provider.device_prefetch does the rest on the batch
             return torch.from_numpy(np.ascontiguousarray(x)), y
         if self.pre is not None:  # (Tv, Cout): collate_fn(max_len=seq_len) pads the time axis and builds the mask
-            from utils.eeg_filter import ResolvedBank, filterbank_numpy, preprocess_numpy
+            from utils.eeg_filter import filterbank_numpy
             p = self.pre
-            if isinstance(p, ResolvedBank):
-                quad = None if p.quad is None else p.quad.astype(np.float32)
-                return torch.from_numpy(filterbank_numpy(x, p.taps.astype(np.float32), quad, p.q, p.edge, p.Cout, p.Tout)
-                                        .astype(np.float32)), y
-            return torch.from_numpy(preprocess_numpy(x, p.taps.astype(np.float32), p.q, p.edge, p.Cout, p.Tout)
+            quad = None if p.quad is None else p.quad.astype(np.float32)
+            return torch.from_numpy(filterbank_numpy(x, p.taps2d.astype(np.float32), quad, p.q, p.edge, p.Cout, p.Tout)
                                     .astype(np.float32)), y
         return torch.from_numpy(per_sample_standardise(x).T.copy()), y
 

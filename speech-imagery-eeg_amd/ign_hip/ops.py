@@ -168,48 +168,8 @@ def standardise_nct_to_btc(x_nct, eps=1e-8):
 EDGE_REFLECT, EDGE_ZERO = 0, 1       # IGN_EDGE_*
 
 
-def eeg_preprocess(x_nct, taps, *, decimate=1, edge="reflect", channels=None, timepoints=None, eps=1e-8):
-    """Raw (B,Cin,Tin) recordings -> (out (B,Tout,Cout), mask (B,Tout) bool) on the GPU (ign_eeg_preprocess_nct_to_btc; the rule
-    is restated in utils/eeg_filter.py): the centred FIR filter `taps` (float32, on the GPU, odd length), every `decimate`-th
-    output, channels cropped / zero-padded to `channels` (None: Cin), time to `timepoints` (None: Td = ceil(Tin / decimate)),
-    then the per-sample, per-channel standardisation of standardise_nct_to_btc over the Tv = min(Td, Tout) valid steps.
-    mask[b, t] = t < Tv; the output is exactly zero where the mask is false and in padded channels.  `edge`: how the row is
-    extended by (len(taps) - 1) / 2 samples, 'reflect' (numpy pad 'reflect') or 'zero'."""
-    name = "eeg_preprocess"
-    _need_gpu(name, x_nct, taps)
-    if x_nct.dim() != 3 or taps.dim() != 1:
-        raise _lib.IgnError(f"{name}: expected x (B,Cin,Tin) and taps (M,), got {tuple(x_nct.shape)} and {tuple(taps.shape)}")
-    if edge not in ("reflect", "zero"):
-        raise ValueError(f"{name}: edge={edge!r} is neither 'reflect' nor 'zero'")
-    x, h = x_nct.contiguous(), taps.contiguous()
-    B, Cin, Tin = x.shape
-    M, q = h.numel(), int(decimate)
-    Td = -(-Tin // q) if q >= 1 else 0
-    Cout = Cin if channels is None else int(channels)
-    Tout = Td if timepoints is None else int(timepoints)
-    L = _lib.lib()
-    out = torch.empty(B, max(Tout, 0), max(Cout, 0), device=x.device, dtype=torch.float32)
-    ws = torch.empty(L.ign_eeg_preprocess_ws_bytes(B, Cin, Tin, M, q, Cout, Tout) // 4 or 1, device=x.device, dtype=torch.float32)
-    _lib.check(L.ign_eeg_preprocess_nct_to_btc(_ptr(x), _ptr(h), _ptr(out), _ptr(ws), B, Cin, Tin, M, q,
-                                               EDGE_REFLECT if edge == "reflect" else EDGE_ZERO, Cout, Tout, eps, _stream()),
-               "ign_eeg_preprocess_nct_to_btc")
-    mask = (torch.arange(Tout, device=x.device) < min(Td, Tout)).unsqueeze(0).expand(B, Tout).contiguous()
-    return out, mask
-
-
-def eeg_filterbank(x_nct, taps, quad=None, *, decimate=1, edge="reflect", channels=None, timepoints=None, eps=1e-8):
-    """Raw (B,Cin,Tin) recordings -> (out (B,Tout,nb*Cout), mask (B,Tout) bool) on the GPU (ign_eeg_filterbank_nct_to_btc; the rule
-    is restated in utils/eeg_filter.py:filterbank_numpy): eeg_preprocess for the nb bands `taps` (nb, M) at once -- the extended row
-    is staged once and every band runs over it.  The output is band-major: channel j * Cout + c is electrode c of band j, each
-    band block cropped / zero-padded to `channels` electrodes on its own, and without `quad` block j is eeg_preprocess(x, taps[j],
-    ...) bit for bit.  With `quad` (nb, M), the quadrature taps of utils.eeg_filter.design_quadrature, every band's output is its
-    envelope sqrt(a^2 + b^2) before the standardisation; that needs edge='reflect' and M > 1."""
-    name = "eeg_filterbank"
-    _need_gpu(name, x_nct, taps, quad)
-    if x_nct.dim() != 3 or taps.dim() != 2:
-        raise _lib.IgnError(f"{name}: expected x (B,Cin,Tin) and taps (nb,M), got {tuple(x_nct.shape)} and {tuple(taps.shape)}")
-    if quad is not None and tuple(quad.shape) != tuple(taps.shape):
-        raise _lib.IgnError(f"{name}: quad {tuple(quad.shape)} does not have the shape of taps {tuple(taps.shape)}")
+def _eeg_bank(name, x_nct, taps, quad, decimate, edge, channels, timepoints, eps):
+    """The work eeg_filterbank and eeg_preprocess share, after their shape checks: taps (nb, M), quad (nb, M) or None."""
     if edge not in ("reflect", "zero"):
         raise ValueError(f"{name}: edge={edge!r} is neither 'reflect' nor 'zero'")
     x, h = x_nct.contiguous(), taps.contiguous()
@@ -228,6 +188,36 @@ def eeg_filterbank(x_nct, taps, quad=None, *, decimate=1, edge="reflect", channe
                "ign_eeg_filterbank_nct_to_btc")
     mask = (torch.arange(Tout, device=x.device) < min(Td, Tout)).unsqueeze(0).expand(B, Tout).contiguous()
     return out, mask
+
+
+def eeg_preprocess(x_nct, taps, *, decimate=1, edge="reflect", channels=None, timepoints=None, eps=1e-8):
+    """Raw (B,Cin,Tin) recordings -> (out (B,Tout,Cout), mask (B,Tout) bool) on the GPU: eeg_filterbank for the one band `taps`
+    (M,) -- the centred FIR filter `taps` (float32, on the GPU, odd length), every `decimate`-th output, channels cropped /
+    zero-padded to `channels` (None: Cin), time to `timepoints` (None: Td = ceil(Tin / decimate)), then the per-sample,
+    per-channel standardisation of standardise_nct_to_btc over the Tv = min(Td, Tout) valid steps.  mask[b, t] = t < Tv; the
+    output is exactly zero where the mask is false and in padded channels.  `edge`: how the row is extended by
+    (len(taps) - 1) / 2 samples, 'reflect' (numpy pad 'reflect') or 'zero'."""
+    name = "eeg_preprocess"
+    _need_gpu(name, x_nct, taps)
+    if x_nct.dim() != 3 or taps.dim() != 1:
+        raise _lib.IgnError(f"{name}: expected x (B,Cin,Tin) and taps (M,), got {tuple(x_nct.shape)} and {tuple(taps.shape)}")
+    return _eeg_bank(name, x_nct, taps.unsqueeze(0), None, decimate, edge, channels, timepoints, eps)
+
+
+def eeg_filterbank(x_nct, taps, quad=None, *, decimate=1, edge="reflect", channels=None, timepoints=None, eps=1e-8):
+    """Raw (B,Cin,Tin) recordings -> (out (B,Tout,nb*Cout), mask (B,Tout) bool) on the GPU (ign_eeg_filterbank_nct_to_btc; the rule
+    is restated in utils/eeg_filter.py:filterbank_numpy): the nb bands `taps` (nb, M) at once -- the extended row is staged once
+    and every band runs over it.  The output is band-major: channel j * Cout + c is electrode c of band j, each band block cropped /
+    zero-padded to `channels` electrodes on its own, and without `quad` block j is eeg_preprocess(x, taps[j], ...) bit for bit.
+    With `quad` (nb, M), the quadrature taps of utils.eeg_filter.design_quadrature, every band's output is its envelope
+    sqrt(a^2 + b^2) before the standardisation; that needs edge='reflect' and M > 1."""
+    name = "eeg_filterbank"
+    _need_gpu(name, x_nct, taps, quad)
+    if x_nct.dim() != 3 or taps.dim() != 2:
+        raise _lib.IgnError(f"{name}: expected x (B,Cin,Tin) and taps (nb,M), got {tuple(x_nct.shape)} and {tuple(taps.shape)}")
+    if quad is not None and tuple(quad.shape) != tuple(taps.shape):
+        raise _lib.IgnError(f"{name}: quad {tuple(quad.shape)} does not have the shape of taps {tuple(taps.shape)}")
+    return _eeg_bank(name, x_nct, taps, quad, decimate, edge, channels, timepoints, eps)
 
 
 def augment(x, seed, *, lengths=None, shift=0.0, scale=0.0, noise=0.0, channel_drop=0.0, time_mask=0.0):

@@ -50,13 +50,18 @@ class EEGPreprocessSpec(NamedTuple):
 
 
 class Resolved(NamedTuple):
-    """A spec resolved against one data set: ``resolve`` returns it; the fields are the arguments of ``ops.eeg_preprocess``."""
-    taps: np.ndarray
+    """A one-band spec resolved against one data set: ``resolve`` returns it; the fields are the arguments of
+    ``ops.eeg_preprocess``.  The properties answer what a ResolvedBank answers, for the bank of one that it is."""
+    taps: np.ndarray                                # (M,)
     q: int
     edge: str
     Cout: int
     Tout: int
     Tv: int
+
+    quad = property(lambda self: None)
+    channels = property(lambda self: self.Cout)
+    taps2d = property(lambda self: self.taps[None], doc="the taps as a bank's (nb, M) = (1, M)")
 
 
 class ResolvedBank(NamedTuple):
@@ -71,9 +76,8 @@ class ResolvedBank(NamedTuple):
     Tv: int
     bands: tuple                                    # ((lo, hi), ...) in Hz; an open upper edge is sfreq / (2 Q) when decimating, else None
 
-    @property
-    def channels(self):
-        return len(self.bands) * self.Cout
+    channels = property(lambda self: len(self.bands) * self.Cout)
+    taps2d = property(lambda self: self.taps)
 
 
 def bank_channel(res, index):
@@ -168,7 +172,7 @@ def parse_eeg_preprocess(text):
                 raise ValueError(f"--eeg_preprocess: upper band edge {hi} Hz is above {nyq} Hz = sfreq / (2 * decimate): it would alias")
             if not 0 < hi < sfreq / 2:
                 raise ValueError(f"--eeg_preprocess: upper band edge {hi} Hz outside (0, {sfreq / 2}) Hz")
-        hi_eff = hi if hi is not None else (nyq if q > 1 else None)
+        hi_eff = _upper_edge(sfreq, hi, q)
         if lo is not None and hi_eff is not None and lo >= hi_eff:
             raise ValueError(f"--eeg_preprocess: empty band {lo}:{hi_eff} Hz")
         return lo, hi, hi_eff
@@ -243,18 +247,25 @@ def design_quadrature(sfreq, lo, hi, numtaps):
     return g * win / scale
 
 
+def _upper_edge(sfreq, hi, q):
+    """the effective upper edge of a band: `hi`; an open one is sfreq / (2 Q) when decimating (the anti-aliasing low-pass), else None"""
+    return hi if hi is not None else (sfreq / (2 * q) if q > 1 else None)
+
+
+def _bank_edges(spec):
+    """the (lo, effective hi) of every band of a spec; a one-band spec is a bank of one"""
+    bands = spec.bank if spec.bank is not None else ((spec.lo, spec.hi),)
+    return tuple((lo, _upper_edge(spec.sfreq, hi, spec.decimate)) for lo, hi in bands)
+
+
 def default_numtaps(spec, notice=print):
     """``taps=`` if given; 20 Q + 1 when only decimating (scipy.signal.decimate's choice); else the smallest odd number
-    >= 3.3 * sfreq / d with d the lowest non-zero band edge (the Hamming window's transition width), capped at MAX_TAPS."""
+    >= 3.3 * sfreq / d with d the lowest non-zero edge of all bands (the Hamming window's transition width), capped at MAX_TAPS."""
     if spec.taps is not None:
         return spec.taps
-    if spec.bank is not None:                         # one M for all bands: the lowest non-zero edge over the whole bank
-        d = min(v for lo, hi in _bank_edges(spec) for v in (lo, hi) if v is not None)
-    elif spec.lo is None and spec.hi is None:
+    if spec.bank is None and spec.lo is None and spec.hi is None:
         return 20 * spec.decimate + 1 if spec.decimate > 1 else 1
-    else:
-        hi_eff = spec.hi if spec.hi is not None else (spec.sfreq / (2 * spec.decimate) if spec.decimate > 1 else None)
-        d = min(v for v in (spec.lo, hi_eff) if v is not None)
+    d = min(v for band in _bank_edges(spec) for v in band if v is not None)
     m = int(math.ceil(3.3 * spec.sfreq / d - 1e-9))
     m += 1 - m % 2
     if m > MAX_TAPS:
@@ -265,27 +276,21 @@ def default_numtaps(spec, notice=print):
     return m
 
 
-def _bank_edges(spec):
-    """the (lo, effective hi) of every band of a bank spec: an open upper edge is sfreq / (2 Q) when decimating"""
-    nyq = spec.sfreq / (2 * spec.decimate) if spec.decimate > 1 else None
-    return tuple((lo, hi if hi is not None else nyq) for lo, hi in spec.bank)
-
-
 def bank_taps(spec, notice=print):
-    """A bank spec -> (H (nb, M) float64, G (nb, M) float64 or None, bands): design_fir / design_quadrature per band, one M."""
-    M = default_numtaps(spec, notice)
+    """Any spec -> (H (nb, M) float64, G (nb, M) float64 or None, bands): design_fir / design_quadrature per band, one M.  A
+    one-band spec gives its single row; one with neither a band nor decimation the identity ``[[1.0]]``."""
     bands = _bank_edges(spec)
+    if bands == ((None, None),):
+        return np.ones((1, 1), dtype=np.float64), None, bands
+    M = default_numtaps(spec, notice)
     H = np.stack([design_fir(spec.sfreq, lo, hi, M) for lo, hi in bands])
     G = np.stack([design_quadrature(spec.sfreq, lo, hi, M) for lo, hi in bands]) if spec.envelope else None
     return H, G, bands
 
 
 def spec_taps(spec, notice=print):
-    """The float64 taps of a spec: ``[1.0]`` with neither a band nor decimation, else design_fir over the effective band."""
-    hi_eff = spec.hi if spec.hi is not None else (spec.sfreq / (2 * spec.decimate) if spec.decimate > 1 else None)
-    if spec.lo is None and hi_eff is None:
-        return np.ones(1, dtype=np.float64)
-    return design_fir(spec.sfreq, spec.lo, hi_eff, default_numtaps(spec, notice))
+    """The float64 taps (M,) of a one-band spec: ``[1.0]`` with neither a band nor decimation, else design_fir over its band."""
+    return bank_taps(spec, notice)[0][0]
 
 
 def resolve(spec, Cin, Tin, target_channels=None, target_timepoints=None, notice=print):
@@ -295,13 +300,8 @@ def resolve(spec, Cin, Tin, target_channels=None, target_timepoints=None, notice
     bands) instead; Cout (and with ``fit`` target_channels) counts electrodes PER BAND, the items have nb * Cout channels."""
     spec = parse_eeg_preprocess(spec)
     Cin, Tin, q = int(Cin), int(Tin), int(spec.decimate)
-    quad = bands = None
-    if spec.bank is not None:
-        taps, quad, bands = bank_taps(spec, notice)
-        M = taps.shape[1]
-    else:
-        taps = spec_taps(spec, notice)
-        M = len(taps)
+    taps, quad, bands = bank_taps(spec, notice)
+    M = taps.shape[1]
     R = (M - 1) // 2
     if spec.edge == 'reflect' and R >= Tin:
         raise ValueError(f"--eeg_preprocess: {M} taps reflect {R} samples about each end, but the rows have {Tin}; "
@@ -319,9 +319,8 @@ def resolve(spec, Cin, Tin, target_channels=None, target_timepoints=None, notice
     if Tv < 2:
         raise ValueError(f"--eeg_preprocess: {Tv} valid time step(s) after decimating {Tin} samples by {q} and fitting to {Tout}; "
                          f"the standardisation needs at least 2")
-    if bands is not None:
-        return ResolvedBank(taps, quad, q, spec.edge, Cout, Tout, Tv, bands)
-    return Resolved(taps, q, spec.edge, Cout, Tout, Tv)
+    return (ResolvedBank(taps, quad, q, spec.edge, Cout, Tout, Tv, bands) if spec.bank is not None
+            else Resolved(taps[0], q, spec.edge, Cout, Tout, Tv))
 
 
 # --------------------------------------------------------------------------------------------------------- the rule, in numpy
@@ -413,9 +412,8 @@ def filterbank_numpy(x_nct, taps, quad=None, q=1, edge='reflect', channels=None,
     x = np.asarray(x_nct)
     blocks = []
     for j in range(H.shape[0]):
-        if G is None:
-            blocks.append(preprocess_numpy(x, H[j], q, edge, channels, timepoints, eps, dtype, standardise))
-        else:
-            f = envelope_of(filter_decimate(x, H[j], q, edge, dtype), filter_decimate(x, G[j], q, edge, dtype), dtype)
-            blocks.append(_fit_standardise(f, channels, timepoints, eps, dtype, standardise))
+        f = filter_decimate(x, H[j], q, edge, dtype)
+        if G is not None:
+            f = envelope_of(f, filter_decimate(x, G[j], q, edge, dtype), dtype)
+        blocks.append(_fit_standardise(f, channels, timepoints, eps, dtype, standardise))
     return np.concatenate(blocks, axis=-1)

@@ -141,6 +141,27 @@ def test_block_j_of_the_bank_is_the_one_band_rule_exactly():
             F.filterbank_numpy(x, kw["taps"], kw["quad"], 1, kw["edge"])
 
 
+@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["float64", "float32"])
+def test_a_band_is_the_bank_of_one_in_numpy(dtype):
+    """filterbank_numpy with a (1, M) tap array is preprocess_numpy with that row, value for value: three rows of the case table
+    (first band, both edge modes), the identity spec and a decimate-only spec."""
+    F = _F()
+    for label in ("A_one_band", "B_crop_pad", "D_channel_crop"):
+        k = case(label, False)
+        x, h, q, Cout, Tout = k["x"], k["H"][0], k["q"], k["Cout"], k["Tout"]
+        for edge in ("reflect", "zero"):
+            got = F.filterbank_numpy(x, h[None], None, q, edge, Cout, Tout, dtype=dtype)
+            assert got.dtype == dtype and np.array_equal(got, F.preprocess_numpy(x, h, q, edge, Cout, Tout, dtype=dtype)), (label, edge)
+        raw = F.filterbank_numpy(x, h[None], None, q, "reflect", Cout, Tout, dtype=dtype, standardise=False)
+        assert np.array_equal(raw, F.preprocess_numpy(x, h, q, "reflect", Cout, Tout, dtype=dtype, standardise=False)), label
+    x = case("B_crop_pad", False)["x"]                                       # (2, 5, 131)
+    for text, M in (("none", 1), ("decimate=2", 41)):
+        r = F.resolve(text, 5, 131, notice=None)
+        assert r.taps.shape == (M,) and r.taps2d.shape == (1, M)
+        got = F.filterbank_numpy(x, r.taps2d, r.quad, r.q, r.edge, r.Cout, r.Tout, dtype=dtype)
+        assert np.array_equal(got, F.preprocess_numpy(x, r.taps, r.q, r.edge, r.Cout, r.Tout, dtype=dtype)), text
+
+
 def test_envelope_blocks_are_standardised_envelopes():
     F = _F()
     k = case("B_crop_pad", True)
@@ -205,6 +226,37 @@ def test_resolve_bank():
         F.resolve("bank=8:13+13:30,taps=21,fit", 12, 100)
 
 
+def test_both_records_answer_the_same_questions():
+    """Resolved is the bank of one: quad, channels and the (nb, M) view of the taps under ResolvedBank's names, as read-only
+    properties beside the six fields; and the one design path behind both."""
+    F = _F()
+    r1 = F.resolve("band=8:30,decimate=2,fit", 122, 1651, 64, 500)
+    assert isinstance(r1, F.Resolved) and r1._fields == ("taps", "q", "edge", "Cout", "Tout", "Tv") and len(r1) == 6
+    assert r1.quad is None and r1.channels == r1.Cout == 64
+    assert r1.taps.shape == (207,) and r1.taps2d.shape == (1, 207) and np.array_equal(r1.taps2d[0], r1.taps)
+    assert np.shares_memory(r1.taps2d, r1.taps)
+    for name in ("quad", "channels", "taps2d"):
+        with pytest.raises(AttributeError):
+            setattr(r1, name, 0)
+    rb = F.resolve("bank=8:13+13:30,taps=41,decimate=2", 12, 200)
+    assert rb._fields == ("taps", "quad", "q", "edge", "Cout", "Tout", "Tv", "bands") and rb.taps2d is rb.taps and rb.channels == 24
+    # a one-band spec and the bank of that band resolve to the same numbers
+    b1 = F.resolve("bank=8:30,decimate=2,fit", 122, 1651, 64, 500)
+    assert np.array_equal(b1.taps, r1.taps2d) and b1[2:7] == r1[1:] and b1.channels == r1.channels
+    # the design path for every kind of spec: (H (nb, M), G or None, bands)
+    P = F.parse_eeg_preprocess
+    H, G, bands = F.bank_taps(P("band=8:30,decimate=2"))
+    assert H.shape == (1, 207) and G is None and bands == ((8.0, 30.0),) and np.array_equal(H[0], F.spec_taps(P("band=8:30,decimate=2")))
+    H, G, bands = F.bank_taps(P("fit"))
+    assert H.dtype == np.float64 and H.tolist() == [[1.0]] and G is None and bands == ((None, None),)
+    H, G, bands = F.bank_taps(P("decimate=3"))
+    assert H.shape == (1, 61) and bands == ((None, 500.0 / 6),) and np.array_equal(H[0], F.design_fir(500.0, None, 500.0 / 6, 61))
+    H, G, bands = F.bank_taps(P("band=20:,decimate=2"))                      # an open upper edge is sfreq / (2 Q) when decimating
+    assert H.shape == (1, 83) and bands == ((20.0, 125.0),)
+    assert F.bank_taps(P("band=20:"))[2] == ((20.0, None),)                   # and stays open without decimation
+    assert list(F.spec_taps(P("none"))) == [1.0] and F.spec_taps(P("none")).shape == (1,)
+
+
 # ---------------------------------------------------------------- the loader
 def _shards(tmp_path, n=50, C=12, T=200):
     rng = np.random.RandomState(1)
@@ -249,6 +301,21 @@ def test_dataset_reports_the_bank_shape_and_its_cpu_items_follow_the_rule(tmp_pa
     # without fit: every electrode of every band, Td time steps
     ds, _ = data_provider(_ns(tmp_path, device_standardise=False, eeg_preprocess="bank=8:13+13:30,taps=41,decimate=2"), "val")
     assert (ds.enc_in, ds.seq_len) == (24, 100) and ds[0][0].shape == (100, 24)
+
+
+def test_one_band_cpu_item_is_the_one_band_rule_exactly(tmp_path):
+    """The data set's item path makes one filterbank_numpy call for every spec; for a one-band spec the item is still
+    preprocess_numpy of the raw item, value for value."""
+    import speech_imagery_eeg_amd  # noqa: F401
+    from data_provider.eeg_npy import EEGNpyDataset3Class
+    F = _F()
+    X = _shards(tmp_path)
+    ds = EEGNpyDataset3Class(str(tmp_path), flag="train", preprocess="band=8:30,decimate=2,fit", target_channels=8, target_timepoints=120)
+    assert isinstance(ds.pre, F.Resolved) and (ds.enc_in, ds.seq_len, ds.pre.Tv) == (8, 120, 100)
+    for i in (0, 7):
+        want = F.preprocess_numpy(X[ds.idx[i]], ds.pre.taps.astype(np.float32), 2, "reflect", 8, 120).astype(np.float32)
+        got = ds[i][0].numpy()
+        assert got.shape == (100, 8) and got.dtype == np.float32 and np.array_equal(got, want)
 
 
 # ---------------------------------------------------------------- ABI

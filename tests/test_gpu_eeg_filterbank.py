@@ -63,8 +63,8 @@ def test_kernel_matches_the_rule_with_zero_extension():
 
 @pytest.mark.parametrize("label", ["A_one_band", "C_tile_crossing", "E_two_sweeps"])
 def test_block_j_is_the_one_band_op_bit_for_bit(label):
-    """Without quad, band j runs the one-band kernel's tap walk, statistics and output line over the same staged row, so block j is
-    ops.eeg_preprocess with H[j]: the same operations in the same order, the same bits.  A_one_band is nb = 1: the whole output."""
+    """Without quad, band j's tap walk, statistics and output line do not depend on the other bands, so block j is the bank of one that
+    ops.eeg_preprocess runs with H[j]: the same operations in the same order, the same bits.  A_one_band is nb = 1: the whole output."""
     ops, F = _mods()
     dev = _dev()
     k = case(label, False)

@@ -6,6 +6,9 @@ import numpy as np
 import pytest
 import torch
 
+# the recipe of test_standardise_matches_cpu_normalizer: standard deviations of 5 to 80 uV, offsets of +-2e4 uV
+from eeg_filterbank_cases import recordings as _recordings
+
 pytestmark = pytest.mark.gpu
 
 
@@ -20,12 +23,6 @@ def _mods():
     from ign_hip import ops
     from utils import eeg_filter
     return ops, eeg_filter
-
-
-def _recordings(B, C, T):
-    """The recipe of test_standardise_matches_cpu_normalizer: standard deviations of 5 to 80 uV, offsets of +-2e4 uV."""
-    rng = np.random.RandomState(B + C + T)
-    return (rng.randn(B, C, T) * rng.uniform(5, 80, size=(B, C, 1)) + rng.uniform(-2e4, 2e4, size=(B, C, 1))).astype(np.float32)
 
 
 def _taps(F, kind, M, q):
@@ -83,6 +80,33 @@ def test_kernel_matches_the_rule(label, B, Cin, Tin, kind, M, q, edge, Cout, Tou
     if Tv > 2:                                              # the statistics are those of the valid part only (the bounds of
         assert float(o[:, :Tv, :Cv].mean(dim=1).abs().max()) < 1e-3               # test_standardise_matches_cpu_normalizer)
         assert float((o[:, :Tv, :Cv].std(dim=1, unbiased=True) - 1).abs().max()) < 1e-3
+
+
+# (label, B, Cin, Tin, taps, M, q, edge, Cout, Tout): eeg_filterbank_cases' A_one_band, and the row of CASES whose 33 channels cross the
+# transpose's 32-channel tile and are padded to 40
+DIRECT = [("A_one_band", 2, 5, 64, "bandpass", 21, 1, "reflect", 5, 64), CASES[1]]
+
+
+@pytest.mark.parametrize("label,B,Cin,Tin,kind,M,q,edge,Cout,Tout", DIRECT, ids=[c[0].replace(" ", "_") for c in DIRECT])
+def test_one_band_entry_points_are_the_bank_of_one(label, B, Cin, Tin, kind, M, q, edge, Cout, Tout):
+    """No Python caller reaches ign_eeg_preprocess_nct_to_btc / ign_eeg_preprocess_ws_bytes any more (ops.eeg_preprocess goes through
+    the bank's entry points), so they are called here directly: the bits of ops.eeg_filterbank(x, h[None]) and the bank's workspace
+    size at nb = 1."""
+    ops, F = _mods()
+    from ign_hip import _lib
+    dev = _dev()
+    L = _lib.lib()
+    x = torch.from_numpy(_recordings(B, Cin, Tin)).to(dev)
+    h = torch.from_numpy(_taps(F, kind, M, q).astype(np.float32)).to(dev)
+    nbytes = L.ign_eeg_preprocess_ws_bytes(B, Cin, Tin, M, q, Cout, Tout)
+    assert nbytes == L.ign_eeg_filterbank_ws_bytes(B, Cin, Tin, M, 1, q, Cout, Tout) == B * min(Cin, Cout) * min(-(-Tin // q), Tout) * 4
+    out = torch.full((B, Tout, Cout), float("nan"), device=dev)                    # every element has to be written
+    ws = torch.empty(nbytes // 4, device=dev)
+    _lib.check(L.ign_eeg_preprocess_nct_to_btc(ops._ptr(x), ops._ptr(h), ops._ptr(out), ops._ptr(ws), B, Cin, Tin, M, q, F.EDGES[edge],
+                                               Cout, Tout, 1e-8, ops._stream()), "ign_eeg_preprocess_nct_to_btc")
+    want, _ = ops.eeg_filterbank(x, h[None], decimate=q, edge=edge, channels=Cout, timepoints=Tout)
+    assert want.shape == out.shape and torch.equal(out, want)
+    assert torch.equal(out, ops.eeg_preprocess(x, h, decimate=q, edge=edge, channels=Cout, timepoints=Tout)[0])
 
 
 def _identity(B=3, C=5, T=50):
