@@ -283,10 +283,20 @@ def test_eegcnn_train_step_at_short_rows_with_many_samples(T, k1):
         parity(f"short rows T={T} k={k1}: grad." + n, u, v, kind="scale", ref_is="same module, layer-by-layer torch ops (float64, CPU)")
 
 
-@pytest.mark.parametrize("shape,Co,bias", [((256, 100, 512), 256, True), ((3, 77, 64), 512, True), ((5, 130), 12, False),
-                                           ((2, 1000, 512), 2048, True)])
-@pytest.mark.parametrize("wgrad,gmath,scale", [("bf16x6", "bf16x6", 1.0), ("f32", "bf16x6", 1.0), ("bf16x6", "f16x3", 1.0),
-                                               ("bf16x6", "f16x3", 1e-6), ("bf16x6", "f16x3", 1e5)])
+# second list: row-count edges of the 128 x 128-tile k = 1 weight-gradient kernel (clconv_wgrad_x6_k1_kernel) on both split arithmetics
+# -- one row; less than a 16-row unit; a ragged second unit over two ci / co tiles; 33 units = 2 splits with 11 live rows in the last
+# unit; 257 units = 9 splits, i.e. a second round over the 8 XCDs whose surplus workgroups return early
+_LINEAR_CASES = [pytest.param(shape, Co, bias, *arith, id="-".join(map(str, arith)) + f"-shape{i}-{Co}-{bias}")     # (ids as before the
+                 for i, (shape, Co, bias) in enumerate([((256, 100, 512), 256, True), ((3, 77, 64), 512, True),    # second list existed)
+                                                        ((5, 130), 12, False), ((2, 1000, 512), 2048, True)])
+                 for arith in [("bf16x6", "bf16x6", 1.0), ("f32", "bf16x6", 1.0), ("bf16x6", "f16x3", 1.0), ("bf16x6", "f16x3", 1e-6),
+                               ("bf16x6", "f16x3", 1e5)]] + \
+                [pytest.param((M, Ci), Co, True, *arith, id="-".join(map(str, arith)) + f"-rows{M}x{Ci}-{Co}-True")
+                 for M, Ci, Co in [(1, 4, 4), (15, 8, 12), (17, 132, 132), (523, 128, 64), (4100, 64, 64)]
+                 for arith in [("bf16x6", "bf16x6", 1.0), ("bf16x6", "f16x3", 1.0)]]
+
+
+@pytest.mark.parametrize("shape,Co,bias,wgrad,gmath,scale", _LINEAR_CASES)
 def test_linear_on_own_gemm_kernels(shape, Co, bias, wgrad, gmath, scale, monkeypatch):
     """ops.linear (forward / input gradient / weight gradient on the split kernels: six-product bf16 or three-product fp16 with
     power-of-two operand scaling; weight gradient alternatively on the fp32-MFMA TN kernel) against float64 torch.  `scale`:
