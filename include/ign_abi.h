@@ -266,6 +266,29 @@ int ign_shapelet_regate_bank(int G, float* const* d_save, const int32_t* len_b, 
                              float* dmin_out, int ld, const int* col0, int32_t* const* tstar, float* const* zmu, int B, int C, int T,
                              const int* K, const int* L, const int* stride, float eps, int mode, void* stream);
 
+/* Shapelet projection (csrc/ign_shapelet_project.hip; run.py --shapelet_project): every shapelet of one length group is snapped
+ * to the nearest window of a training set that is streamed batch by batch.  Runs AFTER the shapelet forward of a batch, on its
+ * outputs: dmin and tstar are (B, ld), column col0 + k*C + c -- the minimum distance per sample and feature and the index of its
+ * window (the layout of ign_shapelet_fwd's dmin_out, and of the (B,K,C) tstar tables of a bank concatenated along the features).
+ * Per (k, c):
+ *   candidates  the samples b with 0 <= tstar < Tw = (T - L)/stride + 1 (ign_shapelet_regate gives a sample shorter than the
+ *               shapelet tstar = -1: it never takes part; an index past Tw is never used as an address either);
+ *   j           the candidate with the smallest dmin, the lowest b on ties; strict <, so a NaN (or +inf) never wins;
+ *   the running best is replaced if accumulate == 0, or if dmin[j] < best_d_kc[k,c] strictly (an earlier batch wins a tie, i.e.
+ *   the lowest global sample index).  On replacement: best_d_kc[k,c] = dmin[j], best_src_kc2[k,c] = (sample0 + j, tstar[j]),
+ *   cand_kcl[k,c,:] = xn_bct[j, c, tstar[j]*stride : +L], copied bit for bit.
+ *   accumulate == 0 and no candidate: best_d = +inf, src = (-1, -1), the cand row is left untouched.
+ * No atomics, no workspace, a fixed order: bitwise repeatable.  Any B, C, K; 1 <= L <= T; stride >= 1; sample0 >= 0.  Nothing is
+ * launched on an error.
+ * ign_shapelet_project_step_bank: every group of a bank (tables of G <= 8 host entries, as ign_shapelet_fwd_bank; dmin / tstar /
+ * ld shared), each validated before the first launch.                                                                            */
+int ign_shapelet_project_step(const float* xn_bct, const float* dmin, const int32_t* tstar, int ld, int col0, int sample0,
+                              float* best_d_kc, int32_t* best_src_kc2, float* cand_kcl, int accumulate, int B, int C, int T, int K,
+                              int L, int stride, void* stream);
+int ign_shapelet_project_step_bank(const float* xn_bct, const float* dmin, const int32_t* tstar, int ld, int G, const int* col0,
+                                   int sample0, float* const* best_d_kc, int32_t* const* best_src_kc2, float* const* cand_kcl,
+                                   int accumulate, int B, int C, int T, const int* K, const int* L, const int* stride, void* stream);
+
 /* Augmentation (csrc/ign_augment.hip; run.py --augment): the training batch x (B,T,C) -> out (B,T,C), one launch, out of place
  * (x == out: IGN_E_ARG; the buffers must not overlap), no workspace, no atomics, bitwise repeatable.  len_b (B) int32 on the DEVICE
  * or NULL (every sample has T steps); n = len_b[b] clamped to 0..T.

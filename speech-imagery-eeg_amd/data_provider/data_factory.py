@@ -91,6 +91,28 @@ def data_provider(args, flag, bin_edges=None):
     return data_set, loader
 
 
+def ordered_loader(loader):
+    """An unshuffled, un-sharded loader over the data set of `loader` (a DataLoader, a TensorBatchLoader, or a DevicePrefetcher
+    around either): batch i holds the data set's items i*batch_size ..., on every rank, so a sample's ordinal in the stream is
+    its data set index -- what a pass that reports sample indices needs (utils/shapelet_project.py).  Same batch size, collate_fn
+    and device_transform / eeg_preprocess attributes; no sampler, drop_last=False.  A DataLoader draws its per-iteration seed
+    from a generator of its own, so iterating the result leaves torch's global RNG stream where it was."""
+    from data_provider.device_prefetch import DevicePrefetcher, TensorBatchLoader
+    if isinstance(loader, DevicePrefetcher):
+        return DevicePrefetcher(ordered_loader(loader.loader), loader.device, transform=loader.transform, depth=loader.depth)
+    if isinstance(loader, TensorBatchLoader):
+        out = TensorBatchLoader(loader.dataset, loader.batch_size, shuffle=False, sampler=None, pin_memory=loader.pin)
+    elif isinstance(loader, DataLoader):
+        out = DataLoader(loader.dataset, batch_size=loader.batch_size, shuffle=False, sampler=None, num_workers=loader.num_workers,
+                         drop_last=False, pin_memory=loader.pin_memory, collate_fn=loader.collate_fn, generator=torch.Generator())
+    else:
+        raise TypeError(f"ordered_loader: expected a DataLoader, TensorBatchLoader or DevicePrefetcher, got {type(loader).__name__}")
+    for attr in ('device_transform', 'eeg_preprocess'):
+        if hasattr(loader, attr):
+            setattr(out, attr, getattr(loader, attr))
+    return out
+
+
 def _regression_provider(args, flag, bin_edges):
     """IGN/data_factory/data_factory.py:123-137.  `bin_edges`: None for the train split (the loader derives them), the train
     split's edges for val / test.  Every batch is padded / clipped to the dataset's max_seq_len and subsampled with the

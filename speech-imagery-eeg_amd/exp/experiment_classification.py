@@ -426,6 +426,7 @@ class Experiment(object):
         early_stopping = EarlyStopping(patience=a.patience, verbose=self.rank == 0, delta=0)
         t_start = time.time()
         train_step = 0
+        project_every, project_end = self._project_schedule()          # --shapelet_project; (0, False) by default
         for epoch in range(a.train_epochs):
             if len(self.train_loader) == 0:
                 continue
@@ -433,6 +434,8 @@ class Experiment(object):
             if not losses:
                 continue
             train_loss = torch.stack(losses).mean().item()      # one host sync per epoch (the reference syncs per step)
+            if project_every and (epoch + 1) % project_every == 0:
+                self._project_shapelets()       # before validation: early stopping and the checkpoint see the projected model
             if self.distributed:
                 # BatchNorm running statistics are per rank (each rank saw its own shards); the model that is validated,
                 # early-stopped on and checkpointed is rank 0's, so every rank evaluates THAT one ...
@@ -469,7 +472,104 @@ class Experiment(object):
         best = os.path.join(self.checkpoint_dir, 'checkpoint.pth')
         if os.path.exists(best):
             self.model.load_state_dict(torch.load(best, map_location=self.device, weights_only=True))
+        if project_end:
+            self._project_final(best)
         return self.model
+
+    # -- `--shapelet_project`: snap the shapelets to real training windows (utils/shapelet_project.py) ---------------------------
+    def _project_schedule(self):
+        """--shapelet_project -> (N, at_end): project after every N-th epoch's training pass (0: never) / after the best
+        checkpoint is reloaded.  none (the default, also for a namespace without the flag): (0, False)."""
+        how = getattr(self.args, 'shapelet_project', 'none')
+        if how is None or how == 'none':
+            return 0, False
+        if how == 'end':
+            return 0, True
+        try:
+            n = int(how)
+        except (TypeError, ValueError):
+            n = 0
+        if n < 1:
+            raise ValueError(f"shapelet_project must be none|end|N with N >= 1, got {how!r}")
+        return n, True
+
+    def _project_shapelets(self):
+        """One projection of the model's shapelets onto the training set (shared by the classification and regression harnesses,
+        like _init_shapelets): an ordered, un-sharded, un-augmented pass over the training data (data_factory.ordered_loader), so
+        the reported sample ordinals are data set indices and, under several ranks, every rank computes the same bit-exact
+        shapelets -- no collective.  Adam moments, thresholds and heads are left alone.  -> the report of project_, also kept as
+        self._shapelet_sources; None when nothing was done (flag off, --test_only, a model without shapelets)."""
+        a = self.args
+        if self._project_schedule() == (0, False) or getattr(a, 'test_only', False):
+            return None
+        if a.model not in ('SBM', 'LTS', 'InterpGN'):
+            if self.rank == 0 and not getattr(self, '_project_notice', False):
+                print(f"--shapelet_project: model {a.model} has no shapelets, nothing to project")
+            self._project_notice = True
+            return None
+        from data_provider.data_factory import ordered_loader
+        from utils.shapelet_project import project_
+        rep = project_(self.model, ordered_loader(self.train_loader))
+        if self.rank == 0 and not getattr(self, '_project_notice', False):
+            print("--shapelet_project: the shapelets are now exact copies of training windows; for continued training, "
+                  "IGN_TIE_EXACT=1 / model.set_tie_exact() gives the reference's sign(0) = 0 at x == w in the L1 backward "
+                  "(not switched on automatically)")
+        self._project_notice = True
+        self._shapelet_sources = rep
+        return rep
+
+    def _project_final(self, best):
+        """The projection after training: validation before and after it, the checkpoint re-saved with the same keys (rank 0) and
+        shapelet_sources.json written beside it."""
+        if self.args.model not in ('SBM', 'LTS', 'InterpGN'):
+            self._project_shapelets()           # the notice; no validation pass for it
+            return
+        before = self._val_metrics()
+        rep = self._project_shapelets()
+        if rep is None:
+            return
+        after = self._val_metrics()
+        if self.rank == 0:
+            self._report_projection(rep, before, after, best)
+        if self.distributed:
+            dist.barrier()                      # the other ranks read the re-saved checkpoint next
+
+    def _report_projection(self, rep, before, after, best):
+        for g in rep["groups"]:
+            d = g["d_before"][torch.isfinite(g["d_before"])]
+            mean = float(d.double().mean()) if d.numel() else float('nan')
+            print(f"shapelet_project: length {g['length']} mean d_before {mean:.6g} kept {g['kept']}")
+        what = "accuracy" if before[1] is not None else "loss"
+        pick = (lambda m: m[1]) if before[1] is not None else (lambda m: m[0])
+        print(f"shapelet_project: validation {what} {pick(before):.4f} -> {pick(after):.4f} "
+              f"({rep['samples']} training samples, {rep['batches']} batches)")
+        from utils.shapelet_project import save_sources
+        torch.save(self.model.state_dict(), best)
+        save_sources(os.path.join(self.checkpoint_dir, 'shapelet_sources.json'), rep)
+
+    def _shapelet_sources_for_test(self):
+        """What test() reports about a projection: this run's report, else -- with the flag on, e.g. under --test_only -- the
+        sidecar beside the checkpoint; None when nothing was projected."""
+        rep = getattr(self, '_shapelet_sources', None)
+        if rep is not None:
+            return rep
+        if self._project_schedule() == (0, False):
+            return None
+        path = os.path.join(self.checkpoint_dir, 'shapelet_sources.json')
+        if not os.path.exists(path):
+            return None
+        from utils.shapelet_project import load_sources
+        return load_sources(path)
+
+    def _project_summary(self):
+        """The summary CSV's columns of a run with --shapelet_project on (none: no column is added): the flag, and the mean
+        distance between the shapelets and the windows that replaced them."""
+        if self._project_schedule() == (0, False):
+            return {}
+        src = self._shapelet_sources_for_test()
+        d = None if src is None else src["d_before"][torch.isfinite(src["d_before"])]
+        return {'shapelet_project': str(self.args.shapelet_project),
+                'project_d_mean': float(d.double().mean()) if d is not None and d.numel() else None}
 
     def _val_metrics(self):
         """-> (val_loss, val_accuracy or None) for the epoch loop of train()."""
@@ -605,6 +705,9 @@ class Experiment(object):
             if a.model == 'InterpGN':
                 res.eta = host(buf.eta)
                 res.dnn_preds = host(buf.dnn_preds)
+            src = self._shapelet_sources_for_test()
+            if src is not None:                 # --shapelet_project: which training window every shapelet is a copy of
+                res.shapelet_source, res.shapelet_source_start, res.shapelet_source_d = src["source"], src["start"], src["d_before"]
         test_df = None
         if save_csv and result_dir is not None and self.rank == 0:
             test_df = self._write_summary(res, result_dir)
@@ -636,6 +739,7 @@ class Experiment(object):
             row['w_max'] = float(w.abs().max())
             row['w_gini_clip'] = float(gini_coefficient(np.clip(w.numpy(), 0, None)))
             row['w_gini_abs'] = float(gini_coefficient(np.abs(w.numpy())))
+        row.update(self._project_summary())
         stamp = datetime.now().strftime("%Y-%m-%d-%H-%M-%S")
         path = os.path.join(result_dir, f"{a.dataset}-{a.seed}-{a.model}-{a.num_shapelet}-{a.lambda_div}-{a.lambda_reg}-{stamp}.csv")
         with open(path, "w", newline="") as f:

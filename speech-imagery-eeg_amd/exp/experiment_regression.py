@@ -196,6 +196,11 @@ class Experiment(ClassificationExperiment):
             row['w_max'] = float(w.abs().max())
             row['w_gini_clip'] = float(gini_coefficient(np.clip(w.numpy(), 0, None)))
             row['w_gini_abs'] = float(gini_coefficient(np.abs(w.numpy())))
+            src = self._shapelet_sources_for_test()
+            if src is not None:                 # --shapelet_project: which training window every shapelet is a copy of
+                df.update(shapelet_source=src["source"].numpy(), shapelet_source_start=src["start"].numpy(),
+                          shapelet_source_d=src["d_before"].numpy())
+        row.update(self._project_summary())
         if save_csv and result_dir is not None and self.rank == 0:
             self._write_row(row, result_dir)
         return test_loss, None, df

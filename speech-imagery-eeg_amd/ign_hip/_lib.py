@@ -160,6 +160,8 @@ SIGNATURES = {
     "ign_instnorm_fwd_len": (ci, [vp, vp, vp, ci, ci, ci, cf, vp]),
     "ign_shapelet_regate": (ci, [vp, vp, vp, vp, vp, ci, ci, vp, vp, ci, ci, ci, ci, ci, ci, cf, ci, vp]),
     "ign_shapelet_regate_bank": (ci, [ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, cf, ci, vp]),
+    "ign_shapelet_project_step": (ci, [vp, vp, vp, ci, ci, ci, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]),
+    "ign_shapelet_project_step_bank": (ci, [vp, vp, vp, ci, ci, vp, ci, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp]),
     "ign_loss_w_fwd_bwd_reg": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, cf, cf, vp]),
     "ign_augment_btc": (ci, [vp, vp, vp, ci, ci, ci, ctypes.c_ulonglong, cf, cf, cf, ctypes.c_uint, cf, vp]),
     "ign_eeg_preprocess_ws_bytes": (sz, [ci, ci, ci, ci, ci, ci, ci]),

@@ -572,6 +572,84 @@ def shapelet_kmeans_update(w, sums, counts):
     return w
 
 
+def _project_inputs(name, xn, d, t):
+    """The batch-side tensors of a projection step: xn (B,C,T) fp32, d (B,ld) fp32 and t (B,ld) int32 -- the Dmin and Tstar of
+    shapelet_bank(..., return_tstar=True) on that xn -- contiguous on the GPU."""
+    _need_gpu(name, xn, d)
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.int32:
+        what = f"{t.dtype} on {t.device}" if torch.is_tensor(t) else type(t).__name__
+        raise _lib.IgnError(f"{name}: t must be an int32 tensor on the GPU, got {what}")
+    if xn.dim() != 3 or d.dim() != 2 or d.shape[0] != xn.shape[0] or t.shape != d.shape:
+        raise _lib.IgnError(f"{name}: xn must be (B,C,T) and d, t (B,ld) with the same B and ld, got {tuple(xn.shape)}, "
+                            f"{tuple(d.shape)} and {tuple(t.shape)}")
+    return xn.detach().contiguous(), d.detach().contiguous(), t.contiguous()
+
+
+def _project_state(name, device, w_shape, state):
+    """-> ((best_d (K,C) f32, best_src (K,C,2) i32, cand (K,C,L) f32), accumulate): allocated when `state` is None, checked else."""
+    K, C, Lw = (int(v) for v in w_shape)
+    if state is None:
+        return (torch.empty(K, C, device=device, dtype=torch.float32), torch.empty(K, C, 2, device=device, dtype=torch.int32),
+                torch.empty(K, C, Lw, device=device, dtype=torch.float32)), 0
+    best_d, best_src, cand = state
+    _need_gpu(name, best_d, cand)
+    if not best_src.is_cuda or best_src.dtype != torch.int32:
+        raise _lib.IgnError(f"{name}: best_src must be an int32 tensor on the GPU, got {best_src.dtype} on {best_src.device}")
+    for label, s, shape in (("best_d", best_d, (K, C)), ("best_src", best_src, (K, C, 2)), ("cand", cand, (K, C, Lw))):
+        if tuple(s.shape) != shape or not s.is_contiguous():
+            raise _lib.IgnError(f"{name}: {label} must be a contiguous tensor of shape {shape}, got {tuple(s.shape)}")
+    return (best_d, best_src, cand), 1
+
+
+def shapelet_project_step(xn, d, t, col0, w_shape, stride, sample0, state=None):
+    """One batch of the projection of one length group (ign_shapelet_project_step), behind the shapelet forward of that batch:
+    `d`, `t` (B, ld) are the Dmin and Tstar of shapelet_bank(xn, ..., return_tstar=True), the group's features start at column
+    `col0`, its shapelets have shape w_shape = (K, C, L) and window step `stride`; `sample0` is the ordinal of the batch's first
+    sample in the stream.  -> state = (best_d (K,C), best_src (K,C,2) int32, cand (K,C,L)): per shapelet the smallest distance
+    so far, the (sample ordinal, window) that attains it -- the lowest on ties -- and a bit-exact copy of that window of xn.
+    state None: allocated and overwritten (best_d = +inf, best_src = -1 where no sample has a window); given: updated where this
+    batch is strictly nearer.  Bitwise repeatable; no gradient."""
+    name = "shapelet_project_step"
+    xn, d, t = _project_inputs(name, xn, d, t)
+    B, C, T = xn.shape
+    K, Cw, Lw = (int(v) for v in w_shape)
+    if Cw != C:
+        raise _lib.IgnError(f"{name}: the shapelets have {Cw} channels, the input has {C}")
+    state, accumulate = _project_state(name, xn.device, (K, C, Lw), state)
+    _lib.check(_lib.lib().ign_shapelet_project_step(_ptr(xn), _ptr(d), _ptr(t), d.shape[1], int(col0), int(sample0), _ptr(state[0]),
+                                                    _ptr(state[1]), _ptr(state[2]), accumulate, B, C, T, K, Lw, int(stride), _stream()),
+               "ign_shapelet_project_step")
+    return state
+
+
+def shapelet_project_bank(xn, d, t, w_shapes, strides, sample0, states=None):
+    """shapelet_project_step for every length group of a bank, the groups' columns following each other from 0 in `d` / `t` as
+    shapelet_bank lays them out: one ign_shapelet_project_step_bank call for up to BANK_MAX_GROUPS groups, group by group above.
+    `states`: None or one state per group (all given or none).  -> list of states."""
+    name = "shapelet_project_bank"
+    G = len(w_shapes)
+    col0s, col0 = [], 0
+    for K, C, _ in w_shapes:
+        col0s.append(col0)
+        col0 += int(K) * int(C)
+    if G > BANK_MAX_GROUPS or G == 0:
+        states = states or [None] * G
+        return [shapelet_project_step(xn, d, t, col0s[g], w_shapes[g], strides[g], sample0, states[g]) for g in range(G)]
+    xn, d, t = _project_inputs(name, xn, d, t)
+    B, C, T = xn.shape
+    if any(int(s[1]) != C for s in w_shapes):
+        raise _lib.IgnError(f"{name}: the shapelets have {[int(s[1]) for s in w_shapes]} channels, the input has {C}")
+    if states is not None and (len(states) != G or any(s is None for s in states)):
+        raise _lib.IgnError(f"{name}: pass one state per group (accumulate) or none at all (overwrite)")
+    new = [_project_state(name, xn.device, w_shapes[g], states[g] if states is not None else None)[0] for g in range(G)]
+    ints = ctypes.c_int * G
+    _lib.check(_lib.lib().ign_shapelet_project_step_bank(
+        _ptr(xn), _ptr(d), _ptr(t), d.shape[1], G, ints(*col0s), int(sample0), _pv([s[0] for s in new]), _pv([s[1] for s in new]),
+        _pv([s[2] for s in new]), 0 if states is None else 1, B, C, T, ints(*[int(s[0]) for s in w_shapes]),
+        ints(*[int(s[2]) for s in w_shapes]), ints(*[int(s) for s in strides]), _stream()), "ign_shapelet_project_step_bank")
+    return new
+
+
 class SbmFn(torch.autograd.Function):
     """The shapelet bottleneck model behind the instance norm as ONE autograd node: shapelet bank (every length group) ->
     linear class head (optional) -> both regularisers (IGN/model/Shapelet.py:190-210, 217-230).

@@ -9,6 +9,10 @@ Differences, all repairs of fork defects listed in SURVEY section 0:
   * ``--data SYNTH`` (+ ``--synthetic n,C,T,classes``) is the synthetic CHISCO-shaped provider of the benchmark;
   * ``--shapelet_init kmeans`` (+ ``--shapelet_init_iters``, ``--shapelet_init_batches``) starts the shapelets from k-means
     centroids of the training windows instead of N(0,1); the default ``normal`` is the reference's initialisation;
+  * ``--shapelet_project none|end|N`` snaps every learned shapelet to the nearest real training window (after training, and with N
+    also every N epochs before validation), re-saves the checkpoint and writes ``shapelet_sources.json`` beside it: per shapelet the
+    data set index and first sample of the window it now is a bit-exact copy of; ``--test_only`` projects nothing and reads that
+    file; the default ``none`` changes nothing;
   * ``--mask_padding`` makes the SBM / LTS expert normalise and match every sample of a ragged (zero-padded) batch over its own
     length only; the default, off, is the reference's behaviour (the padding takes part);
   * ``--class_weight none|balanced|w0,w1,...`` and ``--label_smoothing EPS`` turn the TRAINING cross-entropy into
@@ -47,6 +51,19 @@ exp_dict = {
     "classification": ClassificationExperiment,
     "regression": RegressionExperiment,      # Monash TSER targets, binned, CRPS loss
 }
+
+
+def shapelet_project_arg(text):
+    """--shapelet_project: 'none', 'end' or an integer N >= 1 (-> int)."""
+    if text in ('none', 'end'):
+        return text
+    try:
+        n = int(text)
+    except ValueError:
+        n = 0
+    if n < 1:
+        raise argparse.ArgumentTypeError(f"expected none, end or an integer N >= 1, got {text!r}")
+    return n
 
 
 def build_parser():
@@ -100,6 +117,14 @@ def build_parser():
                         "(utils/shapelet_init.py; SBM / LTS / InterpGN, before training)")
     p.add_argument("--shapelet_init_iters", type=int, default=10, help="Lloyd iterations of --shapelet_init kmeans")
     p.add_argument("--shapelet_init_batches", type=int, default=8, help="training batches --shapelet_init kmeans clusters")
+    p.add_argument("--shapelet_project", type=shapelet_project_arg, default='none', metavar="none|end|N",
+                   help="snap every shapelet of an SBM / LTS / InterpGN model to the nearest real training window under the model's "
+                        "own distance (utils/shapelet_project.py) and record where it came from.  end: after the best checkpoint is "
+                        "reloaded -- validation before / after is printed, checkpoint.pth is re-saved with the same keys and "
+                        "shapelet_sources.json (group, k, c, data set index, start, length, distance per feature column) is written "
+                        "beside it.  N >= 1: also after the training pass of every N-th epoch, before its validation, so early "
+                        "stopping and the checkpoint see a projected model; Adam's moments are left alone.  One ordered, "
+                        "un-augmented pass over the whole training set on every rank (no collective).  none: off")
     p.add_argument("--mask_padding", action="store_true",
                    help="variable-length series: the SBM / LTS expert takes instance norm, shapelet matches and match locations over "
                         "each sample's own length (the loader's padding mask) instead of over the zero padding.  Off: the "

@@ -37,6 +37,11 @@ class ClassificationResult:
     eta: Optional[torch.Tensor] = None
     loss: Optional[float] = None
     accuracy: Optional[float] = None
+    # extension: where each shapelet came from after a projection (--shapelet_project; utils/shapelet_project.py), in p's column
+    # order; None when nothing was projected.  A row of -1: that shapelet had no candidate window and kept its learned value.
+    shapelet_source: Optional[torch.Tensor] = None          # (G*K*C, 2) int32: (training-set index, window)
+    shapelet_source_start: Optional[torch.Tensor] = None    # (G*K*C,) int32: first sample of the window = window * stride
+    shapelet_source_d: Optional[torch.Tensor] = None        # (G*K*C,) distance to that window before the projection
     # extension: where each shapelet matched each test series -- window index per (sample, shapelet) in p's column order,
     # and the (start, length) in samples it corresponds to.  The reference's visualize_shapelets re-derives this on the host
     # (IGN/utils/shapelet_util.py:153); the forward kernel already has it.
