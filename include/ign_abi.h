@@ -315,6 +315,21 @@ int ign_shapelet_project_step_bank(const float* xn_bct, const float* dmin, const
 int ign_augment_btc(const float* x_btc, float* out_btc, const int32_t* len_b, int B, int T, int C, unsigned long long seed,
                     float shift, float scale, float sigma, unsigned chan_thr, float time_mask, void* stream);
 
+/* Mixup / CutMix of the training batch (csrc/ign_mix.hip; run.py --mix): x (B,T,C) -> out (B,T,C), one launch, out of place
+ * (x == out or overlapping buffers: IGN_E_ARG), no workspace, no atomics, bitwise repeatable.  Sample b is mixed with its partner
+ * p = (b + roll) mod B.  len_b (B) int32 on the DEVICE or NULL (every sample has T steps), n = len_b[b] clamped to 0..T; lam_b (B)
+ * float32 and span_b2 (B,2) int32 = (start_b, m_b) (NULL: every span is empty) on the DEVICE:
+ *   out[b,t,c] = x[p,t,c]                                       for start_b <= t < start_b + m_b, t < n   (CutMix span)
+ *   out[b,t,c] = lam_b * x[b,t,c] + (1 - lam_b) * x[p,t,c]      for the other t < n                       (mixup)
+ *   out[b,t,c] = x[b,t,c]                                       for t >= n                                (padding copied through)
+ * The partner is read at the same t whatever its own length (its padding is zero by the loader's contract).  1 - lam_b, the two
+ * products and the sum are separate fp32 roundings (no fma): a float32 restatement (utils/mix.py:mix_reference) is bitwise equal.
+ * lam_b == 1 copies x[b,t,c] (not 1*x + 0*x_p: the partner may hold inf / NaN).  The draws (roll, lam, span) are the host's:
+ * utils/mix.py:mix_draws.  roll outside [0, B), T < 1, a null pointer: IGN_E_ARG; T * C >= 2^31 - 65536: IGN_E_TOOBIG.  Nothing is
+ * launched on an error.                                                                                                          */
+int ign_mix_btc(const float* x_btc, float* out_btc, const int32_t* len_b, const float* lam_b, const int32_t* span_b2, int roll,
+                int B, int T, int C, void* stream);
+
 /* Fused attention core softmax(scale * Q K^T) V, exact fp32 on the matrix cores (v_mfma_f32_32x32x2_f32), scores never
  * materialised.  Replaces IGN/layers/SelfAttention_Family.py:56-75 (FullAttention: no mask; dropout 0 here -- dropout p > 0
  * is ign_attn_*_dropout below) and the attention inside nn.TransformerEncoderLayer of IGN/model/eegcnn.py:219-228.
@@ -481,6 +496,19 @@ int ign_loss_fwd_bwd_reg(const float* sbm, const float* dnn, const long long* la
 int ign_loss_w_fwd_bwd_reg(const float* sbm, const float* dnn, const long long* labels, const float* class_w, const float* reg,
                            float* out, float* eta, float* loss3, float* gsbm, float* gdnn, int B, int N, float beta,
                            float label_smoothing, void* stream);
+/* The weighted tail with TWO labels per row and a per-row share lam_b of the first (run.py --mix: mixup / CutMix), in one launch.
+ * labels (ya) / labels_b (yb): int64 (B); lam_b: float32 (B) in [0, 1] (clamped into it); class_w nullable = all ones;
+ * 0 <= label_smoothing < 1.  With p = softmax(z), lp = log p, W = sum_n w_n, a_b = lam_b w[ya_b], c_b = (1 - lam_b) w[yb_b]:
+ *   D   = sum_b (a_b + c_b)
+ *   CEm = [ (1-eps) sum_b ( a_b (-lp[b,ya_b]) + c_b (-lp[b,yb_b]) ) + (eps/N) sum_b sum_n w_n (-lp[b,n]) ] / D
+ *   dCEm/dz[b,n] = [ (1-eps) ( a_b (p_n - [n = ya_b]) + c_b (p_n - [n = yb_b]) ) + (eps/N) (p_n W - w_n) ] / D
+ * loss3 = {CEm(out), CEm(sbm), CEm(out) + beta*CEm(sbm) + reg[0]}; gsbm / gdnn through the gate as above.  lam == 1 everywhere is
+ * ign_loss_w_fwd_bwd_reg's criterion; without class weights CEm = mean_b [lam_b CE(z_b, ya_b) + (1 - lam_b) CE(z_b, yb_b)].
+ * D and W are summed inside the launch in a fixed order (no atomics: two calls agree bitwise); up to 16 classes out / eta are
+ * bitwise ign_gate_fwd's.  Labels outside [0, N) are clamped into it.  Limits and error codes as ign_loss_w_fwd_bwd_reg.         */
+int ign_loss_mix_fwd_bwd_reg(const float* sbm, const float* dnn, const long long* labels, const long long* labels_b,
+                             const float* lam_b, const float* class_w, const float* reg, float* out, float* eta, float* loss3,
+                             float* gsbm, float* gdnn, int B, int N, float beta, float label_smoothing, void* stream);
 
 /* Regression loss tail (IGN/exp/experiment_regression.py:59-76): CRPS of the softmax CDF over N bins against the step CDF
  * H_j = [edges[j] >= target] (compared in float64; edges may hold +-inf, a target on an edge counts as >=), batch mean, and

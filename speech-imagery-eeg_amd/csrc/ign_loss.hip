@@ -7,7 +7,8 @@
 //    because they are the same source expressions (-ffp-contract=off).  A helper must keep its operation order and association.
 //  * CE tail    loss = CE(gate(s, d), y) + beta*CE(s, y) [+ reg] (batch means) and both logit gradients: one thread per row up to
 //    16 classes (ign_loss_kernel), one wave per row above (ign_loss_wide_kernel).  With class weights and / or label smoothing:
-//    ign_loss_w_kernel / ign_loss_w_wide_kernel, the same two layouts behind an entry point of their own.
+//    ign_loss_w_kernel / ign_loss_w_wide_kernel, the same two layouts behind an entry point of their own.  With two labels per
+//    row and a per-row share of the first (mixup / CutMix, run.py --mix): ign_loss_mix_kernel / ign_loss_mix_wide_kernel.
 //  * CRPS       p = softmax(z), F_j = sum_{i<=j} p_i, H_j = [edge_j >= y] (in float64); loss = mean_b sum_j (F_j - H_j)^2; per row
 //    r_j = F_j - H_j, q_i = (2/B) sum_{j>=i} r_j, dz_k = p_k (q_k - sum_i p_i q_i).  InterpGN's tail: CRPS in place of CE above.
 // The tails stay separate kernels: ign_loss_kernel adds the row terms per thread (rows t, t + 256, ...) and then over the threads,
@@ -512,6 +513,237 @@ __global__ void __launch_bounds__(LOSS_WAVES * 64) ign_loss_w_wide_kernel(const 
     if (threadIdx.x == 0) write_loss3(loss3, tot[0], tot[1], k.invD, beta, reg);
 }
 
+// ------------------------------------------------------------------------------------------------ soft-label (mixup / CutMix) CE tail
+// The weighted tail with two labels per row, ya_b and yb_b, and the share lam_b of the first (run.py --mix).  With a_b = lam_b w[ya_b],
+// c_b = (1 - lam_b) w[yb_b], D = sum_b (a_b + c_b), W = sum_n w_n:
+//   CEm        = sum_b [ (1-eps) (a_b (lse_b - z[b,ya_b]) + c_b (lse_b - z[b,yb_b])) + (eps/N) sum_n w_n (lse_b - z[b,n]) ] / D
+//   dCEm/dz_bn = ( (1-eps) (a_b (p_n - [n = ya_b]) + c_b (p_n - [n = yb_b])) + (eps/N) (p_n W - w_n) ) / D
+// lam == 1 everywhere is CEw.  Separate kernels again, so the tails above keep their bits; the gate is the same gate_* expressions
+// in the same order, the two layouts are those of ign_loss_w_kernel / ign_loss_w_wide_kernel, and D and W come from a pre-pass
+// inside the launch (cem_prepass), summed in cew_prepass's order.
+struct CeMRow {
+    int ya, yb;
+    float a, c;                        // lam w[ya], (1 - lam) w[yb]
+};
+__device__ __forceinline__ float cem_lam(float lam) { return fminf(fmaxf(lam, 0.f), 1.f); }   // device data: clamped (NaN -> 0)
+__device__ __forceinline__ CeMRow cem_row(const long long* __restrict__ ya, const long long* __restrict__ yb,
+                                          const float* __restrict__ lam, int b, int N, const float* wl) {
+    CeMRow r;
+    r.ya = cew_label(ya[b], N);
+    r.yb = cew_label(yb[b], N);
+    const float l = cem_lam(lam[b]);
+    r.a = l * wl[r.ya];
+    r.c = (1.f - l) * wl[r.yb];
+    return r;
+}
+__device__ __forceinline__ float cem_grad(const CeW& k, const CeMRow& r, float p, float wn, int n) {
+    return (k.keep * (r.a * (p - (n == r.ya ? 1.f : 0.f)) + r.c * (p - (n == r.yb ? 1.f : 0.f))) + k.smooth * (p * k.W - wn)) * k.invD;
+}
+// one row's loss term before the division by D; nll_a = lse - z_ya, nll_b = lse - z_yb, smo = sum_n w_n (lse - z_n)
+__device__ __forceinline__ float cem_term(const CeW& k, const CeMRow& r, float nll_a, float nll_b, float smo) {
+    return k.keep * (r.a * nll_a + r.c * nll_b) + k.smooth * smo;
+}
+
+// cew_prepass with D = sum_b (a_b + c_b): per thread over its rows t, t + blockDim, ... in ascending order, then over the threads in
+// thread order; W in class order.  `red`: blockDim floats of LDS, free again on return.
+__device__ __forceinline__ CeW cem_prepass(const float* __restrict__ cw, const long long* __restrict__ ya,
+                                           const long long* __restrict__ yb, const float* __restrict__ lam, int B, int N, float eps,
+                                           float* wl, float* red) {
+    __shared__ float dw[2];
+    const int T = (int)blockDim.x;
+    for (int n = threadIdx.x; n < N; n += T) wl[n] = cw ? cw[n] : 1.f;
+    __syncthreads();
+    float part = 0.f;
+    for (int b = threadIdx.x; b < B; b += T) {
+        const CeMRow r = cem_row(ya, yb, lam, b, N, wl);
+        part += r.a + r.c;
+    }
+    red[threadIdx.x] = part;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float D = 0.f, W = 0.f;
+        for (int i = 0; i < min(T, B); ++i) D += red[i];               // threads past the last row hold zeros
+        for (int n = 0; n < N; ++n) W += wl[n];
+        dw[0] = D;
+        dw[1] = W;
+    }
+    __syncthreads();
+    return CeW{1.f - eps, eps / (float)N, dw[1], 1.f / dw[0]};
+}
+
+// N <= 16: ign_loss_kernel's layout (thread <-> rows b, b + 256, ...; the two sums reduced through LDS in thread order)
+__global__ void __launch_bounds__(256) ign_loss_mix_kernel(const float* __restrict__ s, const float* __restrict__ d,
+                                                           const long long* __restrict__ ya, const long long* __restrict__ yb,
+                                                           const float* __restrict__ lam, const float* __restrict__ cw,
+                                                           float* __restrict__ out, float* __restrict__ eta_out,
+                                                           float* __restrict__ loss3, float* __restrict__ gs, float* __restrict__ gd,
+                                                           int B, int N, float beta, float eps, const float* __restrict__ reg) {
+    __shared__ float red[2][256];
+    __shared__ float wl[LOSS_NMAX];
+    const CeW k = cem_prepass(cw, ya, yb, lam, B, N, eps, wl, red[0]);
+    float ce_o = 0.f, ce_s = 0.f;
+    for (int b = threadIdx.x; b < B; b += 256) {
+        float sv[LOSS_NMAX], ov[LOSS_NMAX], q[LOSS_NMAX];
+        const float* sr = s + (long long)b * N;
+        const float* dr = d + (long long)b * N;
+        const CeMRow r = cem_row(ya, yb, lam, b, N, wl);
+        for (int n = 0; n < N; ++n) sv[n] = sr[n];
+        float mx, z, z2;
+        row_stats<0>(sv, N, mx, z, z2, q);
+        const float G = gate_G(z, z2);
+        const float eta = gate_eta(N, G);
+        eta_out[b] = eta;
+        const float lse_s = mx + logf(z);
+        float mo = -INFINITY;
+        for (int n = 0; n < N; ++n) {
+            ov[n] = gate_mix(eta, sv[n], dr[n]);
+            out[(long long)b * N + n] = ov[n];
+            mo = fmaxf(mo, ov[n]);
+        }
+        float zo = 0.f;
+        for (int n = 0; n < N; ++n) zo += expf(ov[n] - mo);
+        const float lse_o = mo + logf(zo);
+        float smo_s = 0.f, smo_o = 0.f;
+        for (int n = 0; n < N; ++n) {
+            smo_s += wl[n] * (lse_s - sv[n]);
+            smo_o += wl[n] * (lse_o - ov[n]);
+        }
+        ce_s += cem_term(k, r, lse_s - sv[r.ya], lse_s - sv[r.yb], smo_s);
+        ce_o += cem_term(k, r, lse_o - ov[r.ya], lse_o - ov[r.yb], smo_o);
+        // gradients: g_out = dCEm(out)/dout ; through the gate ; + beta * dCEm(s)/ds
+        float dot = 0.f;
+        float go[LOSS_NMAX];
+        for (int n = 0; n < N; ++n) {
+            go[n] = cem_grad(k, r, expf(ov[n] - mo) / zo, wl[n], n);
+            dot += go[n] * (sv[n] - dr[n]);
+        }
+        const float c = gate_coef(N, dot);
+        for (int n = 0; n < N; ++n) {
+            const float qn = q[n] / z;
+            gs[(long long)b * N + n] = gate_ds(eta, go[n], c, qn, G) + beta * cem_grad(k, r, qn, wl[n], n);
+            gd[(long long)b * N + n] = gate_dd(eta, go[n]);
+        }
+    }
+    red[0][threadIdx.x] = ce_o;
+    red[1][threadIdx.x] = ce_s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float a = 0.f, b2 = 0.f;
+        for (int i = 0; i < 256; ++i) { a += red[0][i]; b2 += red[1][i]; }
+        write_loss3(loss3, a, b2, k.invD, beta, reg);
+    }
+}
+
+// 16 < N <= IGN_HEAD_NMAX: ign_loss_wide_kernel's layout (one wave per row, lanes over the classes in chunks of 64, row sums by
+// butterfly, the rows' loss terms added in ascending row order)
+__global__ void __launch_bounds__(LOSS_WAVES * 64) ign_loss_mix_wide_kernel(const float* __restrict__ s, const float* __restrict__ d,
+                                                                            const long long* __restrict__ ya,
+                                                                            const long long* __restrict__ yb,
+                                                                            const float* __restrict__ lam,
+                                                                            const float* __restrict__ cw, float* __restrict__ out,
+                                                                            float* __restrict__ eta_out, float* __restrict__ loss3,
+                                                                            float* __restrict__ gs, float* __restrict__ gd, int B,
+                                                                            int N, float beta, float eps,
+                                                                            const float* __restrict__ reg) {
+    __shared__ float ce[2][LOSS_TILE];
+    __shared__ float wl[IGN_HEAD_NMAX];
+    static_assert(LOSS_TILE >= LOSS_WAVES * 64, "cem_prepass borrows one row of `ce` for its per-thread sums");
+    const CeW k = cem_prepass(cw, ya, yb, lam, B, N, eps, wl, ce[0]);
+    float tot[2] = {0.f, 0.f};                         // {CEm(out), CEm(s)} batch sums before / D, meaningful in thread 0
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int base = 0; base < B; base += LOSS_TILE) {
+        const int rows = min(LOSS_TILE, B - base);
+        for (int r = wave; r < rows; r += LOSS_WAVES) {
+            const int b = base + r;
+            const float* sr = s + (long long)b * N;
+            const float* dr = d + (long long)b * N;
+            const CeMRow row = cem_row(ya, yb, lam, b, N, wl);
+            float sv[LOSS_KMAX], dv[LOSS_KMAX], q[LOSS_KMAX], ov[LOSS_KMAX], eo[LOSS_KMAX], wv[LOSS_KMAX];
+            float mx = -INFINITY;
+#pragma unroll
+            for (int kk = 0; kk < LOSS_KMAX; ++kk) {
+                const int n = kk * 64 + lane;
+                sv[kk] = n < N ? sr[n] : -INFINITY;
+                dv[kk] = n < N ? dr[n] : 0.f;
+                wv[kk] = n < N ? wl[n] : 0.f;
+                mx = fmaxf(mx, sv[kk]);
+            }
+            mx = wave_max(mx);
+            float z = 0.f, z2 = 0.f;
+#pragma unroll
+            for (int kk = 0; kk < LOSS_KMAX; ++kk) {
+                q[kk] = kk * 64 + lane < N ? expf(sv[kk] - mx) : 0.f;
+                z += q[kk];
+                z2 += q[kk] * q[kk];
+            }
+            z = wave_sum(z);
+            z2 = wave_sum(z2);
+            const float G = gate_G(z, z2);
+            const float eta = gate_eta(N, G);
+            if (lane == 0) eta_out[b] = eta;
+            float mo = -INFINITY, s_ya = 0.f, o_ya = 0.f, s_yb = 0.f, o_yb = 0.f;
+#pragma unroll
+            for (int kk = 0; kk < LOSS_KMAX; ++kk) {
+                const int n = kk * 64 + lane;
+                ov[kk] = gate_mix(eta, sv[kk], dv[kk]);
+                if (n < N) {
+                    out[(long long)b * N + n] = ov[kk];
+                    mo = fmaxf(mo, ov[kk]);
+                }
+                if (n == row.ya) { s_ya = sv[kk]; o_ya = ov[kk]; }
+                if (n == row.yb) { s_yb = sv[kk]; o_yb = ov[kk]; }
+            }
+            mo = wave_max(mo);
+            s_ya = wave_sum(s_ya);                // exactly one lane holds a label's logits, the others add zeros
+            o_ya = wave_sum(o_ya);
+            s_yb = wave_sum(s_yb);
+            o_yb = wave_sum(o_yb);
+            float zo = 0.f;
+#pragma unroll
+            for (int kk = 0; kk < LOSS_KMAX; ++kk) {
+                eo[kk] = kk * 64 + lane < N ? expf(ov[kk] - mo) : 0.f;
+                zo += eo[kk];
+            }
+            zo = wave_sum(zo);
+            const float lse_s = mx + logf(z), lse_o = mo + logf(zo);
+            float smo_s = 0.f, smo_o = 0.f;
+#pragma unroll
+            for (int kk = 0; kk < LOSS_KMAX; ++kk)
+                if (kk * 64 + lane < N) {         // the padding lanes hold -inf logits
+                    smo_s += wv[kk] * (lse_s - sv[kk]);
+                    smo_o += wv[kk] * (lse_o - ov[kk]);
+                }
+            smo_s = wave_sum(smo_s);
+            smo_o = wave_sum(smo_o);
+            // gradients: g_out = dCEm(out)/dout ; through the gate ; + beta * dCEm(s)/ds
+            float dot = 0.f;
+#pragma unroll
+            for (int kk = 0; kk < LOSS_KMAX; ++kk) {
+                const int n = kk * 64 + lane;
+                eo[kk] = cem_grad(k, row, eo[kk] / zo, wv[kk], n);               // go
+                if (n < N) dot += eo[kk] * (sv[kk] - dv[kk]);
+            }
+            dot = wave_sum(dot);
+            const float c = gate_coef(N, dot);
+#pragma unroll
+            for (int kk = 0; kk < LOSS_KMAX; ++kk) {
+                const int n = kk * 64 + lane;
+                if (n < N) {
+                    const float qn = q[kk] / z;
+                    gs[(long long)b * N + n] = gate_ds(eta, eo[kk], c, qn, G) + beta * cem_grad(k, row, qn, wv[kk], n);
+                    gd[(long long)b * N + n] = gate_dd(eta, eo[kk]);
+                }
+            }
+            if (lane == 0) {
+                ce[0][r] = cem_term(k, row, lse_o - o_ya, lse_o - o_yb, smo_o);
+                ce[1][r] = cem_term(k, row, lse_s - s_ya, lse_s - s_yb, smo_s);
+            }
+        }
+        add_in_row_order(ce, rows, tot);
+    }
+    if (threadIdx.x == 0) write_loss3(loss3, tot[0], tot[1], k.invD, beta, reg);
+}
+
 // ------------------------------------------------------------------------------------------------ CRPS tails
 // One block of CRPS_THREADS threads, one thread per row (rows base + threadIdx.x of each tile).  Up to CRPS_NREG classes a
 // row lives in registers (loops fully unrolled, guarded by n < N); wider rows are read from global memory and the gradient
@@ -685,6 +917,29 @@ extern "C" int ign_loss_w_fwd_bwd_reg(const float* sbm, const float* dnn, const 
                            reg);
     }
     return ign_check_launch(wide ? "ign_loss_w_wide_kernel" : "ign_loss_w_kernel");
+}
+
+extern "C" int ign_loss_mix_fwd_bwd_reg(const float* sbm, const float* dnn, const long long* labels, const long long* labels_b,
+                                        const float* lam_b, const float* class_w, const float* reg, float* out, float* eta,
+                                        float* loss3, float* gsbm, float* gdnn, int B, int N, float beta, float label_smoothing,
+                                        void* stream) {
+    if (!sbm || !dnn || !labels || !labels_b || !lam_b || !out || !eta || !loss3 || !gsbm || !gdnn || B <= 0 || N < 2) {
+        ign_set_error("ign_loss_mix_fwd_bwd_reg: null pointer or bad dimension (B=%d N=%d, N <= %d)", B, N, IGN_HEAD_NMAX);
+        return IGN_E_ARG;
+    }
+    if (!(label_smoothing >= 0.f && label_smoothing < 1.f)) {
+        ign_set_error("ign_loss_mix_fwd_bwd_reg: label_smoothing=%g outside [0, 1)", (double)label_smoothing);
+        return IGN_E_ARG;
+    }
+    if (N > IGN_HEAD_NMAX) { ign_set_error("ign_loss_mix_fwd_bwd_reg: N=%d classes > %d", N, IGN_HEAD_NMAX); return IGN_E_UNSUP; }
+    const bool wide = N > LOSS_NMAX;
+    {
+        IgnScopedTimer tm("loss_mix", (hipStream_t)stream);
+        hipLaunchKernelGGL(wide ? ign_loss_mix_wide_kernel : ign_loss_mix_kernel, dim3(1), dim3(wide ? LOSS_WAVES * 64 : 256), 0,
+                           (hipStream_t)stream, sbm, dnn, labels, labels_b, lam_b, class_w, out, eta, loss3, gsbm, gdnn, B, N, beta,
+                           label_smoothing, reg);
+    }
+    return ign_check_launch(wide ? "ign_loss_mix_wide_kernel" : "ign_loss_mix_kernel");
 }
 
 static bool crps_dims_ok(const char* name, int B, int N) {

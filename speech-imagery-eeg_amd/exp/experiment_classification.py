@@ -88,6 +88,7 @@ class Experiment(object):
         self._get_params_from_data()
         self._resolve_loss_options()
         self._resolve_augment()
+        self._resolve_mix()
         # host -> device double buffering (and, for raw CHISCO shards, the on-GPU standardise + transpose)
         self.train_loader, self.val_loader, self.test_loader = (self._prefetch(l) for l in
                                                                 (self.train_loader, self.val_loader, self.test_loader))
@@ -184,6 +185,46 @@ class Experiment(object):
         lengths = padding_mask.sum(1).to(torch.int32)
         return ign_ops.augment(batch_x.contiguous(), step_seed(self._augment_base, self.rank, train_step), lengths=lengths,
                                **self._augment_spec._asdict())
+
+    def _resolve_mix(self):
+        """--mix -> self._mix_spec (None when off: the training loops then do nothing extra -- no draw, no launch, no further static
+        input, today's loss entry points).  The draws share --augment's per-step seed rule (utils.augment.step_seed) and base seed.
+        The regression task refuses the flag: its CRPS tails take one real-valued target per row."""
+        from utils.mix import parse_mix
+        spec = parse_mix(getattr(self.args, 'mix', None))
+        self._mix_spec = spec if spec.active else None
+        if self._mix_spec is None:
+            return
+        if getattr(self.args, 'task_name', 'classification') == 'regression':
+            raise ValueError("--mix with --task_name regression: mixup / CutMix mix class labels through the cross-entropy tails; "
+                             "the CRPS tails have no soft-label form")
+        seed = int(getattr(self.args, 'seed', -1))
+        self._mix_base = seed if seed >= 0 else int(torch.initial_seed())
+        if self.rank == 0:
+            print(f"mix: {', '.join(f'{k}={v:g}' for k, v in spec._asdict().items() if v and (k != 'prob' or v != 1.0))}")
+
+    def _mix(self, batch_x, label, padding_mask, train_step):
+        """The training batch of step `train_step` mixed on the device in one launch (ops.mix) -> (batch, (label_b, lam)): the soft
+        labels _train_loss takes after `label`; (batch_x, ()) when --mix is off.  The draws are made on the host
+        (utils.mix.mix_draws under step_seed(base, rank, step): ranks differ, the eager and captured loops agree, no torch generator
+        is consumed) and reach the device from pinned memory without blocking.  Sample b is paired with (b + roll) mod B -- the
+        loader has shuffled already -- and mixed inside its own length, the keep-mask's row sum; only CutMix, whose span depends on
+        the length, reads the lengths back to the host (one small synchronising copy per step; mixup alone draws as for full
+        lengths and never waits for the device).  Training only: validation, test, saliency, the k-means initialisation and
+        the projection never call it."""
+        if self._mix_spec is None:
+            return batch_x, ()
+        from utils.augment import step_seed
+        from utils.mix import mix_draws
+        B, T = batch_x.shape[0], batch_x.shape[1]
+        lengths = padding_mask.sum(1).to(torch.int32)
+        host_lengths = lengths.cpu().numpy() if self._mix_spec.cutmix > 0.0 else T
+        roll, lam, span = mix_draws(step_seed(self._mix_base, self.rank, train_step), B, host_lengths, self._mix_spec)
+        put = (lambda a: torch.from_numpy(a).pin_memory().to(self.device, non_blocking=True)) if self.device.type == 'cuda' \
+            else torch.from_numpy
+        lam = put(lam)
+        span = put(span) if self._mix_spec.cutmix > 0.0 else None
+        return ign_ops.mix(batch_x.contiguous(), lam, roll, span=span, lengths=lengths), (label.roll(-roll), lam)
 
     def _load_data(self):
         self.train_data, self.train_loader = data_provider(self.args, flag="train")
@@ -284,9 +325,10 @@ class Experiment(object):
             train_step += 1
             batch_x, label, padding_mask = self._to_device(batch_x, label, padding_mask)
             batch_x = self._augment(batch_x, padding_mask, train_step)
+            batch_x, soft = self._mix(batch_x, label, padding_mask, train_step)
             with torch.autocast(device_type=self.device.type, dtype=torch.bfloat16, enabled=amp):
                 logits, info = self._forward(batch_x, padding_mask)
-                loss = self._train_loss(logits, info, label, compute_beta(epoch, a.train_epochs, a.beta_schedule), amp)
+                loss = self._train_loss(logits, info, label, compute_beta(epoch, a.train_epochs, a.beta_schedule), amp, *soft)
             if a.gradient_accumulation_steps > 1:
                 loss = loss / a.gradient_accumulation_steps
             ign_ops.backward(loss)                 # = loss.backward() (a cached unit root gradient on the GPU)
@@ -322,11 +364,24 @@ class Experiment(object):
         else:
             self.optimizer.zero_grad()
 
-    def _train_loss(self, logits, info, label, beta, amp):
+    def _train_loss(self, logits, info, label, beta, amp, label_b=None, lam=None):
         """The training loss of one step (IGN/exp/experiment_classification.py:319-329); `beta` weighs InterpGN's SBM term.
-        Every cross-entropy of it takes the run's class weights and label smoothing (_resolve_loss_options)."""
+        Every cross-entropy of it takes the run's class weights and label smoothing (_resolve_loss_options), and under --mix the
+        soft labels (label, label_b, lam) of _mix: the fused tail's soft-label entry point for InterpGN, utils.mix.mix_cross_entropy
+        where the criterion is torch's."""
         a = self.args
         w, eps = self.class_weight, self.label_smoothing
+        if lam is not None:
+            if a.model == 'InterpGN' and logits.is_cuda and not amp:
+                return ign_ops.ign_loss(info.shapelet_preds, info.dnn_preds, label, beta, reg=info.loss, class_weight=w,
+                                        label_smoothing=eps, y_b=label_b, lam=lam)[0]
+            from utils.mix import mix_cross_entropy
+            loss = mix_cross_entropy(logits, label, label_b, lam, w, eps)
+            if a.model != 'DNN':
+                loss = loss + info.loss.mean()
+            if a.model == 'InterpGN':
+                loss = loss + beta * mix_cross_entropy(info.shapelet_preds, label, label_b, lam, w, eps)
+            return loss
         if a.model == 'InterpGN' and logits.is_cuda and not amp:
             # CE(mixture) + info.loss.mean() + beta*CE(sbm) and both logit gradients in one launch (ops.ign_loss)
             # instead of ~40 softmax / nll / mean kernels between the forward and the backward pass
@@ -378,9 +433,9 @@ class Experiment(object):
         # of ITS gradients.
         K = a.gradient_accumulation_steps
 
-        def step_fn(batch_x, label, padding_mask, close=True):
+        def step_fn(batch_x, label, padding_mask, *soft, close=True):         # soft: (label_b, lam) under --mix, else nothing
             logits, info = self._forward(batch_x, padding_mask)
-            loss = self._train_loss(logits, info, label, beta, False)
+            loss = self._train_loss(logits, info, label, beta, False, *soft)
             if K > 1:
                 loss = loss / K
             ign_ops.backward(loss)
@@ -393,8 +448,8 @@ class Experiment(object):
                 self.bucket.clear()
             return loss.detach()
 
-        def micro_fn(batch_x, label, padding_mask):
-            return step_fn(batch_x, label, padding_mask, close=False)
+        def micro_fn(batch_x, label, padding_mask, *soft):
+            return step_fn(batch_x, label, padding_mask, *soft, close=False)
 
         if K > 1 and not getattr(self, '_graph_acc_primed', False):
             self.bucket.clear()                    # every micro-step adds: the first cycle starts from zeros as well
@@ -404,9 +459,11 @@ class Experiment(object):
             train_step += 1
             batch_x, label, padding_mask = self._to_device(batch_x, label, padding_mask)
             batch_x = self._augment(batch_x, padding_mask, train_step)      # outside the graph: its static input takes this batch
+            batch_x, soft = self._mix(batch_x, label, padding_mask, train_step)     # likewise; label_b / lam are static inputs too
+            inputs = (batch_x, label, padding_mask, *soft)
             kind, fn = ('close', step_fn) if train_step % K == 0 else ('micro', micro_fn)
             if batch_x.shape[0] != a.batch_size:                  # ragged last batch: eager
-                losses.append(fn(batch_x, label, padding_mask).clone())
+                losses.append(fn(*inputs).clone())
                 continue
             if graphed is None or graphed[0] != key:
                 graphed = self._graphed = (key, {})
@@ -414,10 +471,10 @@ class Experiment(object):
                 # beta and lr are kernel ARGUMENTS: a new value needs a new capture.  This batch runs eagerly (which also performs
                 # every first-call initialisation outside the capture); the capture that follows records the launch sequence
                 # without executing it, so the parameter trajectory is exactly the eager one
-                losses.append(fn(batch_x, label, padding_mask).clone())
-                graphed[1][kind] = GraphedTrainStep(fn, (batch_x, label, padding_mask), warmup=0)
+                losses.append(fn(*inputs).clone())
+                graphed[1][kind] = GraphedTrainStep(fn, inputs, warmup=0)
                 continue
-            losses.append(graphed[1][kind](batch_x, label, padding_mask).clone())
+            losses.append(graphed[1][kind](*inputs).clone())
         return losses, train_step
 
     def train(self):

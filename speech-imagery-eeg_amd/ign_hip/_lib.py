@@ -163,7 +163,9 @@ SIGNATURES = {
     "ign_shapelet_project_step": (ci, [vp, vp, vp, ci, ci, ci, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]),
     "ign_shapelet_project_step_bank": (ci, [vp, vp, vp, ci, ci, vp, ci, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp]),
     "ign_loss_w_fwd_bwd_reg": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, cf, cf, vp]),
+    "ign_loss_mix_fwd_bwd_reg": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, cf, cf, vp]),
     "ign_augment_btc": (ci, [vp, vp, vp, ci, ci, ci, ctypes.c_ulonglong, cf, cf, cf, ctypes.c_uint, cf, vp]),
+    "ign_mix_btc": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
     "ign_eeg_preprocess_ws_bytes": (sz, [ci, ci, ci, ci, ci, ci, ci]),
     "ign_eeg_preprocess_nct_to_btc": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, vp]),
     "ign_eeg_filterbank_ws_bytes": (sz, [ci, ci, ci, ci, ci, ci, ci, ci]),

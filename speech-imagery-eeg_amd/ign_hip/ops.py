@@ -258,6 +258,38 @@ def augment(x, seed, *, lengths=None, shift=0.0, scale=0.0, noise=0.0, channel_d
     return out
 
 
+def mix(x, lam, roll, span=None, lengths=None):
+    """Mixup / CutMix of a contiguous fp32 (B,T,C) batch on the GPU -> a new tensor (ign_mix_btc; the rule is restated in
+    utils/mix.py:mix_reference): sample b is blended with its partner p = (b + roll) mod B as lam[b] * x[b] + (1 - lam[b]) * x[p],
+    replaced by the partner inside its span (start, m) = span[b], and left as it is from lengths[b] on and where lam[b] == 1.
+    `lam`: float32 (B,), `span`: int32 (B, 2) or None (no spans), `lengths`: int32 (B,) or None (every sample has T steps), all on
+    the GPU; `roll`: a host integer in [0, B).  The draws come from utils.mix.mix_draws.  Refused for an input that requires a
+    gradient (a training batch never does).  Every argument but `roll` is device data, so the call may be captured."""
+    name = "mix"
+    _need_gpu(name, x, lam)
+    if x.dim() != 3 or not x.is_contiguous():
+        raise _lib.IgnError(f"{name}: expected a contiguous (B,T,C) tensor, got shape {tuple(x.shape)} strides {x.stride()}")
+    if x.requires_grad:
+        raise _lib.IgnError(f"{name}: the input requires a gradient; mixing acts on data (there is no backward pass)")
+    B, T, C = x.shape
+    if tuple(lam.shape) != (B,):
+        raise _lib.IgnError(f"{name}: lam must be a float32 tensor of shape ({B},), got {tuple(lam.shape)}")
+    if span is not None and not (torch.is_tensor(span) and span.is_cuda and span.dtype == torch.int32 and tuple(span.shape) == (B, 2)):
+        what = f"{span.dtype} {tuple(span.shape)} on {span.device}" if torch.is_tensor(span) else type(span).__name__
+        raise _lib.IgnError(f"{name}: span must be an int32 tensor of shape ({B}, 2) on the GPU, got {what}")
+    roll = int(roll)
+    if not 0 <= roll < max(B, 1):
+        raise _lib.IgnError(f"{name}: roll = {roll} outside [0, {B})")
+    out = torch.empty_like(x)
+    if B == 0:
+        return out
+    if lengths is not None:
+        lengths = _lengths(name, lengths, B)
+    _lib.check(_lib.lib().ign_mix_btc(_ptr(x), _ptr(out), _ptr(lengths), _ptr(lam.contiguous()),
+                                      _ptr(None if span is None else span.contiguous()), roll, B, T, C, _stream()), "ign_mix_btc")
+    return out
+
+
 def _tables(G):
     return ctypes.c_void_p * G, ctypes.c_int * G
 
@@ -1604,10 +1636,11 @@ def _loss_tail(entry, sbm, dnn, crit, beta, reg, more=()):
     """The one launcher of the gated loss tails -> (loss3, out, eta, gsd): loss3[2] = criterion(gate(sbm, dnn)) + beta*criterion(sbm)
     [+ reg], gsd (2, B, N) = its gradient w.r.t. (sbm, dnn) in one buffer.  `entry`: "ign_loss" (cross-entropy, crit = (labels,)),
     "ign_loss+w" (the weighted / label-smoothed cross-entropy, crit = (labels, class weights or None), more = (label_smoothing,);
-    reports as ign_loss) or "ign_crps_loss" (CRPS, crit = (target, edges)); `crit` sits between `dnn` and `reg` in the entry
+    reports as ign_loss), "ign_loss+mix" (the same with soft labels, crit = (labels, second labels, lam, class weights or None),
+    more = (label_smoothing,); reports as ign_loss) or "ign_crps_loss" (CRPS, crit = (target, edges)); `crit` sits between `dnn` and `reg` in the entry
     point's signature, the numbers `more` between `beta` and the stream."""
     symbol = {"ign_loss": "ign_loss_fwd_bwd_reg", "ign_loss+w": "ign_loss_w_fwd_bwd_reg",
-              "ign_crps_loss": "ign_loss_crps_fwd_bwd_reg"}[entry]
+              "ign_loss+mix": "ign_loss_mix_fwd_bwd_reg", "ign_crps_loss": "ign_loss_crps_fwd_bwd_reg"}[entry]
     entry = entry.partition("+")[0]
     B, N = sbm.shape
     out = torch.empty_like(sbm)
@@ -1654,12 +1687,18 @@ def _ce_inputs(name, logits, y):
 
 class IgnLossFn(torch.autograd.Function):
     """CE(gate(sbm, dnn), y) + beta * CE(sbm, y) [+ reg] with both logit gradients from one launch (_loss_tail).  The optional
-    `opts` = (class_weight, label_smoothing) after `reg` select the weighted / label-smoothed tail; they carry no gradient."""
+    `opts` = (class_weight, label_smoothing) after `reg` select the weighted / label-smoothed tail, (class_weight, label_smoothing,
+    y_b, lam) the soft-label tail of mixup / CutMix; they carry no gradient."""
 
     @staticmethod
     def forward(ctx, sbm, dnn, y, beta, reg, *opts):
         ctx.n_opts = len(opts)
-        class_weight, label_smoothing = opts or (None, 0.0)
+        class_weight, label_smoothing, *soft = opts or (None, 0.0)
+        if soft:
+            y_b, lam = soft
+            return _tail_forward(ctx, "ign_loss+mix", sbm, dnn,
+                                 lambda name, logits, y: _ce_inputs(name, logits, y) + (y_b.contiguous().long(), lam, class_weight),
+                                 (y,), beta, reg, (float(label_smoothing),))
         if class_weight is None and label_smoothing == 0.0:
             return _tail_forward(ctx, "ign_loss", sbm, dnn, _ce_inputs, (y,), beta, reg)
         return _tail_forward(ctx, "ign_loss+w", sbm, dnn, lambda name, logits, y: _ce_inputs(name, logits, y) + (class_weight,),
@@ -1685,13 +1724,37 @@ def _check_ce_options(name, logits, class_weight, label_smoothing):
         raise _lib.IgnError(f"{name}: class_weight must be a float32 ({N},) tensor on {logits.device}, got {what}")
 
 
-def ign_loss(sbm_out, dnn_out, y, beta=1.0, reg=None, class_weight=None, label_smoothing=0.0):
+def _check_soft_labels(name, logits, y_b, lam):
+    """The host's refusals of ign_loss's soft labels: y_b and lam come together, one per row, lam float32 on the logits' device.
+    The VALUES of lam (in [0, 1]) are the caller's (utils.mix.mix_draws); the kernel clamps them."""
+    if y_b is None or lam is None:
+        raise _lib.IgnError(f"{name}: y_b and lam come together (the second label of every row and the share of the first)")
+    B = logits.shape[0]
+    if not (torch.is_tensor(y_b) and not y_b.dtype.is_floating_point and y_b.numel() == B and y_b.device == logits.device):
+        what = f"{y_b.dtype} {tuple(y_b.shape)} on {y_b.device}" if torch.is_tensor(y_b) else type(y_b).__name__
+        raise _lib.IgnError(f"{name}: y_b must hold {B} integer labels on {logits.device}, got {what}")
+    if not (torch.is_tensor(lam) and lam.dtype == torch.float32 and tuple(lam.shape) == (B,) and lam.device == logits.device):
+        what = f"{lam.dtype} {tuple(lam.shape)} on {lam.device}" if torch.is_tensor(lam) else type(lam).__name__
+        raise _lib.IgnError(f"{name}: lam must be a float32 ({B},) tensor on {logits.device}, got {what}")
+    if lam.requires_grad:
+        raise _lib.IgnError(f"{name}: lam requires a gradient; the tail has none for it")
+
+
+def ign_loss(sbm_out, dnn_out, y, beta=1.0, reg=None, class_weight=None, label_smoothing=0.0, y_b=None, lam=None):
     """-> (CE(mix, y) + beta*CE(sbm, y) [+ reg], mix, eta); mix / eta are reporting outputs (no gradient flows through them).
     `reg`: the model's regulariser value (ModelInfo.loss, one element) -- added on the device inside the same launch, i.e. the
     whole training loss of IGN/exp/experiment_classification.py:325-329 (its gradient passes straight through).
     `class_weight` (float32 (N,) on the logits' device, positive and finite) / `label_smoothing` (in [0, 1)): both CE terms become
     F.cross_entropy(., y, weight=class_weight, label_smoothing=label_smoothing), still one launch (ign_loss_w_fwd_bwd_reg).  Without
-    them the call is today's node on today's entry point, bit for bit."""
+    them the call is today's node on today's entry point, bit for bit.
+    `y_b` (integer labels (B,)) / `lam` (float32 (B,) in [0, 1], no gradient): soft labels of mixup / CutMix -- every row counts as
+    class y with the share lam and as class y_b with 1 - lam in both criteria (ign_loss_mix_fwd_bwd_reg, one launch; the formula is
+    utils/mix.py's CEm); lam == 1 is the call without them."""
+    if y_b is not None or lam is not None:
+        _check_ce_options("ign_loss", sbm_out, class_weight, label_smoothing)
+        _check_soft_labels("ign_loss", sbm_out, y_b, lam)
+        return IgnLossFn.apply(sbm_out.float(), dnn_out.float(), y, beta, reg, class_weight.contiguous() if class_weight is not None
+                               else None, float(label_smoothing), y_b.reshape(-1), lam.contiguous())
     if class_weight is None and label_smoothing == 0.0:
         return IgnLossFn.apply(sbm_out.float(), dnn_out.float(), y, beta, reg)
     _check_ce_options("ign_loss", sbm_out, class_weight, label_smoothing)

@@ -20,6 +20,9 @@ Differences, all repairs of fork defects listed in SURVEY section 0:
   * ``--augment shift=0.1,scale=0.1,noise=0.05,chan_drop=0.1,time_mask=0.1`` (any subset) augments every TRAINING batch on the
     device in one fused launch: circular shift, per-channel gain, Gaussian noise, electrode dropout, one masked time span, each
     inside the sample's own length; validation / test never augment; the default ``none`` changes nothing;
+  * ``--mix mixup=0.4[,cutmix=1][,prob=0.5]`` mixes every TRAINING sample with a partner of its batch on the device in one launch
+    (mixup: a Beta(A, A) blend; cutmix: a time span of the partner) and trains on the soft labels (InterpGN: still one fused loss
+    launch, also under ``--hipgraph``); classification only; validation / test never mix; the default ``none`` changes nothing;
   * ``--eeg_preprocess band=8:30,decimate=2,fit`` (``--data EEG`` / ``EEG3``; any subset of sfreq=F, band=LO:HI, decimate=Q, taps=M,
     edge=reflect|zero, fit) filters the raw CHISCO shards with a zero-phase FIR band-pass, decimates them and, with ``fit``, crops /
     zero-pads them to ``--target_channels`` x ``--target_timepoints`` in front of the standardisation -- on the device in the
@@ -138,6 +141,12 @@ def build_parser():
                         "shift=R (circular shift by up to R * length), scale=R (per-channel gain in 1 +- R; the SBM's instance norm "
                         "cancels it, the DNN experts see it), noise=SIGMA (Gaussian), chan_drop=P (electrodes zeroed, no rescaling), "
                         "time_mask=R (one zeroed span of up to R * length per sample); rates in [0, 1).  Reproducible from --seed")
+    p.add_argument("--mix", type=str, default='none',
+                   help="mixup / CutMix of the training batch on the device, one launch per step, with soft labels through the loss: "
+                        "none, or mixup=A[,cutmix=A][,prob=P].  A > 0 is the Beta(A, A) parameter of the mixing share; cutmix "
+                        "replaces one time span of a sample by its partner's instead of blending; with both keys each mixed sample "
+                        "takes one of the two with probability 1/2; prob in (0, 1] is the chance that a sample is mixed at all.  "
+                        "Partners are a random roll of the batch.  Classification only.  Reproducible from --seed")
     p.add_argument("--eeg_preprocess", type=str, default='none',
                    help="--data EEG / EEG3: preprocessing of the raw shards in front of the standardisation, on the device: none, or a "
                         "comma list of sfreq=F (Hz, default 500), band=LO:HI (Hz, either side may be empty), decimate=Q, taps=M "
@@ -202,6 +211,10 @@ def check_args(args):
     check_loss_options(args, _num_class_from_flags(args))
     from utils.augment import parse_augment
     parse_augment(getattr(args, 'augment', None))
+    from utils.mix import parse_mix
+    if parse_mix(getattr(args, 'mix', None)).active and getattr(args, 'task_name', 'classification') == 'regression':
+        raise ValueError("--mix with --task_name regression: mixup / CutMix mix class labels through the cross-entropy tails; the "
+                         "CRPS tails have no soft-label form")
     from utils.eeg_filter import parse_eeg_preprocess
     if parse_eeg_preprocess(getattr(args, 'eeg_preprocess', None)).active and getattr(args, 'data', None) not in ('EEG', 'EEG3'):
         raise ValueError(f"--eeg_preprocess filters the raw CHISCO shards (--data EEG / EEG3), not --data {args.data}")
