@@ -111,6 +111,39 @@ size_t ign_eeg_filterbank_ws_bytes(int B, int Cin, int Tin, int M, int nb, int q
 int ign_eeg_filterbank_nct_to_btc(const float* x_nct, const float* taps, const float* quad, float* out_btc, float* ws, int B, int Cin,
                                   int Tin, int M, int nb, int q, int edge, int Cout, int Tout, float eps, void* stream);
 
+/* Spatial filter stage in front of all of the above (csrc/ign_eeg_spatial.hip; run.py --eeg_spatial; ops.eeg_spatial / ops.eeg_gram;
+ * numpy restatement utils/eeg_spatial.py:spatial_numpy / gram_numpy): one (Cs,Cin) matrix per group of samples applied across the
+ * electrodes of the raw batch -- a common average reference, a montage / unmixing matrix computed offline, the per-subject
+ * whitening of Euclidean alignment (He & Wu 2020).  x (B,Cin,T) fp32 raw, w (G,Cs,Cin) fp32, gid (B) int32 or NULL (group 0),
+ * out (B,Cs,T) in the input's layout, so ign_standardise_nct_to_btc or the filter bank run on it unchanged.  With g = gid[b]:
+ *   p[c] = x[b,c,0];  xc[c,t] = x[b,c,t] - p[c];
+ *   a[s,t] = fmaf chain over c = 0..Cin-1 ascending of w[g,s,c] * xc[c,t], from 0;  P[s] = the same chain of w[g,s,c] * p[c];
+ *   out[b,s,t] = a[s,t] + P[s]
+ * The pivot keeps the recording's offset (1e4 uV over tens of uV of signal) out of the chain's partial sums: it enters once per
+ * row, as a constant that the standardisation removes.  The chain runs on v_mfma_f32_32x32x2_f32 (exact fp32 on gfx950, k in
+ * ascending order; Cin is padded with zeros, which leaves the bits alone).  A gid outside [0,G) writes zeros for that sample and
+ * reads nothing out of bounds.  No atomics, fixed order: two calls give the same bits, and sample b's output does not depend on B or
+ * on its position in the batch.  Nothing beyond Cs, T and Cin is read or written.
+ * IGN_E_ARG: null x / w / out, non-positive dimension.  IGN_E_TOOBIG: B > 65535, Cin or Cs > IGN_EEG_SPATIAL_MAX_CHANNELS,
+ * G > IGN_EEG_SPATIAL_MAX_GROUPS.  Nothing is launched on an error.                                                             */
+#define IGN_EEG_SPATIAL_MAX_CHANNELS 512
+#define IGN_EEG_SPATIAL_MAX_GROUPS   64
+int ign_eeg_spatial_nct(const float* x_nct, const float* w_gsc, const int* gid, float* out_nst, int B, int Cin, int T, int Cs, int G,
+                        void* stream);
+
+/* Per-group Gram matrix of a (B,C,T) fp32 batch (the spatial stage's own output while an alignment is fitted):
+ *   xc = x - x[..,:1];  m[c] = (sum_t xc[c,t]) / T;  z = xc - m
+ *   gram[g,i,j] = sum over b with gid[b] == g, ascending, of sum_t z[b,i,t] * z[b,j,t];   count[g] = number of such b
+ * Every element of gram (G,C,C) and count (G) is OVERWRITTEN (zeros for an empty group; a gid outside [0,G) belongs to no group);
+ * the host accumulates batches in float64.  Same matrix cores; only the upper triangle of 64 x 64 tiles is computed, per sample,
+ * into ws, and summed in ascending b with element (j,i) read from (i,j): gram[g] is symmetric bit for bit.  No atomics.
+ * ws: ign_eeg_gram_ws_bytes() bytes (B*C + B*C*C floats; 0 for arguments the launcher refuses).
+ * IGN_E_ARG: null x / gram / count / ws, non-positive dimension.  IGN_E_TOOBIG: B > 65535, C > IGN_EEG_SPATIAL_MAX_CHANNELS,
+ * G > IGN_EEG_SPATIAL_MAX_GROUPS.  Nothing is launched on an error.                                                             */
+size_t ign_eeg_gram_ws_bytes(int B, int C, int T, int G);
+int ign_eeg_gram_nct(const float* x_nct, const int* gid, float* gram_gcc, int* count_g, float* ws, int B, int C, int T, int G,
+                     void* stream);
+
 /* Shapelet transform of ONE length group: sliding-window distance + gate, never materialising (B,Tw,K,C,L).
  * Replaces IGN/model/Shapelet.py:60-84 (GATE_RBF) / :96-111 (GATE_LTS).   Tw = (T-L)/stride + 1.
  *   xn_bct   (B,C,T)    normalised input

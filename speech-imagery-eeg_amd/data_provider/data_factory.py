@@ -12,7 +12,7 @@ from torch.utils.data import DataLoader, Sampler
 import functools
 
 from data_provider.data_loader import Monashloader, UEAloader
-from data_provider.eeg_npy import EEGNpyDataset, EEGNpyDataset3Class, collate_raw
+from data_provider.eeg_npy import EEGNpyDataset, EEGNpyDataset3Class, collate_raw, collate_raw_group
 from data_provider.synthetic import SyntheticEEG
 from data_provider.uea import collate_fn, collate_subsampled
 
@@ -66,6 +66,10 @@ def data_provider(args, flag, bin_edges=None):
         pre = parse_eeg_preprocess(getattr(args, 'eeg_preprocess', None))
         extra = dict(preprocess=pre, target_channels=getattr(args, 'target_channels', None),
                      target_timepoints=getattr(args, 'target_timepoints', None)) if pre.active else {}
+        from utils.eeg_spatial import parse_eeg_spatial
+        spatial = parse_eeg_spatial(getattr(args, 'eeg_spatial', None))
+        if spatial.active:                                              # the default reads nothing and passes nothing on
+            extra['spatial'] = spatial
         data_set = Data(root_path=args.root_path, flag=flag, test_size=getattr(args, 'test_size', 0.2),
                         val_size=getattr(args, 'val_size', 0.1), raw=raw, **extra)
     else:
@@ -77,6 +81,7 @@ def data_provider(args, flag, bin_edges=None):
         sampler = RankShardSampler(len(data_set), dist.get_rank(), dist.get_world_size(), shuffle,
                                    seed=max(0, getattr(args, 'seed', 0)))
     raw = bool(getattr(data_set, 'raw', False))
+    stage = getattr(data_set, 'spatial', None)                          # --eeg_spatial: the raw batch carries its group ids
     if args.data == 'SYNTH' and args.num_workers == 0:
         # samples are rows of one in-memory tensor: a batch is one multi-threaded gather into a pinned buffer
         from data_provider.device_prefetch import TensorBatchLoader
@@ -84,10 +89,13 @@ def data_provider(args, flag, bin_edges=None):
                                            pin_memory=torch.cuda.is_available())
     loader = DataLoader(data_set, batch_size=args.batch_size, shuffle=(shuffle and sampler is None), sampler=sampler,
                         num_workers=args.num_workers, drop_last=False, pin_memory=torch.cuda.is_available(),
-                        collate_fn=collate_raw if raw else (lambda b: collate_fn(b, max_len=max_len)))
+                        collate_fn=(collate_raw if stage is None else collate_raw_group) if raw
+                        else (lambda b: collate_fn(b, max_len=max_len)))
     loader.device_transform = 'standardise_raw' if raw else None
     if raw and getattr(data_set, 'pre', None) is not None:          # --eeg_preprocess: the resolved spec travels with the loader
         loader.device_transform, loader.eeg_preprocess = 'eeg_preprocess', data_set.pre
+    if stage is not None:
+        loader.eeg_spatial = stage
     return data_set, loader
 
 
@@ -95,7 +103,7 @@ def ordered_loader(loader):
     """An unshuffled, un-sharded loader over the data set of `loader` (a DataLoader, a TensorBatchLoader, or a DevicePrefetcher
     around either): batch i holds the data set's items i*batch_size ..., on every rank, so a sample's ordinal in the stream is
     its data set index -- what a pass that reports sample indices needs (utils/shapelet_project.py).  Same batch size, collate_fn
-    and device_transform / eeg_preprocess attributes; no sampler, drop_last=False.  A DataLoader draws its per-iteration seed
+    and device_transform / eeg_preprocess / eeg_spatial attributes; no sampler, drop_last=False.  A DataLoader draws its per-iteration seed
     from a generator of its own, so iterating the result leaves torch's global RNG stream where it was."""
     from data_provider.device_prefetch import DevicePrefetcher, TensorBatchLoader
     if isinstance(loader, DevicePrefetcher):
@@ -107,7 +115,7 @@ def ordered_loader(loader):
                          drop_last=False, pin_memory=loader.pin_memory, collate_fn=loader.collate_fn, generator=torch.Generator())
     else:
         raise TypeError(f"ordered_loader: expected a DataLoader, TensorBatchLoader or DevicePrefetcher, got {type(loader).__name__}")
-    for attr in ('device_transform', 'eeg_preprocess'):
+    for attr in ('device_transform', 'eeg_preprocess', 'eeg_spatial'):
         if hasattr(loader, attr):
             setattr(out, attr, getattr(loader, attr))
     return out

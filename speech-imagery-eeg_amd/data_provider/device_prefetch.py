@@ -36,6 +36,19 @@ def preprocess_raw_batch(pre, device):
     return transform
 
 
+def spatial_raw_batch(W, inner):
+    """transform for raw loaders under --eeg_spatial: `W` (G,Cs,Cin) float32 on the device, `inner` the transform that would run
+    without the stage (standardise_raw_batch, or preprocess_raw_batch's).  (X[B,Cin,T], y, gid[B] int32) -> inner on
+    (W[gid[b]] . X[b] (B,Cs,T), y, None): one more launch on the prefetch stream, in front of the others."""
+    from ign_hip import ops
+    one_group = W.shape[0] == 1
+
+    def transform(batch):
+        x, y, gid = batch
+        return inner((ops.eeg_spatial(x.float(), W, None if one_group else gid), y, None))
+    return transform
+
+
 class DevicePrefetcher:
     def __init__(self, loader, device, transform=None, depth=2):
         self.loader, self.device, self.transform, self.depth = loader, torch.device(device), transform, max(1, depth)

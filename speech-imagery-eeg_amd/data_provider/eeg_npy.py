@@ -70,7 +70,7 @@ class EEGNpyDataset(Dataset):
     num_label_classes = 39
 
     def __init__(self, root_path, flag='train', label_map=None, test_size=0.2, val_size=0.1, mmap=True, raw=False,
-                 preprocess=None, target_channels=None, target_timepoints=None, **_):
+                 preprocess=None, target_channels=None, target_timepoints=None, spatial=None, **_):
         self.raw = bool(raw)      # True: items are RAW (C,T) recordings; the batch is standardised on the GPU instead
         xp, yp = os.path.join(root_path, "X.npy"), os.path.join(root_path, "y.npy")
         if not (os.path.exists(xp) and os.path.exists(yp)):
@@ -87,6 +87,9 @@ class EEGNpyDataset(Dataset):
         self.X, self.y, self.idx = X, y, idx
         self.enc_in, self.seq_len = int(X.shape[1]), int(X.shape[2])
         self.num_classes = int(y.max()) + 1 if label_map is None else len(set(label_map.values()))
+        self.spatial = None       # --eeg_spatial: one matrix per group across the electrodes, in front of everything (utils/eeg_spatial.py)
+        if spatial is not None:
+            self._init_spatial(spatial, root_path, len(y), notice=print if flag == 'train' else None)
         self.pre = None           # --eeg_preprocess: filter / decimate / fit in front of the standardisation (utils/eeg_filter.py)
         if preprocess is not None:
             from utils.eeg_filter import parse_eeg_preprocess, resolve
@@ -98,15 +101,53 @@ class EEGNpyDataset(Dataset):
                 # a bank has nb * Cout channels, band-major; one band is the bank of one
                 self.enc_in, self.seq_len = self.pre.channels, self.pre.Tout
 
+    def _init_spatial(self, spatial, root_path, n, notice):
+        """--eeg_spatial: compose W0, and -- when the stage needs groups (an alignment, or one matrix per group) -- read the optional
+        <root>/subject.npy (n,) and map its ids to dense 0..G-1 over the WHOLE file, sorted by id, before the split: every split sees
+        the same mapping.  self.group (n,) int32 and self.groups are kept; the models are built for Cs virtual channels."""
+        from utils.eeg_spatial import SpatialStage, compose, load_matrix, needs_groups, parse_eeg_spatial
+        spec = parse_eeg_spatial(spatial)
+        if not spec.active:
+            return
+        matrix = load_matrix(spec)
+        W0 = compose(spec, self.enc_in, matrix)
+        self.group, self.groups, labels = np.zeros(n, dtype=np.int32), 1, None
+        if needs_groups(spec, matrix):
+            sp = os.path.join(root_path, "subject.npy")
+            if os.path.exists(sp):
+                ids = np.load(sp, allow_pickle=False)
+                if ids.shape != (n,) or not np.issubdtype(ids.dtype, np.integer):
+                    raise ValueError(f"{sp}: expected {n} integer subject ids, got {ids.dtype} {ids.shape}")
+                labels, dense = np.unique(ids, return_inverse=True)
+                self.group, self.groups = dense.astype(np.int32).reshape(n), int(len(labels))
+            elif notice is not None:
+                notice(f"eeg_spatial: {sp} not found; all {n} trials are one group")
+        if W0.shape[0] > 1 and W0.shape[0] != self.groups:
+            raise ValueError(f"--eeg_spatial: the matrix holds {W0.shape[0]} groups, the shards {self.groups}")
+        self.spatial = SpatialStage(spec, W0, self.groups, labels)
+        self.enc_in = self.spatial.Cs
+
     def __len__(self):
         return len(self.idx)
+
+    def raw_batches(self, batch_size):
+        """The split's raw trials in data set order as (X (B,C,T) float32, None, gid (B,) int32) host arrays: the pass that fits an
+        alignment when the items themselves are not raw."""
+        for i in range(0, len(self.idx), int(batch_size)):
+            j = self.idx[i:i + int(batch_size)]
+            yield np.stack([np.asarray(self.X[k], dtype=np.float32) for k in j]), None, self.group[j]
 
     def __getitem__(self, i):
         j = self.idx[i]
         x = np.asarray(self.X[j], dtype=np.float32)
         y = torch.tensor([self.y[j]], dtype=torch.int64)
         if self.raw:              # device pipeline: data_provider.device_prefetch does the rest on the batch
+            if self.spatial is not None:
+                return torch.from_numpy(np.ascontiguousarray(x)), y, int(self.group[j])
             return torch.from_numpy(np.ascontiguousarray(x)), y
+        if self.spatial is not None:                  # the stage's fp32 restatement, then the rules below on its output
+            from utils.eeg_spatial import spatial_numpy
+            x = spatial_numpy(x, self.spatial.matrix_of(int(self.group[j])), dtype=np.float32)
         if self.pre is not None:  # (Tv, Cout): collate_fn(max_len=seq_len) pads the time axis and builds the mask
             from utils.eeg_filter import filterbank_numpy
             p = self.pre
@@ -120,6 +161,12 @@ def collate_raw(data):
     """list of (X[C,T] raw, y[1]) -> (X[B,C,T], y[B,1], None): the batch contract before the device transform."""
     feats, labels = zip(*data)
     return torch.stack(feats, dim=0), torch.stack(labels, dim=0), None
+
+
+def collate_raw_group(data):
+    """collate_raw under --eeg_spatial: list of (X[C,T] raw, y[1], group) -> (X[B,C,T], y[B,1], gid[B] int32)."""
+    feats, labels, groups = zip(*data)
+    return torch.stack(feats, dim=0), torch.stack(labels, dim=0), torch.tensor(groups, dtype=torch.int32)
 
 
 # The 39 -> 3 fold of the sentence classes (daily life 0 / social-emotional 1 / professional services 2): the constant

@@ -23,7 +23,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from data_provider.data_factory import data_provider
-from data_provider.device_prefetch import DevicePrefetcher, preprocess_raw_batch, standardise_raw_batch
+from data_provider.device_prefetch import DevicePrefetcher, preprocess_raw_batch, spatial_raw_batch, standardise_raw_batch
 from ign_hip import ddp as ign_ddp
 from ign_hip import ops as ign_ops
 from ign_hip.ddp import FlatAdam, FlatParamBucket
@@ -113,6 +113,8 @@ class Experiment(object):
             args.epsilon, args.beta_schedule, args.distance_func, args.sbm_cls)
         if self.rank == 0:
             os.makedirs(self.checkpoint_dir, exist_ok=True)
+            if getattr(self.train_data, 'spatial', None) is not None:     # the record of what each virtual channel is
+                self.train_data.spatial.save(self.checkpoint_dir)
         self.loss_fn = nn.CrossEntropyLoss()
         self.epoch_stop = 0
         print(f"Experiment: model={args.model} dnn={getattr(args, 'dnn_type', None)} device={self.device} "
@@ -230,6 +232,29 @@ class Experiment(object):
         self.train_data, self.train_loader = data_provider(self.args, flag="train")
         self.val_data, self.val_loader = data_provider(self.args, flag="val")
         self.test_data, self.test_loader = data_provider(self.args, flag="test")
+        self._fit_eeg_spatial()
+
+    def _fit_eeg_spatial(self):
+        """--eeg_spatial align=euclid: one ordered, un-sharded, un-augmented pass over the raw TRAINING trials before the model is
+        built (utils.eeg_spatial.fit_alignment: ops.eeg_spatial + ops.eeg_gram per batch on the device, float64 on the host), also
+        under --test_only; every rank runs the same pass and ends with the same bits, without a collective.  The fitted matrices go
+        to all three splits.  Without the flag, or without align=, nothing runs."""
+        stage = getattr(self.train_data, 'spatial', None)
+        if stage is None or stage.spec.align == 'none':
+            return
+        from data_provider.data_factory import ordered_loader
+        from utils.eeg_spatial import fit_alignment
+        if getattr(self.train_loader, 'device_transform', None) is not None:      # raw items: the loader's own batches
+            batches = ordered_loader(self.train_loader)
+            if self.device.type == 'cuda':
+                batches = DevicePrefetcher(batches, self.device)
+        else:
+            batches = self.train_data.raw_batches(self.args.batch_size)
+        W = fit_alignment(batches, stage.W0, stage.groups, stage.spec.rtol, notice=print if self.rank == 0 else None)
+        for d in (self.train_data, self.val_data, self.test_data):
+            d.spatial.W, d.spatial.fitted = W, True
+        if self.rank == 0:
+            print(f"eeg_spatial: Euclidean alignment of {stage.groups} group(s) fitted on {len(self.train_data)} training trials")
 
     def _sync_buffers(self, src=0):
         """floating-point buffers (BatchNorm running mean / variance) of rank `src` -> every rank"""
@@ -242,6 +267,9 @@ class Experiment(object):
         transform = standardise_raw_batch if kind == 'standardise_raw' else None
         if kind == 'eeg_preprocess':                    # --eeg_preprocess: filter, decimate, fit, then the same standardisation
             transform = preprocess_raw_batch(loader.eeg_preprocess, self.device)
+        stage = getattr(loader, 'eeg_spatial', None)
+        if stage is not None and transform is not None:  # --eeg_spatial: one launch in front of either
+            transform = spatial_raw_batch(torch.from_numpy(stage.W).to(self.device), transform)
         if self.device.type != 'cuda' and transform is None:
             return loader
         return DevicePrefetcher(loader, self.device, transform=transform)
@@ -771,7 +799,7 @@ class Experiment(object):
         return test_loss, res, test_df
 
     SUMMARY_ARGS = ('model', 'dataset', 'dnn_type', 'train_epochs', 'num_shapelet', 'lambda_reg', 'lambda_div', 'epsilon', 'lr',
-                    'seed', 'pos_weight', 'beta_schedule', 'gating_value', 'distance_func', 'sbm_cls')
+                    'seed', 'pos_weight', 'beta_schedule', 'gating_value', 'distance_func', 'sbm_cls', 'eeg_spatial')
 
     def _write_summary(self, res, result_dir):
         """One-row test summary: the run's hyper-parameters, accuracy, and -- for the shapelet models -- the

@@ -170,6 +170,9 @@ SIGNATURES = {
     "ign_eeg_preprocess_nct_to_btc": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, vp]),
     "ign_eeg_filterbank_ws_bytes": (sz, [ci, ci, ci, ci, ci, ci, ci, ci]),
     "ign_eeg_filterbank_nct_to_btc": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, cf, vp]),
+    "ign_eeg_spatial_nct": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]),
+    "ign_eeg_gram_ws_bytes": (sz, [ci, ci, ci, ci]),
+    "ign_eeg_gram_nct": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
 }
 
 

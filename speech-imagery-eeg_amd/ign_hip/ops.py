@@ -220,6 +220,69 @@ def eeg_filterbank(x_nct, taps, quad=None, *, decimate=1, edge="reflect", channe
     return _eeg_bank(name, x_nct, taps, quad, decimate, edge, channels, timepoints, eps)
 
 
+def _group_ids(name, gid, B):
+    """The per-sample group ids as the spatial kernels take them: None, or a contiguous int32 (B) tensor on the GPU."""
+    if gid is None:
+        return None
+    if not torch.is_tensor(gid) or not gid.is_cuda or gid.dtype != torch.int32 or tuple(gid.shape) != (B,):
+        what = f"{gid.dtype} {tuple(gid.shape)} on {gid.device}" if torch.is_tensor(gid) else type(gid).__name__
+        raise _lib.IgnError(f"{name}: gid must be an int32 tensor of shape ({B},) on the GPU, got {what}")
+    return gid.contiguous()
+
+
+def _spatial_out(name, out, shape, dtype, device):
+    if out is None:
+        return torch.empty(shape, device=device, dtype=dtype)
+    if not out.is_cuda or out.dtype != dtype or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+        raise _lib.IgnError(f"{name}: out must be a contiguous {dtype} tensor of shape {tuple(shape)} on the GPU, got {out.dtype} "
+                            f"{tuple(out.shape)} on {out.device}")
+    return out
+
+
+def eeg_spatial(x_nct, W, gid=None, *, out=None):
+    """Raw (B,Cin,T) recordings -> y (B,Cs,T) on the GPU, y[b] = W[gid[b]] . x[b] across the electrodes (ign_eeg_spatial_nct; the
+    rule, pivot included, is restated in utils/eeg_spatial.py:spatial_numpy): W (G,Cs,Cin) float32 on the GPU, a 2-D (Cs,Cin) W is
+    one group; gid (B,) int32 on the GPU, None = group 0.  A gid outside [0,G) gives zeros for that sample.  The output keeps the
+    input's layout, so standardise_nct_to_btc / eeg_filterbank run on it unchanged.  `out`: write into this tensor instead of a
+    new one.  A non-contiguous x or W is copied."""
+    name = "eeg_spatial"
+    _need_gpu(name, x_nct, W)
+    if x_nct.dim() != 3 or W.dim() not in (2, 3):
+        raise _lib.IgnError(f"{name}: expected x (B,Cin,T) and W (G,Cs,Cin) or (Cs,Cin), got {tuple(x_nct.shape)} and {tuple(W.shape)}")
+    w = (W.unsqueeze(0) if W.dim() == 2 else W).contiguous()
+    x = x_nct.contiguous()
+    B, Cin, T = x.shape
+    G, Cs, Cw = w.shape
+    if Cw != Cin:
+        raise _lib.IgnError(f"{name}: W {tuple(W.shape)} takes {Cw} input channels, x {tuple(x_nct.shape)} has {Cin}")
+    gid = _group_ids(name, gid, B)
+    y = _spatial_out(name, out, (B, Cs, T), torch.float32, x.device)
+    _lib.check(_lib.lib().ign_eeg_spatial_nct(_ptr(x), _ptr(w), _ptr(gid), _ptr(y), B, Cin, T, Cs, G, _stream()), "ign_eeg_spatial_nct")
+    return y
+
+
+def eeg_gram(x_nct, gid=None, groups=1, *, out=None):
+    """(B,C,T) float32 on the GPU -> (gram (G,C,C) float32, count (G,) int32), G = `groups` (ign_eeg_gram_nct; restated in
+    utils/eeg_spatial.py:gram_numpy): per group, the sum over its samples in ascending b of z z^T with z the rows minus their first
+    sample, minus the mean of that.  Both outputs are overwritten -- zeros for an empty group -- and gram[g] is symmetric bit for
+    bit; the caller accumulates batches (in float64).  `out`: (gram, count) tensors to write into."""
+    name = "eeg_gram"
+    _need_gpu(name, x_nct)
+    if x_nct.dim() != 3:
+        raise _lib.IgnError(f"{name}: expected x (B,C,T), got {tuple(x_nct.shape)}")
+    x = x_nct.contiguous()
+    B, C, T = x.shape
+    G = int(groups)
+    gid = _group_ids(name, gid, B)
+    gram, count = (None, None) if out is None else out
+    gram = _spatial_out(name, gram, (max(G, 0), C, C), torch.float32, x.device)
+    count = _spatial_out(name, count, (max(G, 0),), torch.int32, x.device)
+    L = _lib.lib()
+    ws = torch.empty(L.ign_eeg_gram_ws_bytes(B, C, T, G) // 4 or 1, device=x.device, dtype=torch.float32)
+    _lib.check(L.ign_eeg_gram_nct(_ptr(x), _ptr(gid), _ptr(gram), _ptr(count), _ptr(ws), B, C, T, G, _stream()), "ign_eeg_gram_nct")
+    return gram, count
+
+
 def augment(x, seed, *, lengths=None, shift=0.0, scale=0.0, noise=0.0, channel_drop=0.0, time_mask=0.0):
     """Training augmentation of a contiguous fp32 (B,T,C) batch on the GPU -> a new tensor (ign_augment_btc; the rule is
     csrc/ign_augment.h, restated in utils/augment.py): a circular shift by up to `shift` * length, a per-channel gain in

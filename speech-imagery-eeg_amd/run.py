@@ -30,6 +30,10 @@ Differences, all repairs of fork defects listed in SURVEY section 0:
     ``bank=4:8+8:13+13:30+30:45`` (1 to 8 bands instead of ``band=``) makes a filter bank in the same two passes: every band of every
     electrode is a channel of its own, band-major (``enc_in`` = bands x electrodes; ``fit`` counts ``--target_channels`` per band),
     and ``envelope`` turns every band into its band-power envelope (needs ``edge=reflect`` and both edges of every band);
+  * ``--eeg_spatial ref=car,matrix=PATH.npy,align=euclid`` (``--data EEG`` / ``EEG3``; any subset) applies one matrix per subject
+    across the electrodes of the raw shards in front of all of that -- a common average reference, a montage or unmixing matrix
+    computed offline, Euclidean alignment fitted on the training split -- as one exact-fp32 matrix-core launch in the prefetcher
+    (numpy on the CPU item path); ``enc_in`` becomes the matrix's row count; the default ``none`` changes nothing;
   * ``--task_name regression --data Monash`` is the reference's regression twin (exp/experiment_regression.py), with the
     repairs R1-R3 of DESIGN 2.3;
   * multi-GPU is one process per GPU: ``python -m torch.distributed.run --nproc-per-node N run.py ...``.
@@ -158,6 +162,16 @@ def build_parser():
                         "electrodes per band; envelope replaces every band by its amplitude envelope (Hilbert-pair FIR; needs "
                         "edge=reflect and both edges of every band; band=LO:HI,envelope is a bank of one band).  --augment sees the "
                         "bank's channels: its chan_drop drops single band channels, not whole electrodes")
+    p.add_argument("--eeg_spatial", type=str, default='none',
+                   help="--data EEG / EEG3: a spatial filter across the electrodes of the raw shards, in front of --eeg_preprocess and "
+                        "the standardisation, one matrix-core launch on the device: none, or a comma list of ref=car (common average "
+                        "reference), matrix=PATH.npy (a (Cs,C) montage / unmixing matrix computed offline, or (G,Cs,C) with one per "
+                        "subject), align=euclid (Euclidean alignment: every subject's trials whitened by the inverse square root of "
+                        "that subject's mean spatial covariance, fitted on the training split before the first step) and rtol=R "
+                        "(default 1e-6: eigenvalues below R times the largest are not inverted).  The matrices compose as "
+                        "align . matrix . ref; the models see Cs virtual channels.  Subjects come from the optional <root>/subject.npy "
+                        "(n,) integer ids; without it all trials are one group.  What was applied is written as eeg_spatial.npz beside "
+                        "the checkpoint")
     # experiment
     p.add_argument("--lr", type=float, default=5e-3)
     p.add_argument("--lr_decay", action="store_true")
@@ -218,6 +232,9 @@ def check_args(args):
     from utils.eeg_filter import parse_eeg_preprocess
     if parse_eeg_preprocess(getattr(args, 'eeg_preprocess', None)).active and getattr(args, 'data', None) not in ('EEG', 'EEG3'):
         raise ValueError(f"--eeg_preprocess filters the raw CHISCO shards (--data EEG / EEG3), not --data {args.data}")
+    from utils.eeg_spatial import parse_eeg_spatial
+    if parse_eeg_spatial(getattr(args, 'eeg_spatial', None)).active and getattr(args, 'data', None) not in ('EEG', 'EEG3'):
+        raise ValueError(f"--eeg_spatial acts on the electrodes of the raw CHISCO shards (--data EEG / EEG3), not --data {args.data}")
 
 
 def _num_class_from_flags(args):
