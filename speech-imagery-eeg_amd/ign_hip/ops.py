@@ -1695,16 +1695,15 @@ def backward(loss):
         loss.backward()
 
 
-def _loss_tail(entry, sbm, dnn, crit, beta, reg, more=()):
+def _loss_tail(entry, sbm, dnn, crit, beta, reg, rule=None, more=()):
     """The one launcher of the gated loss tails -> (loss3, out, eta, gsd): loss3[2] = criterion(gate(sbm, dnn)) + beta*criterion(sbm)
-    [+ reg], gsd (2, B, N) = its gradient w.r.t. (sbm, dnn) in one buffer.  `entry`: "ign_loss" (cross-entropy, crit = (labels,)),
-    "ign_loss+w" (the weighted / label-smoothed cross-entropy, crit = (labels, class weights or None), more = (label_smoothing,);
-    reports as ign_loss), "ign_loss+mix" (the same with soft labels, crit = (labels, second labels, lam, class weights or None),
-    more = (label_smoothing,); reports as ign_loss) or "ign_crps_loss" (CRPS, crit = (target, edges)); `crit` sits between `dnn` and `reg` in the entry
-    point's signature, the numbers `more` between `beta` and the stream."""
-    symbol = {"ign_loss": "ign_loss_fwd_bwd_reg", "ign_loss+w": "ign_loss_w_fwd_bwd_reg",
-              "ign_loss+mix": "ign_loss_mix_fwd_bwd_reg", "ign_crps_loss": "ign_loss_crps_fwd_bwd_reg"}[entry]
-    entry = entry.partition("+")[0]
+    [+ reg], gsd (2, B, N) = its gradient w.r.t. (sbm, dnn) in one buffer.  `entry`: "ign_loss" (cross-entropy; by label `rule`:
+    None, crit = (labels,) | "weighted", also label-smoothed, crit = (labels, class weights or None), more = (label_smoothing,) |
+    "soft", the same with soft labels, crit = (labels, second labels, lam, class weights or None), more = (label_smoothing,)) or
+    "ign_crps_loss" (CRPS, crit = (target, edges)); `crit` sits between `dnn` and `reg` in the entry point's signature, the numbers
+    `more` between `beta` and the stream."""
+    symbol = {("ign_loss", None): "ign_loss_fwd_bwd_reg", ("ign_loss", "weighted"): "ign_loss_w_fwd_bwd_reg",
+              ("ign_loss", "soft"): "ign_loss_mix_fwd_bwd_reg", ("ign_crps_loss", None): "ign_loss_crps_fwd_bwd_reg"}[entry, rule]
     B, N = sbm.shape
     out = torch.empty_like(sbm)
     gsd = torch.empty(2, B, N, device=sbm.device, dtype=torch.float32)
@@ -1719,15 +1718,15 @@ def _loss_tail(entry, sbm, dnn, crit, beta, reg, more=()):
     return loss3, out, eta, gsd
 
 
-def _tail_forward(ctx, entry, sbm, dnn, prepare, crit, beta, reg, more=()):
+def _tail_forward(ctx, entry, sbm, dnn, prepare, crit, beta, reg, rule=None, more=()):
     """What the forwards of IgnLossFn and IgnCrpsLossFn share -> (loss, out, eta); out / eta are reporting outputs.  `prepare`
-    (_ce_inputs / _crps_inputs) checks the node's criterion arguments `crit` against the (B, N) logits and converts them."""
-    name = entry.partition("+")[0]
-    _need_gpu(name, sbm, dnn, reg)
+    (_ce_inputs / _crps_inputs) checks the node's criterion arguments `crit` against the (B, N) logits and converts them; `rule` and
+    `more` are _loss_tail's."""
+    _need_gpu(entry, sbm, dnn, reg)
     sbm, dnn = sbm.contiguous(), dnn.contiguous()
     if dnn.shape != sbm.shape:                        # the kernel reads B*N elements of each
-        raise _lib.IgnError(f"{name}: expert logits {tuple(sbm.shape)} vs {tuple(dnn.shape)}")
-    loss3, out, eta, gsd = _loss_tail(entry, sbm, dnn, prepare(name, sbm, *crit), beta, reg, more)
+        raise _lib.IgnError(f"{entry}: expert logits {tuple(sbm.shape)} vs {tuple(dnn.shape)}")
+    loss3, out, eta, gsd = _loss_tail(entry, sbm, dnn, prepare(entry, sbm, *crit), beta, reg, rule, more)
     ctx.save_for_backward(gsd)
     ctx.n_crit, ctx.has_reg = len(crit), reg is not None
     ctx.mark_non_differentiable(out, eta)
@@ -1757,15 +1756,14 @@ class IgnLossFn(torch.autograd.Function):
     def forward(ctx, sbm, dnn, y, beta, reg, *opts):
         ctx.n_opts = len(opts)
         class_weight, label_smoothing, *soft = opts or (None, 0.0)
-        if soft:
-            y_b, lam = soft
-            return _tail_forward(ctx, "ign_loss+mix", sbm, dnn,
-                                 lambda name, logits, y: _ce_inputs(name, logits, y) + (y_b.contiguous().long(), lam, class_weight),
-                                 (y,), beta, reg, (float(label_smoothing),))
-        if class_weight is None and label_smoothing == 0.0:
-            return _tail_forward(ctx, "ign_loss", sbm, dnn, _ce_inputs, (y,), beta, reg)
-        return _tail_forward(ctx, "ign_loss+w", sbm, dnn, lambda name, logits, y: _ce_inputs(name, logits, y) + (class_weight,),
-                             (y,), beta, reg, (float(label_smoothing),))
+        if soft:                                      # (y_b, lam)
+            rule, extra = "soft", (soft[0].contiguous().long(), soft[1], class_weight)
+        elif class_weight is None and label_smoothing == 0.0:
+            rule, extra = None, ()
+        else:
+            rule, extra = "weighted", (class_weight,)
+        return _tail_forward(ctx, "ign_loss", sbm, dnn, lambda name, logits, y: _ce_inputs(name, logits, y) + extra, (y,), beta, reg,
+                             rule, (float(label_smoothing),) if rule else ())
 
     @staticmethod
     def backward(ctx, gl, gout, geta):
@@ -1813,16 +1811,15 @@ def ign_loss(sbm_out, dnn_out, y, beta=1.0, reg=None, class_weight=None, label_s
     `y_b` (integer labels (B,)) / `lam` (float32 (B,) in [0, 1], no gradient): soft labels of mixup / CutMix -- every row counts as
     class y with the share lam and as class y_b with 1 - lam in both criteria (ign_loss_mix_fwd_bwd_reg, one launch; the formula is
     utils/mix.py's CEm); lam == 1 is the call without them."""
-    if y_b is not None or lam is not None:
+    soft = y_b is not None or lam is not None
+    opts = ()                                         # the default call: a node of five inputs
+    if soft or class_weight is not None or label_smoothing != 0.0:
         _check_ce_options("ign_loss", sbm_out, class_weight, label_smoothing)
+        opts = (class_weight.contiguous() if class_weight is not None else None, float(label_smoothing))
+    if soft:
         _check_soft_labels("ign_loss", sbm_out, y_b, lam)
-        return IgnLossFn.apply(sbm_out.float(), dnn_out.float(), y, beta, reg, class_weight.contiguous() if class_weight is not None
-                               else None, float(label_smoothing), y_b.reshape(-1), lam.contiguous())
-    if class_weight is None and label_smoothing == 0.0:
-        return IgnLossFn.apply(sbm_out.float(), dnn_out.float(), y, beta, reg)
-    _check_ce_options("ign_loss", sbm_out, class_weight, label_smoothing)
-    return IgnLossFn.apply(sbm_out.float(), dnn_out.float(), y, beta, reg, class_weight.contiguous() if class_weight is not None
-                           else None, float(label_smoothing))
+        opts += (y_b.reshape(-1), lam.contiguous())
+    return IgnLossFn.apply(sbm_out.float(), dnn_out.float(), y, beta, reg, *opts)
 
 
 def _crps_inputs(name, logits, target, edges):
