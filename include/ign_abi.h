@@ -648,6 +648,36 @@ int ign_scale_flat(float* g, long long n, const float* coef_dev, void* stream);
  * launch per micro-step (one extra read of each slot) instead of one accumulate kernel per parameter.                        */
 int ign_gather_flat_acc(const void* const* src, const long long* off, const long long* n, int count, float* flat, void* stream);
 
+/* AdamW with a per-step learning-rate schedule and an EMA of the parameters, on the flat buffers (csrc/ign_sched.h holds the rule).
+ * Optimizer step s = 1, 2, ...; W = warmup, M = min_lr, S = total_steps:
+ *   s < W: lr = base_lr * s / W;   IGN_SCHED_CONSTANT (0), s >= W: lr = base_lr;
+ *   IGN_SCHED_COSINE (1), s >= W: lr = M + (base_lr - M) * 0.5 * (1 + cos(pi * t / T)), t = min(s - W, T), T = max(1, S - W);
+ *   EMA decay d = min(ema_decay, (1 + s) / (10 + s));   all in double, rounded to float once.
+ * ign_sched_lr: the learning rate of step `step` by that rule, on the host (no device, no stream): for logging and tests.       */
+float ign_sched_lr(int sched_kind, double base_lr, int warmup, double min_lr, long long total_steps, long long step);
+
+/* One AdamW step with the count on the device (graph-capturable, like ign_adam_step_dev): a tick kernel increments *step_dev and
+ * leaves hp_dev[4] = [bias_correction1, sqrt(bias_correction2), lr of this step, EMA decay of this step]; the update kernel reads
+ * them there, applies param *= 1 - lr * weight_decay where decay_mask says so and then the Adam update of ign_adam_step (same
+ * element rule).  decay_mask: one byte per 64-float chunk of the buffers, ceil(n / 64) bytes ON THE DEVICE, non-zero = decay;
+ * NULL = decay every element.  weight_decay == 0 skips the multiply.  coef_dev: the clip coefficient of ign_grad_norm_clip
+ * (grad is read as grad * coef_dev[0]) or NULL for no clipping.  The schedule arguments must not change over a captured run.
+ * With weight_decay 0, IGN_SCHED_CONSTANT and warmup 0 the parameters and moments are bit for bit those of ign_adam_step_dev /
+ * ign_adam_step_clip_dev at lr = (float)base_lr.  All four buffers 16-byte aligned; arguments out of range: IGN_E_ARG.          */
+int ign_adamw_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, float beta1, float beta2,
+                       float eps, float weight_decay, const unsigned char* decay_mask, int sched_kind, double base_lr, int warmup,
+                       double min_lr, long long total_steps, double ema_decay, int* step_dev, float* hp_dev, const float* coef_dev,
+                       void* stream);
+
+/* ema[i] += (1 - hp_dev[3]) * (param[i] - ema[i]), i < n: the exponential moving average of the parameters with the decay the
+ * tick of ign_adamw_step_dev left on the device.  param == ema (in value) leaves ema unchanged to the bit.  A launch of its own so
+ * that it can follow whatever rewrites the parameters after the optimizer (the --pos_weight clamp).  Both 16-byte aligned.     */
+int ign_ema_update(float* ema, const float* param, long long n, const float* hp_dev, void* stream);
+
+/* Exchange the n floats of a and b in place, one launch, no temporary (a and b 16-byte aligned, not overlapping): the averaged
+ * weights go into the parameter buffer for validation and back out without any pointer changing.                             */
+int ign_swap_flat(float* a, float* b, long long n, void* stream);
+
 /* EEG-CNN block 1 without its (B,F1,C,T) intermediate (1 GB at B=256) -- see csrc/ign_eegcnn.hip for the algebra.
  * Replaces the BatchNorm-1 batch statistics of IGN/model/eegcnn.py:90-91 (block1_conv1 -> block1_bn1):
  *   y1[r,f,t] = sum_j w1[f,j] xpad[r, t+j]   (rows r = (b,c); 'same' zero padding, pad_left on the left)
@@ -950,7 +980,7 @@ int ign_bn_bwd_apply(const float* g, const float* y, const float* a, const float
 /* Per-kernel HIP-event timing (measurement only; off by default).  When enabled every kernel launch made by
  * this library is bracketed by hipEventRecord on the caller's stream.  ign_timing_read() waits for the recorded
  * events of `label` ("shp_fwd", "shp_bwd", "reduce_parts", "instnorm", "attn_fwd", "attn_bwd_dkdv", "attn_bwd_dq",
- * "attn_delta", "head_fwd", "head_bwd_x", "head_bwd_w", "adam", "grad_norm", "scale_flat", "gather_acc",
+ * "attn_delta", "head_fwd", "head_bwd_x", "head_bwd_w", "adam", "adamw", "ema", "swap_flat", "grad_norm", "scale_flat", "gather_acc",
  * "conv1_sumsq_fwd", "conv1_sumsq_bwd", "dwconv1d", "dwconv1d_bwd_w"), and returns the accumulated
  * device milliseconds and launch count since the last enable.  Not for use under graph capture.             */
 int ign_timing_enable(int on);

@@ -4,7 +4,11 @@
 //  * Adam       one launch over the flat buffers (torch.optim.Adam semantics, IGN/exp/experiment_classification.py:136,338): one
 //    element rule (adam_element), one kernel (adam_kernel<CLIP, DEV>), one launcher (adam_launch) behind the four ign_adam_step*
 //    entry points.
+//  * AdamW      the same element rule behind ign_adamw_step_dev (adamw_kernel<CLIP>): decoupled weight decay under a per-chunk mask,
+//    the learning rate of a per-step schedule and the EMA decay computed on the device by the scheduled tick (ign_sched.h), the
+//    EMA of the parameters (ign_ema_update) and the in-place exchange of two flat buffers (ign_swap_flat).
 #include "ign_common.h"
+#include "ign_sched.h"
 
 // ------------------------------------------------------------------------------------------------ Adam
 // The update of one element; `step` = lr / bias_correction1, `bc2_sqrt` = sqrt(bias_correction2).
@@ -57,6 +61,89 @@ __global__ void adam_tick_kernel(int* __restrict__ step_dev, float* __restrict__
     const int step = ++(*step_dev);
     bc_dev[0] = (float)(1.0 - pow((double)b1, (double)step));
     bc_dev[1] = (float)sqrt(1.0 - pow((double)b2, (double)step));
+}
+
+// ------------------------------------------------------------------------------------------------ AdamW, schedule, EMA
+// The scheduled tick: adam_tick_kernel's count and bias corrections (the same expressions, the same bits), plus the learning rate
+// and the EMA decay of this step by the rule of ign_sched.h -> hp = [bc1, bc2_sqrt, lr_t, d_t].  The schedule's parameters are
+// kernel arguments that never change over a run, so one captured launch serves all of it.
+__global__ void sched_tick_kernel(int* __restrict__ step_dev, float* __restrict__ hp, float b1, float b2, int kind, double base,
+                                  int warmup, double min_lr, long long total, double ema) {
+    const int step = ++(*step_dev);
+    hp[0] = (float)(1.0 - pow((double)b1, (double)step));
+    hp[1] = (float)sqrt(1.0 - pow((double)b2, (double)step));
+    hp[2] = ign_sched_lr_at(kind, base, warmup, min_lr, total, step);
+    hp[3] = ign_ema_decay_at(ema, step);
+}
+
+// adam_kernel's layout and element rule with the step's learning rate and bias corrections read from hp (sched_tick_kernel) and
+// decoupled weight decay in front of the update: p *= 1 - lr_t * wd where mask[chunk of 64 floats] != 0 (null mask: everywhere;
+// wd == 0: no multiply at all, so an undecayed element takes adam_element's path alone).  A lane's four elements start at a
+// multiple of four and so never straddle a chunk.
+template <bool CLIP>
+__global__ void __launch_bounds__(256) adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                    float* __restrict__ v, long long n, float b1, float b2, float eps, float wd,
+                                                    const unsigned char* __restrict__ mask, const float* __restrict__ hp,
+                                                    const float* __restrict__ coef) {
+    const long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= n) return;
+    const float bc1 = hp[0], bc2_sqrt = hp[1], lr = hp[2];
+    const float step = lr / bc1;
+    const float c = CLIP ? coef[0] : 1.f;
+    const bool decay = wd != 0.f && (!mask || mask[i >> 6]);
+    const float keep = 1.f - lr * wd;
+    if (i + 3 < n) {
+        float4 pv = *reinterpret_cast<float4*>(p + i);
+        float4 gv = *reinterpret_cast<const float4*>(g + i);
+        if (CLIP) { gv.x *= c; gv.y *= c; gv.z *= c; gv.w *= c; }
+        float4 mv = *reinterpret_cast<float4*>(m + i);
+        float4 vv = *reinterpret_cast<float4*>(v + i);
+        if (decay) { pv.x *= keep; pv.y *= keep; pv.z *= keep; pv.w *= keep; }
+        adam_element(pv.x, gv.x, mv.x, vv.x, b1, b2, step, bc2_sqrt, eps);
+        adam_element(pv.y, gv.y, mv.y, vv.y, b1, b2, step, bc2_sqrt, eps);
+        adam_element(pv.z, gv.z, mv.z, vv.z, b1, b2, step, bc2_sqrt, eps);
+        adam_element(pv.w, gv.w, mv.w, vv.w, b1, b2, step, bc2_sqrt, eps);
+        *reinterpret_cast<float4*>(p + i) = pv;
+        *reinterpret_cast<float4*>(m + i) = mv;
+        *reinterpret_cast<float4*>(v + i) = vv;
+    } else {
+        for (long long j = i; j < n; ++j) {
+            float pv = p[j], gv = CLIP ? g[j] * c : g[j], mv = m[j], vv = v[j];
+            if (decay) pv *= keep;
+            adam_element(pv, gv, mv, vv, b1, b2, step, bc2_sqrt, eps);
+            p[j] = pv; m[j] = mv; v[j] = vv;
+        }
+    }
+}
+
+// ema += (1 - d_t) * (p - ema), d_t = hp[3]: p == ema adds (1 - d_t) * 0 = 0, the average keeps its bits.
+__global__ void __launch_bounds__(256) ema_kernel(float* __restrict__ ema, const float* __restrict__ p, long long n,
+                                                  const float* __restrict__ hp) {
+    const long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= n) return;
+    const float w = 1.f - hp[3];
+    if (i + 3 < n) {
+        float4 e = *reinterpret_cast<float4*>(ema + i);
+        const float4 q = *reinterpret_cast<const float4*>(p + i);
+        e.x += w * (q.x - e.x); e.y += w * (q.y - e.y); e.z += w * (q.z - e.z); e.w += w * (q.w - e.w);
+        *reinterpret_cast<float4*>(ema + i) = e;
+    } else {
+        for (long long j = i; j < n; ++j) ema[j] += w * (p[j] - ema[j]);
+    }
+}
+
+// a <-> b in place: every lane holds its own elements of both in registers between the loads and the stores.
+__global__ void __launch_bounds__(256) swap_flat_kernel(float* __restrict__ a, float* __restrict__ b, long long n) {
+    const long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= n) return;
+    if (i + 3 < n) {
+        const float4 x = *reinterpret_cast<float4*>(a + i);
+        const float4 y = *reinterpret_cast<float4*>(b + i);
+        *reinterpret_cast<float4*>(a + i) = y;
+        *reinterpret_cast<float4*>(b + i) = x;
+    } else {
+        for (long long j = i; j < n; ++j) { const float x = a[j]; a[j] = b[j]; b[j] = x; }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ gather
@@ -211,6 +298,74 @@ extern "C" int ign_adam_step_dev(float* p, const float* g, float* m, float* v, l
 extern "C" int ign_adam_step_clip_dev(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2,
                                       float eps, int* step_dev, float* bc_dev, const float* coef_dev, void* stream) {
     return adam_launch("ign_adam_step_clip_dev", p, g, m, v, n, lr, beta1, beta2, eps, 0, step_dev, bc_dev, coef_dev, stream);
+}
+
+extern "C" float ign_sched_lr(int kind, double base_lr, int warmup, double min_lr, long long total_steps, long long step) {
+    return ign_sched_lr_at(kind, base_lr, warmup, min_lr, total_steps, step);
+}
+
+extern "C" int ign_adamw_step_dev(float* p, const float* g, float* m, float* v, long long n, float beta1, float beta2, float eps,
+                                  float weight_decay, const unsigned char* decay_mask, int sched_kind, double base_lr, int warmup,
+                                  double min_lr, long long total_steps, double ema_decay, int* step_dev, float* hp_dev,
+                                  const float* coef_dev, void* stream) {
+    if (!p || !g || !m || !v || !step_dev || !hp_dev || n <= 0) {
+        ign_set_error("ign_adamw_step_dev: null pointer or n <= 0");
+        return IGN_E_ARG;
+    }
+    if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) {
+        ign_set_error("ign_adamw_step_dev: buffers must be 16-byte aligned");
+        return IGN_E_ARG;
+    }
+    if (!ign_sched_valid(sched_kind, base_lr, warmup, min_lr, total_steps) || !(weight_decay >= 0.f) ||
+        !(ema_decay >= 0.0 && ema_decay < 1.0)) {
+        ign_set_error("ign_adamw_step_dev: schedule kind %d, base_lr %g, warmup %d, min_lr %g, total_steps %lld, weight_decay %g or "
+                      "ema_decay %g out of range", sched_kind, base_lr, warmup, min_lr, total_steps, (double)weight_decay, ema_decay);
+        return IGN_E_ARG;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(sched_tick_kernel, dim3(1), dim3(1), 0, s, step_dev, hp_dev, beta1, beta2, sched_kind, base_lr, warmup, min_lr,
+                       total_steps, ema_decay);
+    int rc;
+    if ((rc = ign_check_launch("sched_tick_kernel"))) return rc;
+    IgnScopedTimer tm("adamw", s);
+    const long long blocks = (n / 4 + 256) / 256;
+    hipLaunchKernelGGL(coef_dev ? adamw_kernel<true> : adamw_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, p, g, m, v, n,
+                       beta1, beta2, eps, weight_decay, decay_mask, (const float*)hp_dev, coef_dev);
+    return ign_check_launch("adamw_kernel");
+}
+
+extern "C" int ign_ema_update(float* ema, const float* p, long long n, const float* hp_dev, void* stream) {
+    if (!ema || !p || !hp_dev || n <= 0) {
+        ign_set_error("ign_ema_update: null pointer or n <= 0");
+        return IGN_E_ARG;
+    }
+    if (((uintptr_t)ema | (uintptr_t)p) & 15) {
+        ign_set_error("ign_ema_update: ema and p must be 16-byte aligned");
+        return IGN_E_ARG;
+    }
+    IgnScopedTimer tm("ema", (hipStream_t)stream);
+    const long long blocks = (n / 4 + 256) / 256;
+    hipLaunchKernelGGL(ema_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, ema, p, n, hp_dev);
+    return ign_check_launch("ema_kernel");
+}
+
+extern "C" int ign_swap_flat(float* a, float* b, long long n, void* stream) {
+    if (!a || !b || n <= 0) {
+        ign_set_error("ign_swap_flat: null pointer or n <= 0");
+        return IGN_E_ARG;
+    }
+    if (((uintptr_t)a | (uintptr_t)b) & 15) {
+        ign_set_error("ign_swap_flat: a and b must be 16-byte aligned");
+        return IGN_E_ARG;
+    }
+    if (a < b ? a + n > b : b + n > a) {
+        ign_set_error("ign_swap_flat: a and b overlap");
+        return IGN_E_ARG;
+    }
+    IgnScopedTimer tm("swap_flat", (hipStream_t)stream);
+    const long long blocks = (n / 4 + 256) / 256;
+    hipLaunchKernelGGL(swap_flat_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, b, n);
+    return ign_check_launch("swap_flat_kernel");
 }
 
 static int gather_flat(const char* who, bool acc, const void* const* src, const long long* off, const long long* n, int count,

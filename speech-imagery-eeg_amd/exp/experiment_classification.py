@@ -11,6 +11,7 @@ Deliberate repairs of fork defects: dataset parameters are ta
 UEA too (D5); ``EEGCNN`` receives (B,C,T) and no mask (D9); ``np.Inf`` is not used (D12).  Reproduced as-is: IGN is
 built WITHOUT the ``--num_shapelet`` lists (D4), ``--amp`` switches bf16 autocast OFF (D3).
 """
+import contextlib
 import os
 import sys
 import time
@@ -73,6 +74,7 @@ class Experiment(object):
         'EEGCNN': get_eegcnn_model,
     }
     class_weight, label_smoothing = None, 0.0       # the training criterion's options (_resolve_loss_options)
+    _optim_active, _ema = False, False              # --weight_decay / --lr_schedule / --ema (_resolve_optim_options)
 
     def __init__(self, args):
         self.args = args
@@ -83,6 +85,7 @@ class Experiment(object):
             self.device = torch.device('cuda', int(os.environ.get('LOCAL_RANK', 0)) if self.distributed else 0)
         else:
             self.device = torch.device('cpu')
+        self._resolve_optim_options()   # --weight_decay / --lr_schedule / --ema: what is refused raises before anything is built
 
         self._load_data()
         self._get_params_from_data()
@@ -101,7 +104,21 @@ class Experiment(object):
         if self.distributed or self.device.type == 'cuda':
             self.bucket = FlatParamBucket(self.model, self.world)
             self.bucket.broadcast_state(0)
-        if self.device.type == 'cuda':
+        if self.device.type == 'cuda' and self._optim_active:
+            # AdamW / per-step schedule / EMA on the flat path; S = the run's optimizer steps (a step closes when the run-wide
+            # batch count is a multiple of the accumulation)
+            from utils.optim_rule import total_steps
+            wd, spec, ema = self._optim_options
+            self.optimizer = FlatAdam(self.bucket, lr=self.args.lr, weight_decay=wd, schedule=spec, ema=ema,
+                                      total_steps=total_steps(self.args.train_epochs, len(self.train_loader),
+                                                              self.args.gradient_accumulation_steps))
+            if ema > 0.0 and self.args.pos_weight:
+                # the average starts inside the constraint the clamp keeps the live weights in from the first step on: the model's
+                # own clamp on the averaged copy (swapped in and out again; the live weights are not touched)
+                self.optimizer.swap_ema()
+                self.model.step()
+                self.optimizer.swap_ema()
+        elif self.device.type == 'cuda':
             self.optimizer = FlatAdam(self.bucket, lr=self.args.lr)
         else:
             self.optimizer = torch.optim.Adam(self.model.parameters(), lr=self.args.lr)
@@ -227,6 +244,34 @@ class Experiment(object):
         lam = put(lam)
         span = put(span) if self._mix_spec.cutmix > 0.0 else None
         return ign_ops.mix(batch_x.contiguous(), lam, roll, span=span, lengths=lengths), (label.roll(-roll), lam)
+
+    def _resolve_optim_options(self):
+        """--weight_decay / --lr_schedule / --ema -> self._optim_options (weight decay, LrSchedule, EMA decay) and self._optim_active
+        (False when all three are neutral, also for a namespace without the flags: the optimizer is then constructed and stepped
+        exactly as before).  utils.optim_rule.check_optim_options refuses what run.check_args refuses, for callers that build the
+        namespace themselves; there is no CPU twin of the flat path."""
+        from utils.optim_rule import check_optim_options
+        self._optim_options = wd, spec, ema = check_optim_options(self.args, flat_path=self.device.type == 'cuda')
+        self._optim_active = wd > 0.0 or spec.active or ema > 0.0
+        self._ema = ema > 0.0
+        if self._optim_active and self.rank == 0:
+            print(f"optimizer: AdamW weight_decay={wd:g} lr_schedule={spec.kind}"
+                  + (f",warmup={spec.warmup}" if spec.active else "") + (f",min={spec.min_lr:g}" if spec.kind == 'cosine' else "")
+                  + f" ema={ema:g}")
+
+    @contextlib.contextmanager
+    def _averaged_weights(self):
+        """--ema: inside the block the model holds the averaged weights (FlatAdam.swap_ema: one in-place exchange of the two flat
+        buffers), after it the live ones again, bit for bit.  BatchNorm running statistics stay the live ones
+        (torch.optim.swa_utils' default).  Without --ema the block runs as it stands."""
+        if not self._ema:
+            yield
+            return
+        self.optimizer.swap_ema()
+        try:
+            yield
+        finally:
+            self.optimizer.swap_ema()
 
     def _load_data(self):
         self.train_data, self.train_loader = data_provider(self.args, flag="train")
@@ -374,7 +419,7 @@ class Experiment(object):
 
     def _optimizer_step(self):
         """The tail of an optimizer step, eager or captured (IGN/exp/experiment_classification.py:335-341): all-reduce, clipped Adam,
-        clamp, zero_grad."""
+        clamp, the EMA launch under --ema, zero_grad."""
         a = self.args
         max_norm = a.gradient_clip if a.gradient_clip > 0 else None
         if self.bucket is not None:
@@ -387,6 +432,8 @@ class Experiment(object):
             self.optimizer.step()
         if a.pos_weight:
             self.model.step()
+        if self._ema:
+            self.optimizer.ema_update()           # after the clamp: an average of clamped values stays inside the constraint
         if self.bucket is not None:
             self.bucket.zero_grad()
         else:
@@ -448,7 +495,8 @@ class Experiment(object):
         from ign_hip.graph import GraphedTrainStep
         a = self.args
         beta = float(compute_beta(epoch, a.train_epochs, a.beta_schedule)) if a.model == 'InterpGN' else 0.0
-        lr = float(self.optimizer.param_groups[0]['lr'])
+        # with --lr_schedule the learning rate is read on the device (hp_dev): it is no kernel argument and no part of the key
+        lr = None if self.optimizer.schedule.active else float(self.optimizer.param_groups[0]['lr'])
         if not self.optimizer.capturable:          # the step count moves to the device so that a captured launch sequence stays valid
             self.optimizer.make_capturable()
 
@@ -496,9 +544,9 @@ class Experiment(object):
             if graphed is None or graphed[0] != key:
                 graphed = self._graphed = (key, {})
             if kind not in graphed[1]:
-                # beta and lr are kernel ARGUMENTS: a new value needs a new capture.  This batch runs eagerly (which also performs
-                # every first-call initialisation outside the capture); the capture that follows records the launch sequence
-                # without executing it, so the parameter trajectory is exactly the eager one
+                # beta and (without --lr_schedule) lr are kernel ARGUMENTS: a new value needs a new capture.  This batch runs eagerly
+                # (which also performs every first-call initialisation outside the capture); the capture that follows records the
+                # launch sequence without executing it, so the parameter trajectory is exactly the eager one
                 losses.append(fn(*inputs).clone())
                 graphed[1][kind] = GraphedTrainStep(fn, inputs, warmup=0)
                 continue
@@ -525,27 +573,33 @@ class Experiment(object):
                 # BatchNorm running statistics are per rank (each rank saw its own shards); the model that is validated,
                 # early-stopped on and checkpointed is rank 0's, so every rank evaluates THAT one ...
                 self._sync_buffers(0)
-            val_loss, val_acc = self._val_metrics()
-            if self.distributed:
-                # ... and the stopping decision is taken from one (val_loss, val_acc) pair: ranks that disagreed by one
-                # flipped argmax would leave the epoch loop at different times and dead-lock in the next all-reduce
-                t = torch.tensor([val_loss, 0.0 if val_acc is None else val_acc], dtype=torch.float64, device=self.device)
-                dist.broadcast(t, src=0)
-                val_loss, val_acc = float(t[0]), (None if val_acc is None else float(t[1]))
-            remain = (time.time() - t_start) * (a.train_epochs - epoch) / (epoch + 1)
-            if (epoch + 1) % a.log_interval == 0 and self.rank == 0:
-                acc = "" if val_acc is None else f" | Val Acc {val_acc:.4f}"
-                print(f"Epoch {epoch + 1}/{a.train_epochs} | Train Loss {train_loss:.4f} | Val Loss {val_loss:.4f}{acc} | "
-                      f"Time Rem {convert_to_hms(remain)}")
-            if a.lr_decay:
-                self.scheduler.step()
-            if epoch >= a.min_epochs:
-                score = val_loss if val_acc is None else -val_acc        # early stopping on -val_accuracy; no accuracy: val loss
-                if self.rank == 0:
-                    early_stopping(score, self.model, self.checkpoint_dir)
-                else:                                           # same decision on every rank, only rank 0 writes
-                    early_stopping.save_checkpoint = lambda *_: None
-                    early_stopping(score, self.model, self.checkpoint_dir)
+            # --ema: validation, early stopping and checkpoint.pth see the averaged weights (every rank holds the same average of the
+            # same flat parameters); the live ones are back before the next training pass
+            with self._averaged_weights():
+                val_loss, val_acc = self._val_metrics()
+                if self.distributed:
+                    # ... and the stopping decision is taken from one (val_loss, val_acc) pair: ranks that disagreed by one
+                    # flipped argmax would leave the epoch loop at different times and dead-lock in the next all-reduce
+                    t = torch.tensor([val_loss, 0.0 if val_acc is None else val_acc], dtype=torch.float64, device=self.device)
+                    dist.broadcast(t, src=0)
+                    val_loss, val_acc = float(t[0]), (None if val_acc is None else float(t[1]))
+                remain = (time.time() - t_start) * (a.train_epochs - epoch) / (epoch + 1)
+                if (epoch + 1) % a.log_interval == 0 and self.rank == 0:
+                    acc = "" if val_acc is None else f" | Val Acc {val_acc:.4f}"
+                    lr = ""
+                    if self._optim_active and self.optimizer.schedule.active:       # the last update's, from the host rule
+                        lr = f" | LR {self.optimizer.lr_at(train_step // a.gradient_accumulation_steps):.3g}"
+                    print(f"Epoch {epoch + 1}/{a.train_epochs} | Train Loss {train_loss:.4f} | Val Loss {val_loss:.4f}{acc} | "
+                          f"Time Rem {convert_to_hms(remain)}{lr}")
+                if a.lr_decay:
+                    self.scheduler.step()
+                if epoch >= a.min_epochs:
+                    score = val_loss if val_acc is None else -val_acc    # early stopping on -val_accuracy; no accuracy: val loss
+                    if self.rank == 0:
+                        early_stopping(score, self.model, self.checkpoint_dir)
+                    else:                                       # same decision on every rank, only rank 0 writes
+                        early_stopping.save_checkpoint = lambda *_: None
+                        early_stopping(score, self.model, self.checkpoint_dir)
             self.epoch_stop = epoch
             if early_stopping.early_stop:
                 if self.rank == 0:

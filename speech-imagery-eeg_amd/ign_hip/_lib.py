@@ -72,6 +72,10 @@ SIGNATURES = {
     "ign_adam_step_clip_dev": (ci, [vp, vp, vp, vp, ll, cf, cf, cf, cf, vp, vp, vp, vp]),
     "ign_scale_flat": (ci, [vp, ll, vp, vp]),
     "ign_gather_flat_acc": (ci, [vp, vp, vp, ci, vp, vp]),
+    "ign_sched_lr": (cf, [ci, cd, ci, cd, ll, ll]),
+    "ign_adamw_step_dev": (ci, [vp, vp, vp, vp, ll, cf, cf, cf, cf, vp, ci, cd, ci, cd, ll, cd, vp, vp, vp, vp]),
+    "ign_ema_update": (ci, [vp, vp, ll, vp, vp]),
+    "ign_swap_flat": (ci, [vp, vp, ll, vp]),
     "ign_conv1_sumsq_workspace_bytes": (sz, [ci, ci, ci]),
     "ign_conv1_sumsq_fwd": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]),
     "ign_conv1_sumsq_bwd": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]),

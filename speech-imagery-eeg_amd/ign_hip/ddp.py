@@ -193,12 +193,30 @@ class FlatAdam(torch.optim.Optimizer):
     checkpoints are unaffected.  Needs the bucket (its flat gradient is the kernel's input).  A torch Optimizer
     subclass, so lr schedulers (CosineAnnealingWarmRestarts at :137) attach to it; the learning rate is read from
     ``param_groups[0]['lr']`` at every step.
+
+    ``weight_decay`` > 0, a ``schedule`` (an ``--lr_schedule`` text or utils.optim_rule.LrSchedule) other than none, or ``ema`` > 0
+    select the AdamW path (``scheduled``): one ``ign_adamw_step_dev`` launch pair per step, always in device-count form.  Its tick
+    kernel computes the step's learning rate (``param_groups[0]['lr']`` is the schedule's base) and EMA decay on the device and
+    leaves them in ``hp_dev`` = [bc1, bc2_sqrt, lr_t, d_t]; the decay applies to the parameters utils.optim_rule.decays names (a
+    byte per 64-float chunk, ``decay_mask``); ``ema_flat`` starts as a copy of ``flat_param`` and follows it by ``ema_update()``.
+    The step count of that path lives in ``step_dev`` alone: ``lr_at(step)`` is the pure host rule and reads nothing back.
+    With all three neutral (the default) this is the class as it was: the same entry points, the same host count.
     """
 
-    def __init__(self, bucket, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, capturable=False):
+    def __init__(self, bucket, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, capturable=False, weight_decay=0.0, schedule=None,
+                 total_steps=None, ema=0.0):
         ps = bucket.params
         if not ps[0].is_cuda:
             raise _lib.IgnError("FlatAdam runs on the GPU only")
+        from utils.optim_rule import parse_lr_schedule
+        self.weight_decay, self.schedule, self.ema = float(weight_decay), parse_lr_schedule(schedule), float(ema)
+        self.scheduled = self.weight_decay > 0.0 or self.schedule.active or self.ema > 0.0
+        if self.weight_decay < 0.0 or not 0.0 <= self.ema < 1.0:
+            raise ValueError(f"FlatAdam: weight_decay {weight_decay} must be >= 0 and ema {ema} in [0, 1)")
+        if self.schedule.kind == 'cosine' and total_steps is None:
+            raise ValueError("FlatAdam: a cosine schedule needs total_steps, the run's number of optimizer steps")
+        self.total_steps = int(total_steps or 0)
+        capturable = capturable or self.scheduled
         super().__init__(ps, dict(lr=lr, betas=betas, eps=eps))
         self.bucket, self.lr, self.betas, self.eps = bucket, lr, betas, eps
         self.step_count = 0
@@ -217,6 +235,41 @@ class FlatAdam(torch.optim.Optimizer):
         # step(max_norm): [gradient norm, clip coefficient] of the last clipped step, on the device (allocated at the first one)
         self.norm_dev = None
         self.last_grad_norm = None
+        self.hp_dev = self.decay_mask = self.ema_flat = None
+        if self.scheduled:
+            from utils.optim_rule import decay_mask
+            dev = self.flat_param.device
+            self.hp_dev = torch.zeros(4, device=dev, dtype=torch.float32)
+            self.bc_dev = self.hp_dev[:2]
+            if self.weight_decay > 0.0:
+                names = [k for k, p in bucket.module.named_parameters() if p.requires_grad]
+                self.decay_mask = torch.from_numpy(decay_mask(names, ps, bucket.offsets, self.flat_param.numel(),
+                                                              bucket.ALIGN)).to(dev)
+            if self.ema > 0.0:
+                self.ema_flat = self.flat_param.clone()
+
+    def lr_at(self, step):
+        """The learning rate optimizer step `step` = 1, 2, ... uses, in float64: the host statement of the rule the tick kernel
+        evaluates (utils.optim_rule.lr_at); reads nothing from the device."""
+        from utils.optim_rule import lr_at
+        return lr_at(self.schedule, self.param_groups[0]["lr"], self.total_steps, step)
+
+    def ema_update(self):
+        """ema_flat += (1 - d_t) * (flat_param - ema_flat) with the decay the last step's tick left in hp_dev: one launch, to be
+        made after whatever rewrites the parameters behind the optimizer (the --pos_weight clamp)."""
+        if self.ema_flat is None:
+            raise _lib.IgnError("FlatAdam.ema_update: constructed with ema = 0")
+        _lib.check(_lib.lib().ign_ema_update(_ptr(self.ema_flat), _ptr(self.flat_param), self.flat_param.numel(), _ptr(self.hp_dev),
+                                             _lib.stream()), "ign_ema_update")
+
+    def swap_ema(self):
+        """Exchange flat_param and ema_flat in place (one launch; no pointer changes, so parameter views and captured graphs stay
+        valid): the model then computes with the averaged weights, a second call puts the live ones back."""
+        if self.ema_flat is None:
+            raise _lib.IgnError("FlatAdam.swap_ema: constructed with ema = 0")
+        _lib.PARAM_GENERATION[0] += 1                # the parameters change behind autograd's back
+        _lib.check(_lib.lib().ign_swap_flat(_ptr(self.flat_param), _ptr(self.ema_flat), self.flat_param.numel(), _lib.stream()),
+                   "ign_swap_flat")
 
     def make_capturable(self):
         """Move the step count to the device (ign_adam_step_dev) so that the optimizer step can be captured into a hipGraph;
@@ -234,7 +287,7 @@ class FlatAdam(torch.optim.Optimizer):
         ``_clip`` Adam entry point reads every gradient times that coefficient (the gradients themselves are not rewritten)."""
         loss = closure() if closure is not None else None
         self.bucket.gather()
-        self.step_count += 1
+        self.step_count += not self.scheduled        # the host count of ign_adam_step; the AdamW path counts in step_dev alone
         _lib.PARAM_GENERATION[0] += 1                # the kernel rewrites the parameters through raw pointers
         clip = max_norm is not None and max_norm > 0
         if clip:
@@ -243,6 +296,15 @@ class FlatAdam(torch.optim.Optimizer):
                 self.last_grad_norm = self.norm_dev[0]
             self.bucket._norm_into(self.norm_dev, max_norm)
         g = self.param_groups[0]
+        if self.scheduled:
+            s = self.schedule
+            _lib.check(_lib.lib().ign_adamw_step_dev(
+                _ptr(self.flat_param), _ptr(self.bucket.flat_grad), _ptr(self.exp_avg), _ptr(self.exp_avg_sq), self.flat_param.numel(),
+                g["betas"][0], g["betas"][1], g["eps"], self.weight_decay,
+                None if self.decay_mask is None else _ptr(self.decay_mask), s.code, float(g["lr"]), s.warmup, s.min_lr,
+                self.total_steps, self.ema, _ptr(self.step_dev), _ptr(self.hp_dev),
+                ctypes.c_void_p(self.norm_dev.data_ptr() + 4) if clip else None, _lib.stream()), "ign_adamw_step_dev")
+            return loss
         entry = "ign_adam_step" + ("_clip" if clip else "") + ("_dev" if self.capturable else "")
         args = [_ptr(self.flat_param), _ptr(self.bucket.flat_grad), _ptr(self.exp_avg), _ptr(self.exp_avg_sq),
                 self.flat_param.numel(), g["lr"], g["betas"][0], g["betas"][1], g["eps"]]

@@ -34,6 +34,9 @@ Differences, all repairs of fork defects listed in SURVEY section 0:
     across the electrodes of the raw shards in front of all of that -- a common average reference, a montage or unmixing matrix
     computed offline, Euclidean alignment fitted on the training split -- as one exact-fp32 matrix-core launch in the prefetcher
     (numpy on the CPU item path); ``enc_in`` becomes the matrix's row count; the default ``none`` changes nothing;
+  * ``--weight_decay WD``, ``--lr_schedule none|constant[,warmup=W]|cosine[,warmup=W][,min=M]`` and ``--ema D`` turn the flat Adam into
+    AdamW with a per-optimizer-step schedule evaluated on the device and keep an exponential moving average of the weights that
+    validation, early stopping and ``checkpoint.pth`` use (GPU only; all three default to off: the reference's optimizer);
   * ``--task_name regression --data Monash`` is the reference's regression twin (exp/experiment_regression.py), with the
     repairs R1-R3 of DESIGN 2.3;
   * multi-GPU is one process per GPU: ``python -m torch.distributed.run --nproc-per-node N run.py ...``.
@@ -175,6 +178,20 @@ def build_parser():
     # experiment
     p.add_argument("--lr", type=float, default=5e-3)
     p.add_argument("--lr_decay", action="store_true")
+    p.add_argument("--weight_decay", type=float, default=0.0,
+                   help="decoupled weight decay as torch.optim.AdamW: p *= 1 - lr_t * WD in front of the Adam update, on the flat "
+                        "optimizer path (GPU).  Matrices and convolution kernels decay; biases, BatchNorm / LayerNorm parameters, the "
+                        "shapelet banks and the LTS thresholds do not.  0: plain Adam, as the reference")
+    p.add_argument("--lr_schedule", type=str, default='none', metavar="none|constant[,warmup=W]|cosine[,warmup=W][,min=M]",
+                   help="learning rate per OPTIMIZER STEP, computed on the device (one --hipgraph capture serves the run): linear "
+                        "warm-up base * s / W over the first W steps, then constant, or a cosine from --lr down to M at the run's "
+                        "last step (CosineAnnealingLR's closed form over train_epochs * batches // accumulation - W steps).  Not "
+                        "with --lr_decay.  none: the reference's behaviour")
+    p.add_argument("--ema", type=float, default=0.0, metavar="D",
+                   help="exponential moving average of the parameters, decay D in [0, 1) (e.g. 0.999; warmed up as "
+                        "min(D, (1 + s) / (10 + s))): validation, early stopping and checkpoint.pth use the averaged weights, "
+                        "training goes on with the live ones; BatchNorm running statistics are the live ones.  Not with "
+                        "--shapelet_project N.  0: off")
     p.add_argument("--gradient_accumulation_steps", type=int, default=1)
     p.add_argument("--gradient_clip", type=float, default=0)
     p.add_argument("--batch_size", type=int, default=64)
@@ -235,6 +252,8 @@ def check_args(args):
     from utils.eeg_spatial import parse_eeg_spatial
     if parse_eeg_spatial(getattr(args, 'eeg_spatial', None)).active and getattr(args, 'data', None) not in ('EEG', 'EEG3'):
         raise ValueError(f"--eeg_spatial acts on the electrodes of the raw CHISCO shards (--data EEG / EEG3), not --data {args.data}")
+    from utils.optim_rule import check_optim_options
+    check_optim_options(args, flat_path=torch.cuda.is_available())
 
 
 def _num_class_from_flags(args):
