@@ -196,6 +196,15 @@ int ign_shapelet_fwd_bank(const float* xn_bct, int G, const float* const* w_kcl,
  * served by a generic-step kernel; shapelets longer than 2048 positions are split over several blocks.  Rows up to
  * T ~ 40 000 fit the forward's LDS staging (160 KB per CU); beyond that both calls return IGN_E_TOOBIG.             */
 size_t ign_shapelet_bwd_workspace_bytes(int B, int C, int T, int K, int L, int stride, int mode);
+/* The launch plan ign_shapelet_bwd derives from the shape, for inspection (host code only, nothing is launched; no mode: every
+ * distance and gate shares the plan).  out receives IGN_SHAPELET_BWD_PLAN_FIELDS ints:
+ *   JJ (shapelet positions per lane), cpk (position chunks per shapelet), kb (shapelets per block), nkt (shapelet tiles),
+ *   threads (per block), tc (window positions staged per chunk), xs_len (floats of the staged x chunk), nbs (batch slices =
+ *   partials to reduce), njt (blocks per long strided shapelet), LDS bytes per block.
+ * Returns 0, IGN_E_ARG for bad dimensions or a null out, or the plan's refusal (IGN_E_TOOBIG: stride 1 and L > 4096, or more
+ * than 64 KB of LDS) -- the code ign_shapelet_bwd returns for the same shape; out is left untouched on an error.                */
+#define IGN_SHAPELET_BWD_PLAN_FIELDS 10
+int ign_shapelet_bwd_plan(int B, int C, int T, int K, int L, int stride, int* out);
 int ign_shapelet_bwd(const float* xn_bct, const float* w_kcl, const float* g_out, const float* p_out,
                      const float* dmin_out, int ld, int col0,
                      const int32_t* tstar, const float* zmu, const float* d_save,

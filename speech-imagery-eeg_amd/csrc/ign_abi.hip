@@ -364,6 +364,23 @@ extern "C" size_t ign_shapelet_bwd_workspace_bytes(int B, int C, int T, int K, i
     return (size_t)p.nbs * K * C * L * sizeof(float);
 }
 
+// Read-only view of the launch plan (host code, nothing is launched): the fields of BwdPlan in declaration order, then the
+// LDS bytes.  For the tests that pin which branch of the plan a shape reaches (tests/test_shapelet_bwd_plan_host.py).
+extern "C" int ign_shapelet_bwd_plan(int B, int C, int T, int K, int L, int stride, int* out) {
+    int rc;
+    if ((rc = check_dims("ign_shapelet_bwd_plan", B, C, T, K, L, stride))) return rc;
+    if (!out) { ign_set_error("ign_shapelet_bwd_plan: null argument"); return IGN_E_ARG; }
+    const int Tw = (T - L) / stride + 1;
+    BwdPlan p;
+    if ((rc = plan_bwd(B, C, T, K, L, Tw, stride, &p))) {
+        ign_set_error("ign_shapelet_bwd_plan: no launch plan for K=%d L=%d Tw=%d stride=%d", K, L, Tw, stride);
+        return rc;
+    }
+    const int f[IGN_SHAPELET_BWD_PLAN_FIELDS] = {p.JJ, p.cpk, p.kb, p.nkt, p.threads, p.tc, p.xs_len, p.nbs, p.njt, (int)p.lds};
+    for (int i = 0; i < IGN_SHAPELET_BWD_PLAN_FIELDS; ++i) out[i] = f[i];
+    return 0;
+}
+
 // validate + launch the backward kernel of one group (partials into `workspace`); *nbs_out = batch slices to reduce
 static int launch_bwd_group(const char* who, const float* xn_bct, const float* w_kcl, const float* g_out, const float* p_out,
                             const float* dmin_out, int ld, int col0, const int32_t* tstar, const float* zmu,

@@ -169,12 +169,12 @@ def test_shapelet_bm_groups_one_bank():
     (4, 122, 1000, 5, 100, 0),     # CHISCO shape, TT=15
     (3, 122, 1000, 5, 500, 0),     # TT=8, JJ=8 backward
     (3, 7, 1000, 10, 300, 0),      # two K-tiles of 5
-    (5, 3, 200, 7, 33, 0),         # K = 5 + 2 tiles, odd L (tail loop)
-    (2, 4, 1300, 3, 10, 0),        # Tw = 1291 > 1024: two passes, K = 2 + 1 tiles
+    (5, 3, 200, 7, 33, 0),         # forward tiles K = 5 + 2 (the backward plans one tile of 7), odd L (tail loop)
+    (2, 4, 1300, 3, 10, 0),        # Tw = 1291 > 1024: two passes, forward tiles K = 2 + 1
     (3, 5, 300, 4, 50, 1),         # MSE
     (3, 5, 300, 5, 50, 2),         # cosine
     (2, 122, 1000, 5, 200, 2),     # cosine, CHISCO shape
-    (3, 5, 300, 7, 33, 3),         # pearson, K = 5 + 2 tiles, odd L
+    (3, 5, 300, 7, 33, 3),         # pearson, forward tiles K = 5 + 2, odd L
     (2, 16, 1000, 5, 500, 3),      # pearson, long shapelets
     (3, 5, 120, 6, 3, 0),          # minimum shapelet length
     (2, 3, 50, 2, 50, 0),          # L == T: a single window
@@ -204,7 +204,7 @@ def test_shapelet_vs_oracle_random(B, C, T, K, L, mode):
 @pytest.mark.parametrize("B,C,T,K,L,mode", [
     (4, 122, 1000, 5, 100, 0),     # CHISCO row, TT=15
     (3, 122, 1000, 10, 500, 0),    # two K-tiles, JJ=8 backward
-    (5, 3, 200, 7, 33, 0),         # K = 5 + 2 tiles, odd L
+    (5, 3, 200, 7, 33, 0),         # forward tiles K = 5 + 2 (the backward plans one tile of 7), odd L
     (2, 4, 1300, 3, 10, 0),        # two passes per row: the soft-min statistics are merged across passes
     (3, 5, 300, 4, 50, 1),         # LTS over the MSE distance
     (3, 5, 300, 5, 50, 2),         # ... cosine
