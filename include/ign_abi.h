@@ -144,6 +144,27 @@ size_t ign_eeg_gram_ws_bytes(int B, int C, int T, int G);
 int ign_eeg_gram_nct(const float* x_nct, const int* gid, float* gram_gcc, int* count_g, float* ws, int B, int C, int T, int G,
                      void* stream);
 
+/* Zero-phase IIR stage behind the spatial filter and in front of the FIR / standardisation stages (csrc/ign_eeg_iir.hip; run.py
+ * --eeg_iir; ops.eeg_iir; the rule in numpy float64: utils/eeg_iir.py:iir_numpy): a cascade of ns second-order sections applied
+ * forward and backward along time to every (b,c) row -- scipy.signal.sosfiltfilt(sos, x, padtype='odd', padlen=P) -- for what FIR
+ * filters cannot do inside a trial: a 0.5 Hz high-pass, a 50 Hz notch 1-2 Hz wide.  x (B,C,T) fp32 raw, out (B,C,T) fp32,
+ * coef (ns,8) DOUBLE on the device, rows (b0, b1, b2, a1, a2, zi1, zi2, 0) with a0 = 1 (utils/eeg_iir.py:section_table), g0 the
+ * squared DC gain of the cascade.  Per row:
+ *   p = x[0];  u = double(x) - double(p);  ue = the odd extension of u by P samples on both sides (N = T + 2P)
+ *   section k, state (s1,s2):  y = b0*v + s1;  s1 = (b1*v - a1*y) + s2;  s2 = b2*v - a2*y
+ *   forward from the states zi_k * ue[0], then the same cascade over the reversed result from zi_k * (its first sample)
+ *   out[t] = float(back[P+t] + g0*p)
+ * All arithmetic between the load and the store is double.  One wave per row, the extended row staged as doubles in LDS
+ * (ign_eeg_iir_lds_bytes(); 0 for arguments the launcher refuses), 64 chunks whose start states come from a fixed six-step scan across
+ * the lanes (within 2e-11 of the row's scale of the sequential evaluation): no workspace, no atomics, two calls give the same bits,
+ * and a row's output does not depend on B, C or its position.  x is read inside [0,T) only.
+ * IGN_E_ARG: null x / coef / out, non-positive dimension, ns outside 1..IGN_EEG_IIR_MAX_SECTIONS, P < 0, P >= T.
+ * IGN_E_TOOBIG: T + 2P > IGN_EEG_IIR_MAX_ROW (64 KB of doubles), B*C beyond the launch grid.  Nothing is launched on an error.   */
+#define IGN_EEG_IIR_MAX_SECTIONS 8
+#define IGN_EEG_IIR_MAX_ROW      8192
+size_t ign_eeg_iir_lds_bytes(int T, int P);
+int ign_eeg_iir_nct(const float* x_nct, const double* coef, float* out_nct, int B, int C, int T, int ns, int P, double g0, void* stream);
+
 /* Shapelet transform of ONE length group: sliding-window distance + gate, never materialising (B,Tw,K,C,L).
  * Replaces IGN/model/Shapelet.py:60-84 (GATE_RBF) / :96-111 (GATE_LTS).   Tw = (T-L)/stride + 1.
  *   xn_bct   (B,C,T)    normalised input

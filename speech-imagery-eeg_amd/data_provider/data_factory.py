@@ -70,6 +70,10 @@ def data_provider(args, flag, bin_edges=None):
         spatial = parse_eeg_spatial(getattr(args, 'eeg_spatial', None))
         if spatial.active:                                              # the default reads nothing and passes nothing on
             extra['spatial'] = spatial
+        from utils.eeg_iir import parse_eeg_iir
+        iir = parse_eeg_iir(getattr(args, 'eeg_iir', None))
+        if iir.active:                                                  # likewise: the default designs nothing
+            extra['iir'] = iir
         data_set = Data(root_path=args.root_path, flag=flag, test_size=getattr(args, 'test_size', 0.2),
                         val_size=getattr(args, 'val_size', 0.1), raw=raw, **extra)
     else:
@@ -96,6 +100,8 @@ def data_provider(args, flag, bin_edges=None):
         loader.device_transform, loader.eeg_preprocess = 'eeg_preprocess', data_set.pre
     if stage is not None:
         loader.eeg_spatial = stage
+    if getattr(data_set, 'iir', None) is not None:                   # --eeg_iir: the resolved sections travel with the loader
+        loader.eeg_iir = data_set.iir
     return data_set, loader
 
 
@@ -103,7 +109,7 @@ def ordered_loader(loader):
     """An unshuffled, un-sharded loader over the data set of `loader` (a DataLoader, a TensorBatchLoader, or a DevicePrefetcher
     around either): batch i holds the data set's items i*batch_size ..., on every rank, so a sample's ordinal in the stream is
     its data set index -- what a pass that reports sample indices needs (utils/shapelet_project.py).  Same batch size, collate_fn
-    and device_transform / eeg_preprocess / eeg_spatial attributes; no sampler, drop_last=False.  A DataLoader draws its per-iteration seed
+    and device_transform / eeg_preprocess / eeg_spatial / eeg_iir attributes; no sampler, drop_last=False.  A DataLoader draws its per-iteration seed
     from a generator of its own, so iterating the result leaves torch's global RNG stream where it was."""
     from data_provider.device_prefetch import DevicePrefetcher, TensorBatchLoader
     if isinstance(loader, DevicePrefetcher):
@@ -115,7 +121,7 @@ def ordered_loader(loader):
                          drop_last=False, pin_memory=loader.pin_memory, collate_fn=loader.collate_fn, generator=torch.Generator())
     else:
         raise TypeError(f"ordered_loader: expected a DataLoader, TensorBatchLoader or DevicePrefetcher, got {type(loader).__name__}")
-    for attr in ('device_transform', 'eeg_preprocess', 'eeg_spatial'):
+    for attr in ('device_transform', 'eeg_preprocess', 'eeg_spatial', 'eeg_iir'):
         if hasattr(loader, attr):
             setattr(out, attr, getattr(loader, attr))
     return out

@@ -49,6 +49,45 @@ def spatial_raw_batch(W, inner):
     return transform
 
 
+def iir_stage_fn(stage):
+    """x (B,C,T) on the GPU -> ops.eeg_iir(x) for a resolved --eeg_iir stage (utils.eeg_iir.ResolvedIIR); the float64 section table
+    is uploaded once, with the first batch, as the FIR taps are once per loader."""
+    from ign_hip import ops
+    coef = {}
+
+    def run(x):
+        if x.device not in coef:
+            coef[x.device] = torch.from_numpy(stage.table).to(x.device)
+        return ops.eeg_iir(x.float(), coef[x.device], pad=stage.pad, g0=stage.g0)
+    return run
+
+
+def iir_post(stage):
+    """The stage as utils.eeg_spatial.fit_alignment's `post`: a GPU tensor goes through ops.eeg_iir, a host array through the float64
+    rule unrounded -- so the alignment is fitted on what the model will see."""
+    from utils.eeg_iir import iir_numpy
+    run = iir_stage_fn(stage)
+
+    def post(y):
+        if torch.is_tensor(y) and y.is_cuda:
+            return run(y)
+        return iir_numpy(y.numpy() if torch.is_tensor(y) else y, stage.table, stage.pad, stage.g0)
+    return post
+
+
+def iir_raw_batch(stage, inner):
+    """transform for raw loaders under --eeg_iir: `stage` the resolved sections, `inner` the transform that would run without the
+    stage (standardise_raw_batch, or preprocess_raw_batch's).  (X[B,C,T], y, third) -> inner on (the rows filtered forward and
+    backward along time (B,C,T), y, third): one more launch on the prefetch stream, behind the spatial stage (spatial_raw_batch wraps
+    this one) and in front of the others."""
+    run = iir_stage_fn(stage)
+
+    def transform(batch):
+        x, y, third = batch
+        return inner((run(x), y, third))
+    return transform
+
+
 class DevicePrefetcher:
     def __init__(self, loader, device, transform=None, depth=2):
         self.loader, self.device, self.transform, self.depth = loader, torch.device(device), transform, max(1, depth)

@@ -70,7 +70,7 @@ class EEGNpyDataset(Dataset):
     num_label_classes = 39
 
     def __init__(self, root_path, flag='train', label_map=None, test_size=0.2, val_size=0.1, mmap=True, raw=False,
-                 preprocess=None, target_channels=None, target_timepoints=None, spatial=None, **_):
+                 preprocess=None, target_channels=None, target_timepoints=None, spatial=None, iir=None, **_):
         self.raw = bool(raw)      # True: items are RAW (C,T) recordings; the batch is standardised on the GPU instead
         xp, yp = os.path.join(root_path, "X.npy"), os.path.join(root_path, "y.npy")
         if not (os.path.exists(xp) and os.path.exists(yp)):
@@ -90,10 +90,17 @@ class EEGNpyDataset(Dataset):
         self.spatial = None       # --eeg_spatial: one matrix per group across the electrodes, in front of everything (utils/eeg_spatial.py)
         if spatial is not None:
             self._init_spatial(spatial, root_path, len(y), notice=print if flag == 'train' else None)
+        self.iir = None           # --eeg_iir: zero-phase second-order sections along time, behind the spatial stage (utils/eeg_iir.py)
+        if iir is not None:
+            from utils.eeg_iir import parse_eeg_iir, resolve_iir
+            if parse_eeg_iir(iir).active:
+                self.iir = resolve_iir(iir, self.seq_len)            # rows keep their shape: enc_in / seq_len are untouched
         self.pre = None           # --eeg_preprocess: filter / decimate / fit in front of the standardisation (utils/eeg_filter.py)
         if preprocess is not None:
             from utils.eeg_filter import parse_eeg_preprocess, resolve
             spec = parse_eeg_preprocess(preprocess)
+            if spec.active and self.iir is not None and spec.sfreq != self.iir.spec.sfreq:
+                raise ValueError(f"--eeg_iir: sfreq={self.iir.spec.sfreq:g} Hz, but --eeg_preprocess names sfreq={spec.sfreq:g} Hz")
             if spec.active:
                 # the models are built for what the items become: Tout time steps of Cout channels
                 self.pre = resolve(spec, self.enc_in, self.seq_len, target_channels, target_timepoints,
@@ -148,6 +155,8 @@ class EEGNpyDataset(Dataset):
         if self.spatial is not None:                  # the stage's fp32 restatement, then the rules below on its output
             from utils.eeg_spatial import spatial_numpy
             x = spatial_numpy(x, self.spatial.matrix_of(int(self.group[j])), dtype=np.float32)
+        if self.iir is not None:                      # the float64 rule, rounded to fp32 once as the kernel's store does
+            x = self.iir.apply(x)
         if self.pre is not None:  # (Tv, Cout): collate_fn(max_len=seq_len) pads the time axis and builds the mask
             from utils.eeg_filter import filterbank_numpy
             p = self.pre

@@ -24,7 +24,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from data_provider.data_factory import data_provider
-from data_provider.device_prefetch import DevicePrefetcher, preprocess_raw_batch, spatial_raw_batch, standardise_raw_batch
+from data_provider.device_prefetch import (DevicePrefetcher, iir_post, iir_raw_batch, preprocess_raw_batch, spatial_raw_batch,
+                                           standardise_raw_batch)
 from ign_hip import ddp as ign_ddp
 from ign_hip import ops as ign_ops
 from ign_hip.ddp import FlatAdam, FlatParamBucket
@@ -132,6 +133,8 @@ class Experiment(object):
             os.makedirs(self.checkpoint_dir, exist_ok=True)
             if getattr(self.train_data, 'spatial', None) is not None:     # the record of what each virtual channel is
                 self.train_data.spatial.save(self.checkpoint_dir)
+            if getattr(self.train_data, 'iir', None) is not None:         # eeg_iir.json: the resolved spec and its sections
+                self.train_data.iir.save(self.checkpoint_dir)
         self.loss_fn = nn.CrossEntropyLoss()
         self.epoch_stop = 0
         print(f"Experiment: model={args.model} dnn={getattr(args, 'dnn_type', None)} device={self.device} "
@@ -295,7 +298,9 @@ class Experiment(object):
                 batches = DevicePrefetcher(batches, self.device)
         else:
             batches = self.train_data.raw_batches(self.args.batch_size)
-        W = fit_alignment(batches, stage.W0, stage.groups, stage.spec.rtol, notice=print if self.rank == 0 else None)
+        iir = getattr(self.train_data, 'iir', None)      # --eeg_iir: the Gram of the filtered rows, what the model will see
+        W = fit_alignment(batches, stage.W0, stage.groups, stage.spec.rtol, notice=print if self.rank == 0 else None,
+                          post=None if iir is None else iir_post(iir))
         for d in (self.train_data, self.val_data, self.test_data):
             d.spatial.W, d.spatial.fitted = W, True
         if self.rank == 0:
@@ -312,6 +317,9 @@ class Experiment(object):
         transform = standardise_raw_batch if kind == 'standardise_raw' else None
         if kind == 'eeg_preprocess':                    # --eeg_preprocess: filter, decimate, fit, then the same standardisation
             transform = preprocess_raw_batch(loader.eeg_preprocess, self.device)
+        iir = getattr(loader, 'eeg_iir', None)
+        if iir is not None and transform is not None:    # --eeg_iir: one launch in front of either, behind the spatial stage
+            transform = iir_raw_batch(iir, transform)
         stage = getattr(loader, 'eeg_spatial', None)
         if stage is not None and transform is not None:  # --eeg_spatial: one launch in front of either
             transform = spatial_raw_batch(torch.from_numpy(stage.W).to(self.device), transform)

@@ -178,6 +178,8 @@ SIGNATURES = {
     "ign_eeg_spatial_nct": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]),
     "ign_eeg_gram_ws_bytes": (sz, [ci, ci, ci, ci]),
     "ign_eeg_gram_nct": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
+    "ign_eeg_iir_lds_bytes": (sz, [ci, ci]),
+    "ign_eeg_iir_nct": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, cd, vp]),
 }
 
 

@@ -283,6 +283,31 @@ def eeg_gram(x_nct, gid=None, groups=1, *, out=None):
     return gram, count
 
 
+IIR_TABLE_COLUMNS = 8     # b0 b1 b2 a1 a2 zi1 zi2 0: one row of the section table ign_eeg_iir_nct reads
+
+
+def eeg_iir(x_nct, coef, *, pad, g0, out=None):
+    """Raw (B,C,T) recordings -> (B,C,T) float32 on the GPU, every row filtered forward and backward along time by a cascade of
+    second-order sections (ign_eeg_iir_nct; the rule, in float64, is utils/eeg_iir.py:iir_numpy -- scipy's sosfiltfilt with an odd
+    extension of `pad` samples): coef (ns,8) FLOAT64 on the GPU, rows (b0, b1, b2, a1, a2, zi1, zi2, 0), and g0 the squared DC gain,
+    both from utils.eeg_iir.section_table.  The recurrence runs in float64 on the device; only the output is rounded.  The output
+    keeps the input's layout, so standardise_nct_to_btc / eeg_filterbank run on it unchanged.  `out`: write into this tensor instead
+    of a new one.  A non-contiguous x is copied.  Nothing of the call is a host value that a graph replay would freeze."""
+    name = "eeg_iir"
+    _need_gpu(name, x_nct)
+    if not torch.is_tensor(coef) or not coef.is_cuda or coef.dtype != torch.float64 or coef.dim() != 2 or coef.shape[1] != IIR_TABLE_COLUMNS:
+        what = f"{coef.dtype} {tuple(coef.shape)} on {coef.device}" if torch.is_tensor(coef) else type(coef).__name__
+        raise _lib.IgnError(f"{name}: coef must be a float64 tensor of shape (ns,8) on the GPU, got {what}")
+    if x_nct.dim() != 3:
+        raise _lib.IgnError(f"{name}: expected x (B,C,T), got {tuple(x_nct.shape)}")
+    x, table = x_nct.contiguous(), coef.contiguous()
+    B, C, T = x.shape
+    y = _spatial_out(name, out, (B, C, T), torch.float32, x.device)
+    _lib.check(_lib.lib().ign_eeg_iir_nct(_ptr(x), _ptr(table), _ptr(y), B, C, T, int(table.shape[0]), int(pad), float(g0),
+                                          _stream()), "ign_eeg_iir_nct")
+    return y
+
+
 def augment(x, seed, *, lengths=None, shift=0.0, scale=0.0, noise=0.0, channel_drop=0.0, time_mask=0.0):
     """Training augmentation of a contiguous fp32 (B,T,C) batch on the GPU -> a new tensor (ign_augment_btc; the rule is
     csrc/ign_augment.h, restated in utils/augment.py): a circular shift by up to `shift` * length, a per-channel gain in

@@ -34,6 +34,10 @@ Differences, all repairs of fork defects listed in SURVEY section 0:
     across the electrodes of the raw shards in front of all of that -- a common average reference, a montage or unmixing matrix
     computed offline, Euclidean alignment fitted on the training split -- as one exact-fp32 matrix-core launch in the prefetcher
     (numpy on the CPU item path); ``enc_in`` becomes the matrix's row count; the default ``none`` changes nothing;
+  * ``--eeg_iir hp=0.5,lp=100,order=4,notch=50`` (``--data EEG`` / ``EEG3``; any subset) filters every row forward and backward
+    along time with Butterworth and notch second-order sections (scipy's ``sosfiltfilt``, float64 recurrence) between
+    ``--eeg_spatial`` and ``--eeg_preprocess``: drift and mains removal, which FIR taps cannot do inside a trial; shapes are kept;
+    the default ``none`` changes nothing;
   * ``--weight_decay WD``, ``--lr_schedule none|constant[,warmup=W]|cosine[,warmup=W][,min=M]`` and ``--ema D`` turn the flat Adam into
     AdamW with a per-optimizer-step schedule evaluated on the device and keep an exponential moving average of the weights that
     validation, early stopping and ``checkpoint.pth`` use (GPU only; all three default to off: the reference's optimizer);
@@ -175,6 +179,15 @@ def build_parser():
                         "align . matrix . ref; the models see Cs virtual channels.  Subjects come from the optional <root>/subject.npy "
                         "(n,) integer ids; without it all trials are one group.  What was applied is written as eeg_spatial.npz beside "
                         "the checkpoint")
+    p.add_argument("--eeg_iir", type=str, default='none',
+                   help="--data EEG / EEG3: a zero-phase IIR stage along time on every row of the raw shards, behind --eeg_spatial and in "
+                        "front of --eeg_preprocess and the standardisation, one launch on the device (float64 recurrence): none, or a "
+                        "comma list of hp=F and lp=F (Butterworth high-pass / low-pass edges in Hz), order=N (1..8, default 4, of hp "
+                        "and of lp each), notch=F[+F...] (notch centres in Hz), q=Q (default 30: each notch is F/Q Hz wide), sfreq=F "
+                        "(default 500; must equal --eeg_preprocess's) and pad=P (samples of odd extension on both sides; default "
+                        "scipy's 3 * (2 * sections + 1 - first-order sections)).  Sections run hp, lp, notches, forward then backward "
+                        "(scipy.signal.sosfiltfilt); at most 8 sections; shapes do not change.  What was applied is written as "
+                        "eeg_iir.json beside the checkpoint")
     # experiment
     p.add_argument("--lr", type=float, default=5e-3)
     p.add_argument("--lr_decay", action="store_true")
@@ -252,6 +265,13 @@ def check_args(args):
     from utils.eeg_spatial import parse_eeg_spatial
     if parse_eeg_spatial(getattr(args, 'eeg_spatial', None)).active and getattr(args, 'data', None) not in ('EEG', 'EEG3'):
         raise ValueError(f"--eeg_spatial acts on the electrodes of the raw CHISCO shards (--data EEG / EEG3), not --data {args.data}")
+    from utils.eeg_iir import parse_eeg_iir
+    iir = parse_eeg_iir(getattr(args, 'eeg_iir', None))
+    if iir.active and getattr(args, 'data', None) not in ('EEG', 'EEG3'):
+        raise ValueError(f"--eeg_iir filters the rows of the raw CHISCO shards (--data EEG / EEG3), not --data {args.data}")
+    pre = parse_eeg_preprocess(getattr(args, 'eeg_preprocess', None))
+    if iir.active and pre.active and pre.sfreq != iir.sfreq:
+        raise ValueError(f"--eeg_iir: sfreq={iir.sfreq:g} Hz, but --eeg_preprocess names sfreq={pre.sfreq:g} Hz")
     from utils.optim_rule import check_optim_options
     check_optim_options(args, flat_path=torch.cuda.is_available())
 

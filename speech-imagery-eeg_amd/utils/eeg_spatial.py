@@ -193,8 +193,9 @@ def inverse_root(R, rtol):
     return 0.5 * (A + A.T)                            # symmetric bit for bit
 
 
-def _batch_gram(x, gid, W0, groups):
-    """one raw batch through the stage with W0, then the Gram rule -> (gram (G, C, C), count (G,)) as float64 / int64 numpy, and T"""
+def _batch_gram(x, gid, W0, groups, post=None):
+    """one raw batch through the stage with W0, then `post` if given, then the Gram rule -> (gram (G, C, C), count (G,)) as float64 /
+    int64 numpy, and T"""
     try:
         import torch
     except ImportError:                                                                   # numpy batches need no torch
@@ -205,23 +206,29 @@ def _batch_gram(x, gid, W0, groups):
         if gid is not None:
             gid = gid.to(device=x.device, dtype=torch.int32)
         y = ops.eeg_spatial(x.float(), w, gid if w.shape[0] > 1 else None)
+        if post is not None:
+            y = post(y)
         gram, count = ops.eeg_gram(y, gid, groups)
         return gram.double().cpu().numpy(), count.cpu().numpy().astype(np.int64), int(x.shape[-1])
     if torch is not None and torch.is_tensor(x):
         x = x.numpy()
         gid = None if gid is None else gid.numpy()
     y = spatial_numpy(x, W0, gid if np.shape(W0)[0] > 1 else None)
+    if post is not None:
+        y = post(y)
     gram, count = gram_numpy(y, gid, groups)
     return gram, count, int(np.shape(x)[-1])
 
 
-def fit_alignment(batches, W0, groups, rtol=1e-6, notice=print, return_info=False):
+def fit_alignment(batches, W0, groups, rtol=1e-6, notice=print, return_info=False, post=None):
     """Euclidean alignment over one ordered pass: `batches` yields raw (X (B, Cin, T), y, gid (B,) or None) -- device tensors go
     through ops.eeg_spatial and ops.eeg_gram, host tensors and arrays through the two numpy forms in float64.  W0 (G0, Cs, Cin)
     float64 with G0 in (1, groups).  The Grams and counts of all batches are summed in float64; R_g = gram_g / (count_g * T);
     A_g = inverse_root(R_g, rtol); W_g = A_g . W0_g, rounded to fp32 once -> W (groups, Cs, Cin) float32.  A group without a training
     trial takes the pooled matrix (from the sum of all groups' Grams), with one notice.  Deterministic: the same batches give the same
-    bits on every rank.  return_info: also a dict with the float64 W, R (G, Cs, Cs), counts and the list of empty groups."""
+    bits on every rank.  return_info: also a dict with the float64 W, R (G, Cs, Cs), counts and the list of empty groups.
+    `post`: a shape-keeping callable applied to W0 . x before the Gram, on both branches (--eeg_iir: the covariance of what the model
+    will see, not of drift and the mains line); None: nothing runs in between."""
     W0 = np.asarray(W0, dtype=np.float64)
     W0 = W0[None] if W0.ndim == 2 else W0
     G = int(groups)
@@ -231,7 +238,7 @@ def fit_alignment(batches, W0, groups, rtol=1e-6, notice=print, return_info=Fals
     gram, count, T = np.zeros((G, Cs, Cs)), np.zeros(G, dtype=np.int64), None
     for batch in batches:
         x, gid = batch[0], batch[2] if len(batch) > 2 else None
-        gb, cb, Tb = _batch_gram(x, gid if G > 1 else None, W0, G)      # the device path rounds W0 to fp32, the host path does not
+        gb, cb, Tb = _batch_gram(x, gid if G > 1 else None, W0, G, post)    # the device path rounds W0 to fp32, the host path does not
         if T is not None and Tb != T:
             raise ValueError(f"fit_alignment: trials of {Tb} and of {T} samples in one pass")
         T = Tb
