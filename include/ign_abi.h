@@ -165,6 +165,28 @@ int ign_eeg_gram_nct(const float* x_nct, const int* gid, float* gram_gcc, int* c
 size_t ign_eeg_iir_lds_bytes(int T, int P);
 int ign_eeg_iir_nct(const float* x_nct, const double* coef, float* out_nct, int B, int C, int T, int ns, int P, double g0, void* stream);
 
+/* Rational resampling stage behind the IIR stage and in front of the FIR / standardisation stages (csrc/ign_eeg_resample.hip; run.py
+ * --eeg_resample; ops.eeg_resample; the rule in numpy float64: utils/eeg_resample.py:resample_numpy): every (b,c) row goes from Tin to
+ * Tout = ceil(Tin*up/down) samples through the polyphase Kaiser-windowed low-pass that scipy.signal.resample_poly designs.
+ * x (B,C,Tin) fp32 raw, out (B,C,Tout) fp32, up/down in lowest terms, tab (up,Lp) fp32 on the device: tab[r][i] = h[r + i*up] of the
+ * 2*hl+1 taps h (DC gain up), zero past the last tap, Lp = ceil((2*hl+1)/up) (utils/eeg_resample.py:design_taps, phase_table).  Per row:
+ *   p = x[0];  u = x - p;  ue = u extended by R = Lp samples on both sides: mirrored about the end samples (IGN_EDGE_REFLECT) or zeros
+ *   (IGN_EDGE_ZERO: out - p is scipy.signal.resample_poly(u, up, down))
+ *   n in [0,Tout):  a = n*down + hl;  khi = a div up;  r = a mod up
+ *   out[n] = p + sum_{i<Lp} tab[r][i] * ue[khi - i]        one fmaf chain, i ascending
+ * The pivot p re-enters with gain exactly 1, not with the phase's DC gain sum_i tab[r][i] (which differs from 1 by up to 1.4e-4 at
+ * 64/125 and would print a ripple of the recording's offset onto the signal): a constant row gives p bit for bit.
+ * One workgroup per row; the extended row and the table (row stride Lp|1) are staged in LDS (ign_eeg_resample_lds_bytes(); 0 for
+ * arguments the launcher refuses).  One launch, no workspace, no atomics, two calls give the same bits, a row's output does not depend
+ * on B, C or its position; x is read inside [0,Tin) only and every element of out is written.
+ * IGN_E_ARG: null x / tab / out, non-positive dimension, up/down not in lowest terms, Lp != ceil((2*hl+1)/up),
+ * Tout != ceil(Tin*up/down), unknown edge, reflect with R >= Tin.  IGN_E_TOOBIG: up*Lp > IGN_EEG_RESAMPLE_MAX_TABLE, a row plus table
+ * over 64 KB of LDS, B*C beyond the launch grid.  Nothing is launched on an error.                                                     */
+#define IGN_EEG_RESAMPLE_MAX_TABLE 8192
+size_t ign_eeg_resample_lds_bytes(int Tin, int up, int Lp);
+int ign_eeg_resample_nct(const float* x_nct, const float* tab, float* out_nct, int B, int C, int Tin, int Tout, int up, int down, int hl,
+                         int Lp, int edge, void* stream);
+
 /* Shapelet transform of ONE length group: sliding-window distance + gate, never materialising (B,Tw,K,C,L).
  * Replaces IGN/model/Shapelet.py:60-84 (GATE_RBF) / :96-111 (GATE_LTS).   Tw = (T-L)/stride + 1.
  *   xn_bct   (B,C,T)    normalised input

@@ -74,6 +74,10 @@ def data_provider(args, flag, bin_edges=None):
         iir = parse_eeg_iir(getattr(args, 'eeg_iir', None))
         if iir.active:                                                  # likewise: the default designs nothing
             extra['iir'] = iir
+        from utils.eeg_resample import parse_eeg_resample
+        rs = parse_eeg_resample(getattr(args, 'eeg_resample', None), notice=print if flag == 'train' else None)
+        if rs.active:                                                   # likewise; a rate equal to sfreq is no stage either
+            extra['resample'] = rs
         data_set = Data(root_path=args.root_path, flag=flag, test_size=getattr(args, 'test_size', 0.2),
                         val_size=getattr(args, 'val_size', 0.1), raw=raw, **extra)
     else:
@@ -102,6 +106,8 @@ def data_provider(args, flag, bin_edges=None):
         loader.eeg_spatial = stage
     if getattr(data_set, 'iir', None) is not None:                   # --eeg_iir: the resolved sections travel with the loader
         loader.eeg_iir = data_set.iir
+    if getattr(data_set, 'resample', None) is not None:              # --eeg_resample: the resolved ratio and its table likewise
+        loader.eeg_resample = data_set.resample
     return data_set, loader
 
 
@@ -109,7 +115,7 @@ def ordered_loader(loader):
     """An unshuffled, un-sharded loader over the data set of `loader` (a DataLoader, a TensorBatchLoader, or a DevicePrefetcher
     around either): batch i holds the data set's items i*batch_size ..., on every rank, so a sample's ordinal in the stream is
     its data set index -- what a pass that reports sample indices needs (utils/shapelet_project.py).  Same batch size, collate_fn
-    and device_transform / eeg_preprocess / eeg_spatial / eeg_iir attributes; no sampler, drop_last=False.  A DataLoader draws its per-iteration seed
+    and device_transform / eeg_preprocess / eeg_spatial / eeg_iir / eeg_resample attributes; no sampler, drop_last=False.  A DataLoader draws its per-iteration seed
     from a generator of its own, so iterating the result leaves torch's global RNG stream where it was."""
     from data_provider.device_prefetch import DevicePrefetcher, TensorBatchLoader
     if isinstance(loader, DevicePrefetcher):
@@ -121,7 +127,7 @@ def ordered_loader(loader):
                          drop_last=False, pin_memory=loader.pin_memory, collate_fn=loader.collate_fn, generator=torch.Generator())
     else:
         raise TypeError(f"ordered_loader: expected a DataLoader, TensorBatchLoader or DevicePrefetcher, got {type(loader).__name__}")
-    for attr in ('device_transform', 'eeg_preprocess', 'eeg_spatial', 'eeg_iir'):
+    for attr in ('device_transform', 'eeg_preprocess', 'eeg_spatial', 'eeg_iir', 'eeg_resample'):
         if hasattr(loader, attr):
             setattr(out, attr, getattr(loader, attr))
     return out

@@ -88,6 +88,23 @@ def iir_raw_batch(stage, inner):
     return transform
 
 
+def resample_raw_batch(stage, inner):
+    """transform for raw loaders under --eeg_resample: `stage` the resolved ratio (utils.eeg_resample.ResolvedResample), `inner` the
+    transform that would run without the stage.  (X[B,C,Tin], y, third) -> inner on (the rows resampled to Tout samples (B,C,Tout), y,
+    third): one more launch on the prefetch stream, behind the IIR stage (iir_raw_batch wraps this one) and in front of the others.
+    The fp32 phase table is uploaded once, with the first batch."""
+    from ign_hip import ops
+    tab = {}
+
+    def transform(batch):
+        x, y, third = batch
+        if x.device not in tab:
+            tab[x.device] = torch.from_numpy(stage.tab).to(x.device)
+        x = ops.eeg_resample(x.float(), tab[x.device], up=stage.up, down=stage.down, half_len=stage.hl, edge=stage.edge)
+        return inner((x, y, third))
+    return transform
+
+
 class DevicePrefetcher:
     def __init__(self, loader, device, transform=None, depth=2):
         self.loader, self.device, self.transform, self.depth = loader, torch.device(device), transform, max(1, depth)

@@ -70,7 +70,7 @@ class EEGNpyDataset(Dataset):
     num_label_classes = 39
 
     def __init__(self, root_path, flag='train', label_map=None, test_size=0.2, val_size=0.1, mmap=True, raw=False,
-                 preprocess=None, target_channels=None, target_timepoints=None, spatial=None, iir=None, **_):
+                 preprocess=None, target_channels=None, target_timepoints=None, spatial=None, iir=None, resample=None, **_):
         self.raw = bool(raw)      # True: items are RAW (C,T) recordings; the batch is standardised on the GPU instead
         xp, yp = os.path.join(root_path, "X.npy"), os.path.join(root_path, "y.npy")
         if not (os.path.exists(xp) and os.path.exists(yp)):
@@ -95,11 +95,26 @@ class EEGNpyDataset(Dataset):
             from utils.eeg_iir import parse_eeg_iir, resolve_iir
             if parse_eeg_iir(iir).active:
                 self.iir = resolve_iir(iir, self.seq_len)            # rows keep their shape: enc_in / seq_len are untouched
+        self.resample = None      # --eeg_resample: a rational change of rate along time, behind the IIR stage (utils/eeg_resample.py)
+        if resample is not None:
+            from utils.eeg_resample import resolve_resample, same_rate
+            # the parser's notice (a rate equal to sfreq is no stage) is data_factory's to print: a spec arrives here already parsed
+            self.resample = resolve_resample(resample, self.seq_len)
+            if self.resample is not None:
+                if self.iir is not None and not same_rate(self.iir.spec.sfreq, self.resample.spec.sfreq):
+                    raise ValueError(f"--eeg_resample: the rows arrive at sfreq={self.resample.spec.sfreq:g} Hz, but --eeg_iir names "
+                                     f"sfreq={self.iir.spec.sfreq:g} Hz")
+                self.seq_len = self.resample.Tout                    # what the FIR stage and the models see; enc_in is untouched
         self.pre = None           # --eeg_preprocess: filter / decimate / fit in front of the standardisation (utils/eeg_filter.py)
         if preprocess is not None:
             from utils.eeg_filter import parse_eeg_preprocess, resolve
             spec = parse_eeg_preprocess(preprocess)
-            if spec.active and self.iir is not None and spec.sfreq != self.iir.spec.sfreq:
+            if self.resample is not None:
+                from utils.eeg_resample import same_rate
+                if spec.active and not same_rate(spec.sfreq, self.resample.spec.rate):
+                    raise ValueError(f"--eeg_resample: the rows leave at {self.resample.spec.rate:g} Hz, but --eeg_preprocess names "
+                                     f"sfreq={spec.sfreq:g} Hz")
+            elif spec.active and self.iir is not None and spec.sfreq != self.iir.spec.sfreq:
                 raise ValueError(f"--eeg_iir: sfreq={self.iir.spec.sfreq:g} Hz, but --eeg_preprocess names sfreq={spec.sfreq:g} Hz")
             if spec.active:
                 # the models are built for what the items become: Tout time steps of Cout channels
@@ -157,6 +172,8 @@ class EEGNpyDataset(Dataset):
             x = spatial_numpy(x, self.spatial.matrix_of(int(self.group[j])), dtype=np.float32)
         if self.iir is not None:                      # the float64 rule, rounded to fp32 once as the kernel's store does
             x = self.iir.apply(x)
+        if self.resample is not None:                 # the float64 rule on the fp32 taps, rounded to fp32 once: (C, Tout)
+            x = self.resample.apply(x)
         if self.pre is not None:  # (Tv, Cout): collate_fn(max_len=seq_len) pads the time axis and builds the mask
             from utils.eeg_filter import filterbank_numpy
             p = self.pre

@@ -24,8 +24,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from data_provider.data_factory import data_provider
-from data_provider.device_prefetch import (DevicePrefetcher, iir_post, iir_raw_batch, preprocess_raw_batch, spatial_raw_batch,
-                                           standardise_raw_batch)
+from data_provider.device_prefetch import (DevicePrefetcher, iir_post, iir_raw_batch, preprocess_raw_batch, resample_raw_batch,
+                                           spatial_raw_batch, standardise_raw_batch)
 from ign_hip import ddp as ign_ddp
 from ign_hip import ops as ign_ops
 from ign_hip.ddp import FlatAdam, FlatParamBucket
@@ -135,6 +135,8 @@ class Experiment(object):
                 self.train_data.spatial.save(self.checkpoint_dir)
             if getattr(self.train_data, 'iir', None) is not None:         # eeg_iir.json: the resolved spec and its sections
                 self.train_data.iir.save(self.checkpoint_dir)
+            if getattr(self.train_data, 'resample', None) is not None:    # eeg_resample.json: the rates, the ratio, the row lengths
+                self.train_data.resample.save(self.checkpoint_dir)
         self.loss_fn = nn.CrossEntropyLoss()
         self.epoch_stop = 0
         print(f"Experiment: model={args.model} dnn={getattr(args, 'dnn_type', None)} device={self.device} "
@@ -317,6 +319,9 @@ class Experiment(object):
         transform = standardise_raw_batch if kind == 'standardise_raw' else None
         if kind == 'eeg_preprocess':                    # --eeg_preprocess: filter, decimate, fit, then the same standardisation
             transform = preprocess_raw_batch(loader.eeg_preprocess, self.device)
+        rs = getattr(loader, 'eeg_resample', None)
+        if rs is not None and transform is not None:     # --eeg_resample: one launch in front of either, behind the IIR stage
+            transform = resample_raw_batch(rs, transform)
         iir = getattr(loader, 'eeg_iir', None)
         if iir is not None and transform is not None:    # --eeg_iir: one launch in front of either, behind the spatial stage
             transform = iir_raw_batch(iir, transform)

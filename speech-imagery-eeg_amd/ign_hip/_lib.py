@@ -180,6 +180,8 @@ SIGNATURES = {
     "ign_eeg_gram_nct": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
     "ign_eeg_iir_lds_bytes": (sz, [ci, ci]),
     "ign_eeg_iir_nct": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, cd, vp]),
+    "ign_eeg_resample_lds_bytes": (sz, [ci, ci, ci]),
+    "ign_eeg_resample_nct": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp]),
 }
 
 

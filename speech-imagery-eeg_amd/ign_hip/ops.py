@@ -308,6 +308,34 @@ def eeg_iir(x_nct, coef, *, pad, g0, out=None):
     return y
 
 
+def eeg_resample(x_nct, tab, *, up, down, half_len, edge="reflect", out=None):
+    """Raw (B,C,Tin) recordings -> (B,C,Tout) float32 on the GPU, Tout = ceil(Tin * up / down): every row resampled by the ratio
+    up/down (lowest terms) through the polyphase low-pass `tab` (ign_eeg_resample_nct; the rule, in float64, is
+    utils/eeg_resample.py:resample_numpy -- scipy's resample_poly on the row minus its first sample, which is added back with gain
+    exactly 1 so that the recording's offset never meets the phases' unequal DC gains).  tab (up,Lp) float32 on the GPU from
+    utils.eeg_resample.phase_table, `half_len` the hl of its 2 hl + 1 taps; `edge`: how the row is extended by Lp samples, 'reflect'
+    (numpy pad 'reflect') or 'zero'.  The output keeps the input's layout, so standardise_nct_to_btc / eeg_filterbank run on it
+    unchanged.  `out`: write into this tensor instead of a new one.  A non-contiguous x is copied."""
+    name = "eeg_resample"
+    _need_gpu(name, x_nct, tab)
+    if edge not in ("reflect", "zero"):
+        raise _lib.IgnError(f"{name}: edge={edge!r} is neither 'reflect' nor 'zero'")
+    if x_nct.dim() != 3 or tab.dim() != 2:
+        raise _lib.IgnError(f"{name}: expected x (B,C,Tin) and tab (up,Lp), got {tuple(x_nct.shape)} and {tuple(tab.shape)}")
+    up, down, hl = int(up), int(down), int(half_len)
+    if up < 1 or down < 1:
+        raise _lib.IgnError(f"{name}: up/down = {up}/{down} is not a positive ratio")
+    if tab.shape[0] != up:
+        raise _lib.IgnError(f"{name}: tab {tuple(tab.shape)} does not hold up={up} phases")
+    x, table = x_nct.contiguous(), tab.contiguous()
+    B, C, Tin = x.shape
+    Tout = -(-Tin * up // down)
+    y = _spatial_out(name, out, (B, C, Tout), torch.float32, x.device)
+    _lib.check(_lib.lib().ign_eeg_resample_nct(_ptr(x), _ptr(table), _ptr(y), B, C, Tin, Tout, up, down, hl, int(table.shape[1]),
+                                               EDGE_REFLECT if edge == "reflect" else EDGE_ZERO, _stream()), "ign_eeg_resample_nct")
+    return y
+
+
 def augment(x, seed, *, lengths=None, shift=0.0, scale=0.0, noise=0.0, channel_drop=0.0, time_mask=0.0):
     """Training augmentation of a contiguous fp32 (B,T,C) batch on the GPU -> a new tensor (ign_augment_btc; the rule is
     csrc/ign_augment.h, restated in utils/augment.py): a circular shift by up to `shift` * length, a per-channel gain in

@@ -38,6 +38,10 @@ Differences, all repairs of fork defects listed in SURVEY section 0:
     along time with Butterworth and notch second-order sections (scipy's ``sosfiltfilt``, float64 recurrence) between
     ``--eeg_spatial`` and ``--eeg_preprocess``: drift and mains removal, which FIR taps cannot do inside a trial; shapes are kept;
     the default ``none`` changes nothing;
+  * ``--eeg_resample rate=256`` (``--data EEG`` / ``EEG3``; or ``ratio=64/125``) changes the rate of every row by the exact fraction
+    ``rate / sfreq`` with a polyphase Kaiser-windowed low-pass (scipy's ``resample_poly``) between ``--eeg_iir`` and
+    ``--eeg_preprocess``: 500 -> 256 Hz, which ``decimate=Q`` cannot express; ``seq_len`` becomes ``ceil(T * up / down)``,
+    ``--eeg_iir`` names the rate in front of it and ``--eeg_preprocess`` the rate behind it; the default ``none`` changes nothing;
   * ``--weight_decay WD``, ``--lr_schedule none|constant[,warmup=W]|cosine[,warmup=W][,min=M]`` and ``--ema D`` turn the flat Adam into
     AdamW with a per-optimizer-step schedule evaluated on the device and keep an exponential moving average of the weights that
     validation, early stopping and ``checkpoint.pth`` use (GPU only; all three default to off: the reference's optimizer);
@@ -188,6 +192,15 @@ def build_parser():
                         "scipy's 3 * (2 * sections + 1 - first-order sections)).  Sections run hp, lp, notches, forward then backward "
                         "(scipy.signal.sosfiltfilt); at most 8 sections; shapes do not change.  What was applied is written as "
                         "eeg_iir.json beside the checkpoint")
+    p.add_argument("--eeg_resample", type=str, default='none',
+                   help="--data EEG / EEG3: a rational change of the sampling rate along time on every row of the raw shards, behind "
+                        "--eeg_iir and in front of --eeg_preprocess and the standardisation, one launch on the device: none, or a "
+                        "comma list of rate=F (the output rate in Hz) or ratio=P/Q in its place, sfreq=F (the input rate, default 500; "
+                        "--eeg_iir must name it, --eeg_preprocess must name the output rate), half=H (1..32, default 10: the low-pass "
+                        "reaches H * max(up, down) samples of the up-sampled grid to each side), beta=B (of its Kaiser window, default "
+                        "5.0) and edge=reflect|zero (default reflect).  up/down is the exact fraction rate/sfreq (256/500 = 64/125); "
+                        "rows of T samples leave with ceil(T * up / down); the filter is scipy.signal.resample_poly's, applied to "
+                        "the row minus its first sample.  What was applied is written as eeg_resample.json beside the checkpoint")
     # experiment
     p.add_argument("--lr", type=float, default=5e-3)
     p.add_argument("--lr_decay", action="store_true")
@@ -270,7 +283,16 @@ def check_args(args):
     if iir.active and getattr(args, 'data', None) not in ('EEG', 'EEG3'):
         raise ValueError(f"--eeg_iir filters the rows of the raw CHISCO shards (--data EEG / EEG3), not --data {args.data}")
     pre = parse_eeg_preprocess(getattr(args, 'eeg_preprocess', None))
-    if iir.active and pre.active and pre.sfreq != iir.sfreq:
+    from utils.eeg_resample import parse_eeg_resample, same_rate
+    rs = parse_eeg_resample(getattr(args, 'eeg_resample', None))
+    if rs.active:                                        # the rate changes between the two: each names the one it sees
+        if getattr(args, 'data', None) not in ('EEG', 'EEG3'):
+            raise ValueError(f"--eeg_resample resamples the rows of the raw CHISCO shards (--data EEG / EEG3), not --data {args.data}")
+        if iir.active and not same_rate(iir.sfreq, rs.sfreq):
+            raise ValueError(f"--eeg_resample: the rows arrive at sfreq={rs.sfreq:g} Hz, but --eeg_iir names sfreq={iir.sfreq:g} Hz")
+        if pre.active and not same_rate(pre.sfreq, rs.rate):
+            raise ValueError(f"--eeg_resample: the rows leave at {rs.rate:g} Hz, but --eeg_preprocess names sfreq={pre.sfreq:g} Hz")
+    elif iir.active and pre.active and pre.sfreq != iir.sfreq:
         raise ValueError(f"--eeg_iir: sfreq={iir.sfreq:g} Hz, but --eeg_preprocess names sfreq={pre.sfreq:g} Hz")
     from utils.optim_rule import check_optim_options
     check_optim_options(args, flat_path=torch.cuda.is_available())
