@@ -62,24 +62,11 @@ def data_provider(args, flag, bin_edges=None):
     elif args.data in ('EEG', 'EEG3'):
         # on a GPU the items stay RAW and the batch is standardised + transposed on the device (device_prefetch.py)
         raw = bool(getattr(args, 'device_standardise', torch.cuda.is_available()))
-        from utils.eeg_filter import parse_eeg_preprocess
-        pre = parse_eeg_preprocess(getattr(args, 'eeg_preprocess', None))
-        extra = dict(preprocess=pre, target_channels=getattr(args, 'target_channels', None),
-                     target_timepoints=getattr(args, 'target_timepoints', None)) if pre.active else {}
-        from utils.eeg_spatial import parse_eeg_spatial
-        spatial = parse_eeg_spatial(getattr(args, 'eeg_spatial', None))
-        if spatial.active:                                              # the default reads nothing and passes nothing on
-            extra['spatial'] = spatial
-        from utils.eeg_iir import parse_eeg_iir
-        iir = parse_eeg_iir(getattr(args, 'eeg_iir', None))
-        if iir.active:                                                  # likewise: the default designs nothing
-            extra['iir'] = iir
-        from utils.eeg_resample import parse_eeg_resample
-        rs = parse_eeg_resample(getattr(args, 'eeg_resample', None), notice=print if flag == 'train' else None)
-        if rs.active:                                                   # likewise; a rate equal to sfreq is no stage either
-            extra['resample'] = rs
+        # the --eeg_* flags as one chain; its "a rate equal to sfreq is no stage" line is the train split's to print
+        from data_provider.eeg_chain import EEGChain
         data_set = Data(root_path=args.root_path, flag=flag, test_size=getattr(args, 'test_size', 0.2),
-                        val_size=getattr(args, 'val_size', 0.1), raw=raw, **extra)
+                        val_size=getattr(args, 'val_size', 0.1), raw=raw,
+                        chain=EEGChain.from_args(args, notice=print if flag == 'train' else None))
     else:
         data_set = Data(root_path=args.root_path, flag=flag)
 
@@ -89,7 +76,7 @@ def data_provider(args, flag, bin_edges=None):
         sampler = RankShardSampler(len(data_set), dist.get_rank(), dist.get_world_size(), shuffle,
                                    seed=max(0, getattr(args, 'seed', 0)))
     raw = bool(getattr(data_set, 'raw', False))
-    stage = getattr(data_set, 'spatial', None)                          # --eeg_spatial: the raw batch carries its group ids
+    stage = getattr(data_set, 'spatial', None)                          # an active --eeg_spatial: the raw batch carries its group ids
     if args.data == 'SYNTH' and args.num_workers == 0:
         # samples are rows of one in-memory tensor: a batch is one multi-threaded gather into a pinned buffer
         from data_provider.device_prefetch import TensorBatchLoader
@@ -99,15 +86,7 @@ def data_provider(args, flag, bin_edges=None):
                         num_workers=args.num_workers, drop_last=False, pin_memory=torch.cuda.is_available(),
                         collate_fn=(collate_raw if stage is None else collate_raw_group) if raw
                         else (lambda b: collate_fn(b, max_len=max_len)))
-    loader.device_transform = 'standardise_raw' if raw else None
-    if raw and getattr(data_set, 'pre', None) is not None:          # --eeg_preprocess: the resolved spec travels with the loader
-        loader.device_transform, loader.eeg_preprocess = 'eeg_preprocess', data_set.pre
-    if stage is not None:
-        loader.eeg_spatial = stage
-    if getattr(data_set, 'iir', None) is not None:                   # --eeg_iir: the resolved sections travel with the loader
-        loader.eeg_iir = data_set.iir
-    if getattr(data_set, 'resample', None) is not None:              # --eeg_resample: the resolved ratio and its table likewise
-        loader.eeg_resample = data_set.resample
+    loader.eeg_chain = data_set.chain if raw else None              # raw items: Experiment._prefetch builds the device transform from it
     return data_set, loader
 
 
@@ -115,7 +94,7 @@ def ordered_loader(loader):
     """An unshuffled, un-sharded loader over the data set of `loader` (a DataLoader, a TensorBatchLoader, or a DevicePrefetcher
     around either): batch i holds the data set's items i*batch_size ..., on every rank, so a sample's ordinal in the stream is
     its data set index -- what a pass that reports sample indices needs (utils/shapelet_project.py).  Same batch size, collate_fn
-    and device_transform / eeg_preprocess / eeg_spatial / eeg_iir / eeg_resample attributes; no sampler, drop_last=False.  A DataLoader draws its per-iteration seed
+    and eeg_chain attribute; no sampler, drop_last=False.  A DataLoader draws its per-iteration seed
     from a generator of its own, so iterating the result leaves torch's global RNG stream where it was."""
     from data_provider.device_prefetch import DevicePrefetcher, TensorBatchLoader
     if isinstance(loader, DevicePrefetcher):
@@ -127,9 +106,7 @@ def ordered_loader(loader):
                          drop_last=False, pin_memory=loader.pin_memory, collate_fn=loader.collate_fn, generator=torch.Generator())
     else:
         raise TypeError(f"ordered_loader: expected a DataLoader, TensorBatchLoader or DevicePrefetcher, got {type(loader).__name__}")
-    for attr in ('device_transform', 'eeg_preprocess', 'eeg_spatial', 'eeg_iir', 'eeg_resample'):
-        if hasattr(loader, attr):
-            setattr(out, attr, getattr(loader, attr))
+    out.eeg_chain = getattr(loader, 'eeg_chain', None)
     return out
 
 
@@ -149,5 +126,4 @@ def _regression_provider(args, flag, bin_edges):
     loader = DataLoader(data_set, batch_size=args.batch_size, shuffle=(shuffle and sampler is None), sampler=sampler,
                         num_workers=args.num_workers, drop_last=False, pin_memory=torch.cuda.is_available(),
                         collate_fn=functools.partial(collate_subsampled, max_len=data_set.max_seq_len, stride=data_set.stride))
-    loader.device_transform = None
     return data_set, loader

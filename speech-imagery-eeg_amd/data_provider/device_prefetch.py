@@ -5,8 +5,8 @@ per-item CPU normalisation in the DataLoader workers become the bottleneck (a 25
 over PCIe Gen5, and ~0.5 ms of CPU z-scoring per sample).  ``DevicePrefetcher`` wraps any DataLoader of the batch contract
 ``(X, y, mask)``: batch i+1 is pinned and copied on a side HIP stream while batch i trains; an optional ``transform`` runs
 on that stream too -- for the CHISCO shards the loader ships RAW (B,C,T) microvolt tensors and the per-sample
-standardisation + transpose happen on the GPU (``ops.standardise_nct_to_btc``; with ``--eeg_preprocess`` the filter, decimation
-and fitting in front of it too: ``ops.eeg_filterbank``, a one-band spec as the bank of one).  On a CPU device it is a pass-through.
+standardisation + transpose happen on the GPU (``ops.standardise_nct_to_btc``; under the ``--eeg_*`` flags behind their stages:
+the transform is then ``data_provider.eeg_chain.ResolvedChain.device_transform``).  On a CPU device it is a pass-through.
 """
 import torch
 
@@ -17,92 +17,6 @@ def standardise_raw_batch(batch):
     x, y, _ = batch
     xs = ops.standardise_nct_to_btc(x.float())
     return xs, y, torch.ones(xs.shape[0], xs.shape[1], device=xs.device, dtype=torch.bool)
-
-
-def preprocess_raw_batch(pre, device):
-    """transform for raw loaders under --eeg_preprocess, built once per loader: `pre` is the data set's resolved spec
-    (utils.eeg_filter.Resolved or ResolvedBank; one band is the bank of one); its taps go to the device here, once.
-    (X[B,Cin,Tin], y, None) -> (X[B,Tout,nb*Cout] filtered, decimated, fitted and standardised, band-major, y,
-    mask[B,Tout] = t < Tv)."""
-    from ign_hip import ops
-    taps = torch.as_tensor(pre.taps2d, dtype=torch.float32).to(device)
-    quad = None if pre.quad is None else torch.as_tensor(pre.quad, dtype=torch.float32).to(device)
-    kw = dict(decimate=pre.q, edge=pre.edge, channels=pre.Cout, timepoints=pre.Tout)
-
-    def transform(batch):
-        x, y, _ = batch
-        xs, mask = ops.eeg_filterbank(x.float(), taps, quad, **kw)
-        return xs, y, mask
-    return transform
-
-
-def spatial_raw_batch(W, inner):
-    """transform for raw loaders under --eeg_spatial: `W` (G,Cs,Cin) float32 on the device, `inner` the transform that would run
-    without the stage (standardise_raw_batch, or preprocess_raw_batch's).  (X[B,Cin,T], y, gid[B] int32) -> inner on
-    (W[gid[b]] . X[b] (B,Cs,T), y, None): one more launch on the prefetch stream, in front of the others."""
-    from ign_hip import ops
-    one_group = W.shape[0] == 1
-
-    def transform(batch):
-        x, y, gid = batch
-        return inner((ops.eeg_spatial(x.float(), W, None if one_group else gid), y, None))
-    return transform
-
-
-def iir_stage_fn(stage):
-    """x (B,C,T) on the GPU -> ops.eeg_iir(x) for a resolved --eeg_iir stage (utils.eeg_iir.ResolvedIIR); the float64 section table
-    is uploaded once, with the first batch, as the FIR taps are once per loader."""
-    from ign_hip import ops
-    coef = {}
-
-    def run(x):
-        if x.device not in coef:
-            coef[x.device] = torch.from_numpy(stage.table).to(x.device)
-        return ops.eeg_iir(x.float(), coef[x.device], pad=stage.pad, g0=stage.g0)
-    return run
-
-
-def iir_post(stage):
-    """The stage as utils.eeg_spatial.fit_alignment's `post`: a GPU tensor goes through ops.eeg_iir, a host array through the float64
-    rule unrounded -- so the alignment is fitted on what the model will see."""
-    from utils.eeg_iir import iir_numpy
-    run = iir_stage_fn(stage)
-
-    def post(y):
-        if torch.is_tensor(y) and y.is_cuda:
-            return run(y)
-        return iir_numpy(y.numpy() if torch.is_tensor(y) else y, stage.table, stage.pad, stage.g0)
-    return post
-
-
-def iir_raw_batch(stage, inner):
-    """transform for raw loaders under --eeg_iir: `stage` the resolved sections, `inner` the transform that would run without the
-    stage (standardise_raw_batch, or preprocess_raw_batch's).  (X[B,C,T], y, third) -> inner on (the rows filtered forward and
-    backward along time (B,C,T), y, third): one more launch on the prefetch stream, behind the spatial stage (spatial_raw_batch wraps
-    this one) and in front of the others."""
-    run = iir_stage_fn(stage)
-
-    def transform(batch):
-        x, y, third = batch
-        return inner((run(x), y, third))
-    return transform
-
-
-def resample_raw_batch(stage, inner):
-    """transform for raw loaders under --eeg_resample: `stage` the resolved ratio (utils.eeg_resample.ResolvedResample), `inner` the
-    transform that would run without the stage.  (X[B,C,Tin], y, third) -> inner on (the rows resampled to Tout samples (B,C,Tout), y,
-    third): one more launch on the prefetch stream, behind the IIR stage (iir_raw_batch wraps this one) and in front of the others.
-    The fp32 phase table is uploaded once, with the first batch."""
-    from ign_hip import ops
-    tab = {}
-
-    def transform(batch):
-        x, y, third = batch
-        if x.device not in tab:
-            tab[x.device] = torch.from_numpy(stage.tab).to(x.device)
-        x = ops.eeg_resample(x.float(), tab[x.device], up=stage.up, down=stage.down, half_len=stage.hl, edge=stage.edge)
-        return inner((x, y, third))
-    return transform
 
 
 class DevicePrefetcher:
@@ -169,7 +83,6 @@ class TensorBatchLoader:
     def __init__(self, dataset, batch_size, shuffle=False, sampler=None, pin_memory=True):
         self.dataset, self.batch_size, self.shuffle, self.sampler = dataset, int(batch_size), bool(shuffle), sampler
         self.pin = bool(pin_memory) and torch.cuda.is_available()
-        self.device_transform = None
 
     def __len__(self):
         n = len(self.sampler) if self.sampler is not None else len(self.dataset)

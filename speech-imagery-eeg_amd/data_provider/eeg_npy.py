@@ -24,6 +24,8 @@ import numpy as np
 import torch
 from torch.utils.data import Dataset
 
+from data_provider.eeg_chain import EEGChain
+
 
 def per_sample_standardise(x_nct, eps=1e-8):
     """Normalizer('per_sample_std') of IGN/data_factory/eeg.py:332-367: per sample and channel over time."""
@@ -70,7 +72,7 @@ class EEGNpyDataset(Dataset):
     num_label_classes = 39
 
     def __init__(self, root_path, flag='train', label_map=None, test_size=0.2, val_size=0.1, mmap=True, raw=False,
-                 preprocess=None, target_channels=None, target_timepoints=None, spatial=None, iir=None, resample=None, **_):
+                 chain=None, **_):
         self.raw = bool(raw)      # True: items are RAW (C,T) recordings; the batch is standardised on the GPU instead
         xp, yp = os.path.join(root_path, "X.npy"), os.path.join(root_path, "y.npy")
         if not (os.path.exists(xp) and os.path.exists(yp)):
@@ -85,69 +87,15 @@ class EEGNpyDataset(Dataset):
             y = np.asarray([label_map.get(int(v), -1) for v in y], dtype=np.int64)
             idx = idx[y[idx] >= 0]
         self.X, self.y, self.idx = X, y, idx
-        self.enc_in, self.seq_len = int(X.shape[1]), int(X.shape[2])
         self.num_classes = int(y.max()) + 1 if label_map is None else len(set(label_map.values()))
-        self.spatial = None       # --eeg_spatial: one matrix per group across the electrodes, in front of everything (utils/eeg_spatial.py)
-        if spatial is not None:
-            self._init_spatial(spatial, root_path, len(y), notice=print if flag == 'train' else None)
-        self.iir = None           # --eeg_iir: zero-phase second-order sections along time, behind the spatial stage (utils/eeg_iir.py)
-        if iir is not None:
-            from utils.eeg_iir import parse_eeg_iir, resolve_iir
-            if parse_eeg_iir(iir).active:
-                self.iir = resolve_iir(iir, self.seq_len)            # rows keep their shape: enc_in / seq_len are untouched
-        self.resample = None      # --eeg_resample: a rational change of rate along time, behind the IIR stage (utils/eeg_resample.py)
-        if resample is not None:
-            from utils.eeg_resample import resolve_resample, same_rate
-            # the parser's notice (a rate equal to sfreq is no stage) is data_factory's to print: a spec arrives here already parsed
-            self.resample = resolve_resample(resample, self.seq_len)
-            if self.resample is not None:
-                if self.iir is not None and not same_rate(self.iir.spec.sfreq, self.resample.spec.sfreq):
-                    raise ValueError(f"--eeg_resample: the rows arrive at sfreq={self.resample.spec.sfreq:g} Hz, but --eeg_iir names "
-                                     f"sfreq={self.iir.spec.sfreq:g} Hz")
-                self.seq_len = self.resample.Tout                    # what the FIR stage and the models see; enc_in is untouched
-        self.pre = None           # --eeg_preprocess: filter / decimate / fit in front of the standardisation (utils/eeg_filter.py)
-        if preprocess is not None:
-            from utils.eeg_filter import parse_eeg_preprocess, resolve
-            spec = parse_eeg_preprocess(preprocess)
-            if self.resample is not None:
-                from utils.eeg_resample import same_rate
-                if spec.active and not same_rate(spec.sfreq, self.resample.spec.rate):
-                    raise ValueError(f"--eeg_resample: the rows leave at {self.resample.spec.rate:g} Hz, but --eeg_preprocess names "
-                                     f"sfreq={spec.sfreq:g} Hz")
-            elif spec.active and self.iir is not None and spec.sfreq != self.iir.spec.sfreq:
-                raise ValueError(f"--eeg_iir: sfreq={self.iir.spec.sfreq:g} Hz, but --eeg_preprocess names sfreq={spec.sfreq:g} Hz")
-            if spec.active:
-                # the models are built for what the items become: Tout time steps of Cout channels
-                self.pre = resolve(spec, self.enc_in, self.seq_len, target_channels, target_timepoints,
-                                   notice=print if flag == 'train' else None)
-                # a bank has nb * Cout channels, band-major; one band is the bank of one
-                self.enc_in, self.seq_len = self.pre.channels, self.pre.Tout
-
-    def _init_spatial(self, spatial, root_path, n, notice):
-        """--eeg_spatial: compose W0, and -- when the stage needs groups (an alignment, or one matrix per group) -- read the optional
-        <root>/subject.npy (n,) and map its ids to dense 0..G-1 over the WHOLE file, sorted by id, before the split: every split sees
-        the same mapping.  self.group (n,) int32 and self.groups are kept; the models are built for Cs virtual channels."""
-        from utils.eeg_spatial import SpatialStage, compose, load_matrix, needs_groups, parse_eeg_spatial
-        spec = parse_eeg_spatial(spatial)
-        if not spec.active:
-            return
-        matrix = load_matrix(spec)
-        W0 = compose(spec, self.enc_in, matrix)
-        self.group, self.groups, labels = np.zeros(n, dtype=np.int32), 1, None
-        if needs_groups(spec, matrix):
-            sp = os.path.join(root_path, "subject.npy")
-            if os.path.exists(sp):
-                ids = np.load(sp, allow_pickle=False)
-                if ids.shape != (n,) or not np.issubdtype(ids.dtype, np.integer):
-                    raise ValueError(f"{sp}: expected {n} integer subject ids, got {ids.dtype} {ids.shape}")
-                labels, dense = np.unique(ids, return_inverse=True)
-                self.group, self.groups = dense.astype(np.int32).reshape(n), int(len(labels))
-            elif notice is not None:
-                notice(f"eeg_spatial: {sp} not found; all {n} trials are one group")
-        if W0.shape[0] > 1 and W0.shape[0] != self.groups:
-            raise ValueError(f"--eeg_spatial: the matrix holds {W0.shape[0]} groups, the shards {self.groups}")
-        self.spatial = SpatialStage(spec, W0, self.groups, labels)
-        self.enc_in = self.spatial.Cs
+        # chain: the parsed --eeg_* flags (eeg_chain.EEGChain; None: no stage), checked as the driver checks them, then resolved
+        chain = EEGChain() if chain is None else chain
+        chain.check('EEG')                                           # this class is --data EEG / EEG3
+        self.chain = chain.resolve(X.shape[1], X.shape[2], root_path, len(y), notice=print if flag == 'train' else None)
+        self.enc_in, self.seq_len = self.chain.shape                 # the models are built for what the items become
+        self.spatial, self.iir, self.resample, self.pre = (self.chain.stage(k) for k in ('spatial', 'iir', 'resample', 'preprocess'))
+        if self.spatial is not None:
+            self.group, self.groups = self.chain.group, self.spatial.groups
 
     def __len__(self):
         return len(self.idx)
@@ -164,22 +112,13 @@ class EEGNpyDataset(Dataset):
         x = np.asarray(self.X[j], dtype=np.float32)
         y = torch.tensor([self.y[j]], dtype=torch.int64)
         if self.raw:              # device pipeline: data_provider.device_prefetch does the rest on the batch
-            if self.spatial is not None:
-                return torch.from_numpy(np.ascontiguousarray(x)), y, int(self.group[j])
-            return torch.from_numpy(np.ascontiguousarray(x)), y
-        if self.spatial is not None:                  # the stage's fp32 restatement, then the rules below on its output
-            from utils.eeg_spatial import spatial_numpy
-            x = spatial_numpy(x, self.spatial.matrix_of(int(self.group[j])), dtype=np.float32)
-        if self.iir is not None:                      # the float64 rule, rounded to fp32 once as the kernel's store does
-            x = self.iir.apply(x)
-        if self.resample is not None:                 # the float64 rule on the fp32 taps, rounded to fp32 once: (C, Tout)
-            x = self.resample.apply(x)
+            item = torch.from_numpy(np.ascontiguousarray(x)), y
+            return item if self.spatial is None else item + (int(self.group[j]),)
+        g = int(self.group[j]) if self.spatial is not None else 0
+        for stage in self.chain.stages:                # the stages' numpy rules, in the chain's order
+            x = stage.apply_item(x, g)
         if self.pre is not None:  # (Tv, Cout): collate_fn(max_len=seq_len) pads the time axis and builds the mask
-            from utils.eeg_filter import filterbank_numpy
-            p = self.pre
-            quad = None if p.quad is None else p.quad.astype(np.float32)
-            return torch.from_numpy(filterbank_numpy(x, p.taps2d.astype(np.float32), quad, p.q, p.edge, p.Cout, p.Tout)
-                                    .astype(np.float32)), y
+            return torch.from_numpy(x), y
         return torch.from_numpy(per_sample_standardise(x).T.copy()), y
 
 

@@ -24,8 +24,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from data_provider.data_factory import data_provider
-from data_provider.device_prefetch import (DevicePrefetcher, iir_post, iir_raw_batch, preprocess_raw_batch, resample_raw_batch,
-                                           spatial_raw_batch, standardise_raw_batch)
+from data_provider.device_prefetch import DevicePrefetcher
 from ign_hip import ddp as ign_ddp
 from ign_hip import ops as ign_ops
 from ign_hip.ddp import FlatAdam, FlatParamBucket
@@ -131,12 +130,8 @@ class Experiment(object):
             args.epsilon, args.beta_schedule, args.distance_func, args.sbm_cls)
         if self.rank == 0:
             os.makedirs(self.checkpoint_dir, exist_ok=True)
-            if getattr(self.train_data, 'spatial', None) is not None:     # the record of what each virtual channel is
-                self.train_data.spatial.save(self.checkpoint_dir)
-            if getattr(self.train_data, 'iir', None) is not None:         # eeg_iir.json: the resolved spec and its sections
-                self.train_data.iir.save(self.checkpoint_dir)
-            if getattr(self.train_data, 'resample', None) is not None:    # eeg_resample.json: the rates, the ratio, the row lengths
-                self.train_data.resample.save(self.checkpoint_dir)
+            if getattr(self.train_data, 'chain', None) is not None:       # eeg_spatial.npz, eeg_iir.json, eeg_resample.json: what ran
+                self.train_data.chain.save(self.checkpoint_dir)
         self.loss_fn = nn.CrossEntropyLoss()
         self.epoch_stop = 0
         print(f"Experiment: model={args.model} dnn={getattr(args, 'dnn_type', None)} device={self.device} "
@@ -294,15 +289,14 @@ class Experiment(object):
             return
         from data_provider.data_factory import ordered_loader
         from utils.eeg_spatial import fit_alignment
-        if getattr(self.train_loader, 'device_transform', None) is not None:      # raw items: the loader's own batches
+        if getattr(self.train_loader, 'eeg_chain', None) is not None:             # raw items: the loader's own batches
             batches = ordered_loader(self.train_loader)
             if self.device.type == 'cuda':
                 batches = DevicePrefetcher(batches, self.device)
         else:
             batches = self.train_data.raw_batches(self.args.batch_size)
-        iir = getattr(self.train_data, 'iir', None)      # --eeg_iir: the Gram of the filtered rows, what the model will see
         W = fit_alignment(batches, stage.W0, stage.groups, stage.spec.rtol, notice=print if self.rank == 0 else None,
-                          post=None if iir is None else iir_post(iir))
+                          post=self.train_data.chain.alignment_post(self.device))     # --eeg_iir: the Gram of the filtered rows
         for d in (self.train_data, self.val_data, self.test_data):
             d.spatial.W, d.spatial.fitted = W, True
         if self.rank == 0:
@@ -315,22 +309,11 @@ class Experiment(object):
                 dist.broadcast(buf.data, src=src)
 
     def _prefetch(self, loader):
-        kind = getattr(loader, 'device_transform', None)
-        transform = standardise_raw_batch if kind == 'standardise_raw' else None
-        if kind == 'eeg_preprocess':                    # --eeg_preprocess: filter, decimate, fit, then the same standardisation
-            transform = preprocess_raw_batch(loader.eeg_preprocess, self.device)
-        rs = getattr(loader, 'eeg_resample', None)
-        if rs is not None and transform is not None:     # --eeg_resample: one launch in front of either, behind the IIR stage
-            transform = resample_raw_batch(rs, transform)
-        iir = getattr(loader, 'eeg_iir', None)
-        if iir is not None and transform is not None:    # --eeg_iir: one launch in front of either, behind the spatial stage
-            transform = iir_raw_batch(iir, transform)
-        stage = getattr(loader, 'eeg_spatial', None)
-        if stage is not None and transform is not None:  # --eeg_spatial: one launch in front of either
-            transform = spatial_raw_batch(torch.from_numpy(stage.W).to(self.device), transform)
-        if self.device.type != 'cuda' and transform is None:
-            return loader
-        return DevicePrefetcher(loader, self.device, transform=transform)
+        # raw CHISCO items carry their resolved --eeg_* chain; built here, after _fit_eeg_spatial: the transform reads the fitted matrices
+        chain = getattr(loader, 'eeg_chain', None)
+        if chain is None:
+            return loader if self.device.type != 'cuda' else DevicePrefetcher(loader, self.device)
+        return DevicePrefetcher(loader, self.device, transform=chain.device_transform(self.device))
 
     # ------------------------------------------------------------------------------------------------
     def _get_params_from_data(self):

@@ -42,6 +42,7 @@ Differences, all repairs of fork defects listed in SURVEY section 0:
     ``rate / sfreq`` with a polyphase Kaiser-windowed low-pass (scipy's ``resample_poly``) between ``--eeg_iir`` and
     ``--eeg_preprocess``: 500 -> 256 Hz, which ``decimate=Q`` cannot express; ``seq_len`` becomes ``ceil(T * up / down)``,
     ``--eeg_iir`` names the rate in front of it and ``--eeg_preprocess`` the rate behind it; the default ``none`` changes nothing;
+  * the ``--eeg_*`` stages run in one fixed order: spatial -> iir -> resample -> preprocess -> standardise (data_provider/eeg_chain.py);
   * ``--weight_decay WD``, ``--lr_schedule none|constant[,warmup=W]|cosine[,warmup=W][,min=M]`` and ``--ema D`` turn the flat Adam into
     AdamW with a per-optimizer-step schedule evaluated on the device and keep an exponential moving average of the weights that
     validation, early stopping and ``checkpoint.pth`` use (GPU only; all three default to off: the reference's optimizer);
@@ -272,28 +273,8 @@ def check_args(args):
     if parse_mix(getattr(args, 'mix', None)).active and getattr(args, 'task_name', 'classification') == 'regression':
         raise ValueError("--mix with --task_name regression: mixup / CutMix mix class labels through the cross-entropy tails; the "
                          "CRPS tails have no soft-label form")
-    from utils.eeg_filter import parse_eeg_preprocess
-    if parse_eeg_preprocess(getattr(args, 'eeg_preprocess', None)).active and getattr(args, 'data', None) not in ('EEG', 'EEG3'):
-        raise ValueError(f"--eeg_preprocess filters the raw CHISCO shards (--data EEG / EEG3), not --data {args.data}")
-    from utils.eeg_spatial import parse_eeg_spatial
-    if parse_eeg_spatial(getattr(args, 'eeg_spatial', None)).active and getattr(args, 'data', None) not in ('EEG', 'EEG3'):
-        raise ValueError(f"--eeg_spatial acts on the electrodes of the raw CHISCO shards (--data EEG / EEG3), not --data {args.data}")
-    from utils.eeg_iir import parse_eeg_iir
-    iir = parse_eeg_iir(getattr(args, 'eeg_iir', None))
-    if iir.active and getattr(args, 'data', None) not in ('EEG', 'EEG3'):
-        raise ValueError(f"--eeg_iir filters the rows of the raw CHISCO shards (--data EEG / EEG3), not --data {args.data}")
-    pre = parse_eeg_preprocess(getattr(args, 'eeg_preprocess', None))
-    from utils.eeg_resample import parse_eeg_resample, same_rate
-    rs = parse_eeg_resample(getattr(args, 'eeg_resample', None))
-    if rs.active:                                        # the rate changes between the two: each names the one it sees
-        if getattr(args, 'data', None) not in ('EEG', 'EEG3'):
-            raise ValueError(f"--eeg_resample resamples the rows of the raw CHISCO shards (--data EEG / EEG3), not --data {args.data}")
-        if iir.active and not same_rate(iir.sfreq, rs.sfreq):
-            raise ValueError(f"--eeg_resample: the rows arrive at sfreq={rs.sfreq:g} Hz, but --eeg_iir names sfreq={iir.sfreq:g} Hz")
-        if pre.active and not same_rate(pre.sfreq, rs.rate):
-            raise ValueError(f"--eeg_resample: the rows leave at {rs.rate:g} Hz, but --eeg_preprocess names sfreq={pre.sfreq:g} Hz")
-    elif iir.active and pre.active and pre.sfreq != iir.sfreq:
-        raise ValueError(f"--eeg_iir: sfreq={iir.sfreq:g} Hz, but --eeg_preprocess names sfreq={pre.sfreq:g} Hz")
+    from data_provider.eeg_chain import EEGChain
+    EEGChain.from_args(args).check(getattr(args, 'data', None))      # the --eeg_* flags: the data they need, the rates they name
     from utils.optim_rule import check_optim_options
     check_optim_options(args, flat_path=torch.cuda.is_available())
 

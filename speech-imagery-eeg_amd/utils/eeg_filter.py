@@ -9,7 +9,7 @@ the CPU loader path applies per item and what the tests compare the kernel again
 With ``h = firwin(20 q + 1, 1 / q, window='hamming')`` and zero extension, f is ``scipy.signal.decimate(x, q, ftype='fir',
 zero_phase=True)`` -- what the reference's loader runs (IGN/data_factory/eeg_processor.py:258-381).  In reflect mode with R > 0 the
 rule filters ``x - x[0]``: a constant is a fixed point of reflect-extended filtering up to the factor sum(h), and the
-standardisation removes it.  No scipy and no torch in this module.
+standardisation removes it.  No scipy in this module, and torch only where a stage's ``device_fn`` meets the device.
 
 A filter bank (``bank=LO:HI+LO:HI+...``, optionally ``envelope``) runs nb bands with one common tap count over the same extended row
 (``ign_eeg_filterbank_nct_to_btc`` / ``ops.eeg_filterbank``; here ``filterbank_numpy``):
@@ -26,6 +26,8 @@ import math
 from typing import NamedTuple, Optional
 
 import numpy as np
+
+from utils.flag_items import FlagItems
 
 MAX_TAPS, MAX_DECIMATE = 1023, 16                   # IGN_EEG_MAX_TAPS, IGN_EEG_MAX_DECIMATE
 MAX_BANDS = 8                                       # IGN_EEG_MAX_BANDS
@@ -49,6 +51,23 @@ class EEGPreprocessSpec(NamedTuple):
         return self.lo is not None or self.hi is not None or self.decimate > 1 or self.fit or self.bank is not None
 
 
+# The stage protocol of data_provider/eeg_chain.py, once for Resolved and ResolvedBank; the chain's last stage: its rules standardise too.
+def _apply_item(self, x, group):
+    """one item (Cin, Tin) -> (Tv, channels) float32: the rule in fp32 on the fp32 taps"""
+    quad = None if self.quad is None else self.quad.astype(np.float32)
+    return filterbank_numpy(x, self.taps2d.astype(np.float32), quad, self.q, self.edge, self.Cout, self.Tout).astype(np.float32)
+
+
+def _device_fn(self, device):
+    """x (B,Cin,Tin), gid -> (X[B,Tout,channels] filtered, decimated, fitted, standardised, band-major, mask = t < Tv); uploads the taps"""
+    import torch
+    from ign_hip import ops
+    taps = torch.as_tensor(self.taps2d, dtype=torch.float32).to(device)
+    quad = None if self.quad is None else torch.as_tensor(self.quad, dtype=torch.float32).to(device)
+    kw = dict(decimate=self.q, edge=self.edge, channels=self.Cout, timepoints=self.Tout)
+    return lambda x, gid: ops.eeg_filterbank(x.float(), taps, quad, **kw)
+
+
 class Resolved(NamedTuple):
     """A one-band spec resolved against one data set: ``resolve`` returns it; the fields are the arguments of
     ``ops.eeg_preprocess``.  The properties answer what a ResolvedBank answers, for the bank of one that it is."""
@@ -62,6 +81,8 @@ class Resolved(NamedTuple):
     quad = property(lambda self: None)
     channels = property(lambda self: self.Cout)
     taps2d = property(lambda self: self.taps[None], doc="the taps as a bank's (nb, M) = (1, M)")
+    name, apply_item, device_fn = 'preprocess', _apply_item, _device_fn
+    out_shape, save = (lambda self, C, T: (self.channels, self.Tout)), (lambda self, directory: None)     # no record file
 
 
 class ResolvedBank(NamedTuple):
@@ -78,6 +99,8 @@ class ResolvedBank(NamedTuple):
 
     channels = property(lambda self: len(self.bands) * self.Cout)
     taps2d = property(lambda self: self.taps)
+    name, apply_item, device_fn = 'preprocess', _apply_item, _device_fn
+    out_shape, save = (lambda self, C, T: (self.channels, self.Tout)), (lambda self, directory: None)     # no record file
 
 
 def bank_channel(res, index):
@@ -90,19 +113,10 @@ def bank_channel(res, index):
     return j, res.bands[j], c
 
 
-_KEYS = ('sfreq', 'band', 'bank', 'decimate', 'taps', 'edge', 'fit', 'envelope')
-_FLAGS = ('fit', 'envelope')
-_GRAMMAR = "sfreq=F, band=LO:HI, bank=LO:HI+LO:HI+..., decimate=Q, taps=M, edge=reflect|zero, fit, envelope"
-
-
-def _number(key, val):
-    try:
-        v = float(val)
-    except ValueError:
-        raise ValueError(f"--eeg_preprocess: {key}={val!r} is not a number") from None
-    if not math.isfinite(v):
-        raise ValueError(f"--eeg_preprocess: {key}={val!r} is not finite")
-    return v
+_ITEMS = FlagItems("--eeg_preprocess", "sfreq=F, band=LO:HI, bank=LO:HI+LO:HI+..., decimate=Q, taps=M, edge=reflect|zero, fit, envelope",
+                   ('sfreq', 'band', 'bank', 'decimate', 'taps', 'edge', 'fit', 'envelope'), bare=('fit', 'envelope'),
+                   need_value=False, expected=False)
+_number = _ITEMS.number
 
 
 def parse_eeg_preprocess(text):
@@ -114,18 +128,12 @@ def parse_eeg_preprocess(text):
     not with ``edge=zero``); ``band=LO:HI,envelope`` is a bank of one band.  Without either the spec is what it always was."""
     if isinstance(text, EEGPreprocessSpec):
         return text
-    text = '' if text is None else str(text).strip()
-    if text.lower() in ('', 'none'):
+    text = _ITEMS.clean(text)
+    if text is None:
         return EEGPreprocessSpec()
     got = {}
-    for item in text.split(','):
-        key, eq, val = item.partition('=')
-        key, val = key.strip(), val.strip()
-        if key not in _KEYS or (key in _FLAGS) == bool(eq):
-            raise ValueError(f"--eeg_preprocess: {item!r} is not one of {_GRAMMAR}")
-        if key in got:
-            raise ValueError(f"--eeg_preprocess: {key} given twice")
-        if key in _FLAGS:
+    for key, val in _ITEMS.items(text):
+        if key in _ITEMS.bare:
             got[key] = True
         elif key == 'edge':
             if val not in EDGES:

@@ -23,7 +23,7 @@ signal, out of the recurrence.  All arithmetic of the recurrence is float64, on 
 from float64 -- outside the project's 1e-4 budget before the model has run.  In float64 the order of evaluation stops mattering
 (the kernel's 64-chunk evaluation and this sequential one differ by ~1e-11 of the scale).
 
-No scipy and no torch in this module.
+No scipy in this module, and torch only where the stage's ``device_fn`` meets the device.
 """
 import json
 import math
@@ -31,6 +31,8 @@ import os
 from typing import NamedTuple, Optional
 
 import numpy as np
+
+from utils.flag_items import FlagItems
 
 MAX_SECTIONS = 8                                    # IGN_EEG_IIR_MAX_SECTIONS
 MAX_ROW = 8192                                      # IGN_EEG_IIR_MAX_ROW: T + 2 P samples staged as float64 in LDS
@@ -67,25 +69,8 @@ class EEGIIRSpec(NamedTuple):
         return ','.join(parts)
 
 
-_KEYS = ('hp', 'lp', 'order', 'notch', 'q', 'sfreq', 'pad')
 _GRAMMAR = "hp=F, lp=F, order=N, notch=F[+F...], q=Q, sfreq=F, pad=P"
-
-
-def _number(key, val):
-    try:
-        out = float(val)
-    except ValueError:
-        raise ValueError(f"--eeg_iir: {key}={val!r} is not a number; expected {_GRAMMAR}") from None
-    if not math.isfinite(out):
-        raise ValueError(f"--eeg_iir: {key}={val!r} is not finite; expected {_GRAMMAR}")
-    return out
-
-
-def _integer(key, val):
-    try:
-        return int(val)
-    except ValueError:
-        raise ValueError(f"--eeg_iir: {key}={val!r} is not an integer; expected {_GRAMMAR}") from None
+_ITEMS = FlagItems("--eeg_iir", _GRAMMAR, ('hp', 'lp', 'order', 'notch', 'q', 'sfreq', 'pad'))
 
 
 def parse_eeg_iir(text):
@@ -94,23 +79,17 @@ def parse_eeg_iir(text):
     without a filter, and more than MAX_SECTIONS sections in total raise ValueError."""
     if isinstance(text, EEGIIRSpec):
         return text
-    text = '' if text is None else str(text).strip()
-    if text.lower() in ('', 'none'):
+    text = _ITEMS.clean(text)
+    if text is None:
         return EEGIIRSpec()
     got = {}
-    for item in text.split(','):
-        key, eq, val = item.partition('=')
-        key, val = key.strip(), val.strip()
-        if key not in _KEYS or not eq or not val:
-            raise ValueError(f"--eeg_iir: {item!r} is not one of {_GRAMMAR}")
-        if key in got:
-            raise ValueError(f"--eeg_iir: {key} given twice; expected {_GRAMMAR}")
+    for key, val in _ITEMS.items(text):
         if key in ('order', 'pad'):
-            got[key] = _integer(key, val)
+            got[key] = _ITEMS.integer(key, val)
         elif key == 'notch':
-            got[key] = tuple(_number(key, v.strip()) for v in val.split('+'))
+            got[key] = tuple(_ITEMS.number(key, v.strip()) for v in val.split('+'))
         else:
-            got[key] = _number(key, val)
+            got[key] = _ITEMS.number(key, val)
     spec = EEGIIRSpec(**got)
     if spec.sfreq <= 0:
         raise ValueError(f"--eeg_iir: sfreq must be positive, got {spec.sfreq}; expected {_GRAMMAR}")
@@ -243,11 +222,22 @@ class ResolvedIIR(NamedTuple):
     pad: int
     g0: float
 
+    name = 'iir'                                    # the stage protocol of data_provider/eeg_chain.py: name and four methods
     ns = property(lambda self: int(self.sos.shape[0]))
 
     def apply(self, x):
         """the rule on host rows (..., T) -> float32"""
         return iir_numpy(x, self.table, self.pad, self.g0).astype(np.float32)
+
+    out_shape = lambda self, C, T: (C, T)
+    apply_item = lambda self, x, group: self.apply(x)
+
+    def device_fn(self, device):
+        """x (B,C,T), gid -> the rows filtered forward and backward (B,C,T), one launch; the float64 section table is uploaded now"""
+        import torch
+        from ign_hip import ops
+        coef = torch.from_numpy(self.table).to(device)
+        return lambda x, gid: ops.eeg_iir(x.float(), coef, pad=self.pad, g0=self.g0)
 
     def save(self, directory):
         """eeg_iir.json: the resolved spec and the section table."""

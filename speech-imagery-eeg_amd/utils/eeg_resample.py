@@ -26,7 +26,7 @@ recording's offset (2e4 uV) of about 3 uV onto tens of uV of signal, and a zero 
 at both ends; pivoted, the filter sees the signal alone, a constant row yields p exactly, and the float32 evaluation stays an order
 of magnitude closer to float64.
 
-No scipy and no torch in this module.
+No scipy in this module, and torch only where the stage's ``device_fn`` meets the device.
 """
 import json
 import math
@@ -35,6 +35,8 @@ from fractions import Fraction
 from typing import NamedTuple
 
 import numpy as np
+
+from utils.flag_items import FlagItems
 
 MAX_TABLE = 8192                                    # IGN_EEG_RESAMPLE_MAX_TABLE: up * Lp floats of phase table
 MAX_LDS_BYTES = 64 * 1024                           # the extended row plus the padded table, staged in LDS
@@ -68,8 +70,8 @@ class EEGResampleSpec(NamedTuple):
         return f"ratio={self.up}/{self.down},sfreq={self.sfreq!r},half={self.half},beta={self.beta!r},edge={self.edge}"
 
 
-_KEYS = ('rate', 'ratio', 'sfreq', 'half', 'beta', 'edge')
 _GRAMMAR = "rate=F or ratio=P/Q, sfreq=F, half=H, beta=B, edge=reflect|zero"
+_ITEMS = FlagItems("--eeg_resample", _GRAMMAR, ('rate', 'ratio', 'sfreq', 'half', 'beta', 'edge'))
 
 
 def _decimal(key, val):
@@ -81,13 +83,6 @@ def _decimal(key, val):
     if '/' in val:
         raise ValueError(f"--eeg_resample: {key}={val!r} is not a decimal number; expected {_GRAMMAR}")
     return out
-
-
-def _integer(key, val):
-    try:
-        return int(val)
-    except ValueError:
-        raise ValueError(f"--eeg_resample: {key}={val!r} is not an integer; expected {_GRAMMAR}") from None
 
 
 def phase_count(up, down, half):
@@ -105,19 +100,13 @@ def parse_eeg_resample(text, notice=None):
     equal to sfreq is no stage: the inactive spec, with one line to `notice`."""
     if isinstance(text, EEGResampleSpec):
         return text
-    text = '' if text is None else str(text).strip()
-    if text.lower() in ('', 'none'):
+    text = _ITEMS.clean(text)
+    if text is None:
         return EEGResampleSpec()
     got = {}
-    for item in text.split(','):
-        key, eq, val = item.partition('=')
-        key, val = key.strip(), val.strip()
-        if key not in _KEYS or not eq or not val:
-            raise ValueError(f"--eeg_resample: {item!r} is not one of {_GRAMMAR}")
-        if key in got:
-            raise ValueError(f"--eeg_resample: {key} given twice; expected {_GRAMMAR}")
+    for key, val in _ITEMS.items(text):
         if key == 'half':
-            got[key] = _integer(key, val)
+            got[key] = _ITEMS.integer(key, val)
         elif key == 'edge':
             if val not in EDGES:
                 raise ValueError(f"--eeg_resample: edge={val!r} is neither reflect nor zero; expected {_GRAMMAR}")
@@ -126,7 +115,7 @@ def parse_eeg_resample(text, notice=None):
             p, slash, q = val.partition('/')
             if not slash:
                 raise ValueError(f"--eeg_resample: ratio={val!r} is not P/Q; expected {_GRAMMAR}")
-            got[key] = (_integer(key, p.strip()), _integer(key, q.strip()))
+            got[key] = (_ITEMS.integer(key, p.strip()), _ITEMS.integer(key, q.strip()))
         else:
             got[key] = _decimal(key, val)
     if ('rate' in got) == ('ratio' in got):
@@ -211,6 +200,17 @@ class ResolvedResample(NamedTuple):
     def apply(self, x):
         """the rule on host rows (..., Tin) -> (..., Tout) float32: float64 arithmetic on the float32 taps, rounded once"""
         return resample_numpy(x, self.tab, self.up, self.down, self.hl, self.edge).astype(np.float32)
+
+    name = 'resample'                               # the stage protocol of data_provider/eeg_chain.py: name and four methods
+    out_shape = lambda self, C, T: (C, self.Tout)
+    apply_item = lambda self, x, group: self.apply(x)
+
+    def device_fn(self, device):
+        """x (B,C,Tin), gid -> the rows resampled (B,C,Tout), one launch; the fp32 phase table is uploaded now"""
+        import torch
+        from ign_hip import ops
+        tab = torch.from_numpy(self.tab).to(device)
+        return lambda x, gid: ops.eeg_resample(x.float(), tab, up=self.up, down=self.down, half_len=self.hl, edge=self.edge)
 
     def record(self):
         s = self.spec

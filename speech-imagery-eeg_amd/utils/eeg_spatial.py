@@ -22,13 +22,15 @@ The Gram rule (the covariance's numerator), on the stage's own output:
     xc = x - x[..., :1];  m[c] = (sum_t xc[c,t]) / T;  z = xc - m
     gram[g,i,j] = sum over b with gid[b] == g of sum_t z[b,i,t] * z[b,j,t];   count[g] = number of such b
 
-No scipy in this module; torch only where ``fit_alignment`` meets device tensors.
+No scipy in this module; torch only where ``fit_alignment`` and the stage's ``device_fn`` meet device tensors.
 """
 import math
 import os
 from typing import NamedTuple, Optional
 
 import numpy as np
+
+from utils.flag_items import FlagItems
 
 MAX_CHANNELS, MAX_GROUPS = 512, 64                  # IGN_EEG_SPATIAL_MAX_CHANNELS, IGN_EEG_SPATIAL_MAX_GROUPS
 FILE_NAME = "eeg_spatial.npz"
@@ -55,8 +57,8 @@ class EEGSpatialSpec(NamedTuple):
         return ','.join(parts)
 
 
-_KEYS = ('ref', 'matrix', 'align', 'rtol')
-_GRAMMAR = "ref=car, matrix=PATH.npy, align=euclid, rtol=R"
+_ITEMS = FlagItems("--eeg_spatial", "ref=car, matrix=PATH.npy, align=euclid, rtol=R", ('ref', 'matrix', 'align', 'rtol'),
+                   need_value=False, expected=False)
 
 
 def parse_eeg_spatial(text):
@@ -65,17 +67,11 @@ def parse_eeg_spatial(text):
     (0, 1) and a matrix file that does not exist raise ValueError."""
     if isinstance(text, EEGSpatialSpec):
         return text
-    text = '' if text is None else str(text).strip()
-    if text.lower() in ('', 'none'):
+    text = _ITEMS.clean(text)
+    if text is None:
         return EEGSpatialSpec()
     got = {}
-    for item in text.split(','):
-        key, eq, val = item.partition('=')
-        key, val = key.strip(), val.strip()
-        if key not in _KEYS or not eq:
-            raise ValueError(f"--eeg_spatial: {item!r} is not one of {_GRAMMAR}")
-        if key in got:
-            raise ValueError(f"--eeg_spatial: {key} given twice")
+    for key, val in _ITEMS.items(text):
         if key == 'ref':
             if val != 'car':
                 raise ValueError(f"--eeg_spatial: ref={val!r} is not car")
@@ -86,10 +82,7 @@ def parse_eeg_spatial(text):
             if not val or not os.path.isfile(val):
                 raise ValueError(f"--eeg_spatial: matrix={val!r}: no such file")
         else:
-            try:
-                val = float(val)
-            except ValueError:
-                raise ValueError(f"--eeg_spatial: rtol={val!r} is not a number") from None
+            val = _ITEMS.number(key, val, finite=False)
             if not (math.isfinite(val) and 0.0 < val < 1.0):
                 raise ValueError(f"--eeg_spatial: rtol={val} outside (0, 1)")
         got[key] = val
@@ -273,10 +266,22 @@ class SpatialStage:
         self.W = W0.astype(np.float32)
         self.fitted = False
 
+    name = 'spatial'                                # the stage protocol of data_provider/eeg_chain.py: name and four methods
     Cs = property(lambda self: int(self.W0.shape[1]))
 
     def matrix_of(self, g):
         return self.W[g if self.W.shape[0] > 1 else 0]
+
+    out_shape = lambda self, C, T: (self.Cs, T)
+    apply_item = lambda self, x, group: spatial_numpy(x, self.matrix_of(group), dtype=np.float32)
+
+    def device_fn(self, device):
+        """x (B,Cin,T), gid (B,) int32 -> W[gid[b]] . x[b] (B,Cs,T), one launch; W is read and uploaded now: the fitted one, if fitted"""
+        import torch
+        from ign_hip import ops
+        W = torch.from_numpy(self.W).to(device)
+        one_group = W.shape[0] == 1
+        return lambda x, gid: ops.eeg_spatial(x.float(), W, None if one_group else gid)
 
     def save(self, directory):
         """eeg_spatial.npz: the record of what each virtual channel is."""

@@ -83,6 +83,7 @@ def step_cpu_emulation():
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import eeg_spatial_cases as K
     s = K.S()
+    from data_provider.eeg_chain import EEGChain
     from data_provider.eeg_npy import EEGNpyDataset, per_sample_standardise
     from utils.eeg_filter import filterbank_numpy
     res = dict(margin=2.0, apply_cases={}, identity_inexact={}, loader_path={})
@@ -96,7 +97,7 @@ def step_cpu_emulation():
         X, _, _ = K.write_shards(d)
         for spec in ("ref=car", "ref=car,align=euclid"):
             for pre in (None, "band=8:30,taps=41"):
-                ds = EEGNpyDataset(d, flag="train", spatial=spec, **({} if pre is None else dict(preprocess=pre)))
+                ds = EEGNpyDataset(d, flag="train", chain=EEGChain(spatial=spec, preprocess=pre))
                 if "align" in spec:
                     ds.spatial.W = s.fit_alignment(ds.raw_batches(8), ds.spatial.W0, 3, 1e-6, notice=None)
                 worst = 0.0

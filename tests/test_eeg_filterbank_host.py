@@ -282,7 +282,7 @@ def test_dataset_reports_the_bank_shape_and_its_cpu_items_follow_the_rule(tmp_pa
     spec = "bank=8:13+13:30+30:45,decimate=2,taps=41,fit" + (",envelope" if envelope else "")
     ds, loader = data_provider(_ns(tmp_path, device_standardise=False, eeg_preprocess=spec), "test")
     assert isinstance(ds.pre, F.ResolvedBank) and (ds.pre.quad is not None) == envelope
-    assert (ds.enc_in, ds.seq_len, ds.pre.Tv, ds.pre.Cout) == (3 * 8, 120, 100, 8) and loader.device_transform is None
+    assert (ds.enc_in, ds.seq_len, ds.pre.Tv, ds.pre.Cout) == (3 * 8, 120, 100, 8) and loader.eeg_chain is None
     x0, y0 = ds[0]
     assert x0.shape == (100, 24) and x0.dtype == torch.float32 and y0.shape == (1,)
     p = ds.pre
@@ -297,7 +297,7 @@ def test_dataset_reports_the_bank_shape_and_its_cpu_items_follow_the_rule(tmp_pa
     # a raw data set ships raw items and hands the resolved bank to the loader
     ds, loader = data_provider(_ns(tmp_path, device_standardise=True, eeg_preprocess=spec), "train")
     assert ds[0][0].shape == (12, 200) and (ds.seq_len, ds.enc_in) == (120, 24)
-    assert loader.device_transform == "eeg_preprocess" and loader.eeg_preprocess is ds.pre
+    assert loader.eeg_chain.names == ["preprocess"] and loader.eeg_chain.stages[0] is ds.pre
     # without fit: every electrode of every band, Td time steps
     ds, _ = data_provider(_ns(tmp_path, device_standardise=False, eeg_preprocess="bank=8:13+13:30,taps=41,decimate=2"), "val")
     assert (ds.enc_in, ds.seq_len) == (24, 100) and ds[0][0].shape == (100, 24)
@@ -307,10 +307,12 @@ def test_one_band_cpu_item_is_the_one_band_rule_exactly(tmp_path):
     """The data set's item path makes one filterbank_numpy call for every spec; for a one-band spec the item is still
     preprocess_numpy of the raw item, value for value."""
     import speech_imagery_eeg_amd  # noqa: F401
+    from data_provider.eeg_chain import EEGChain
     from data_provider.eeg_npy import EEGNpyDataset3Class
     F = _F()
     X = _shards(tmp_path)
-    ds = EEGNpyDataset3Class(str(tmp_path), flag="train", preprocess="band=8:30,decimate=2,fit", target_channels=8, target_timepoints=120)
+    ds = EEGNpyDataset3Class(str(tmp_path), flag="train",
+                             chain=EEGChain(preprocess="band=8:30,decimate=2,fit", target_channels=8, target_timepoints=120))
     assert isinstance(ds.pre, F.Resolved) and (ds.enc_in, ds.seq_len, ds.pre.Tv) == (8, 120, 100)
     for i in (0, 7):
         want = F.preprocess_numpy(X[ds.idx[i]], ds.pre.taps.astype(np.float32), 2, "reflect", 8, 120).astype(np.float32)

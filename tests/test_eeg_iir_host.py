@@ -297,13 +297,13 @@ def test_default_builds_the_same_objects_and_never_calls_the_op(tmp_path, monkey
     me = SimpleNamespace(device=torch.device("cpu"))
     for kw in ({}, dict(eeg_iir="none"), dict(eeg_iir=None), dict(eeg_iir="")):
         ds, loader = data_provider(_ns(tmp_path, device_standardise=True, **kw), "train")
-        assert loader.collate_fn is collate_raw and loader.device_transform == "standardise_raw"
-        assert ds.iir is None and not hasattr(loader, "eeg_iir") and not hasattr(ordered_loader(loader), "eeg_iir")
+        assert loader.collate_fn is collate_raw and loader.eeg_chain is ds.chain and loader.eeg_chain.stages == []
+        assert ds.iir is None and ordered_loader(loader).eeg_chain is ds.chain
         assert (ds.enc_in, ds.seq_len) == (6, 64) and len(ds[0]) == 2 and next(iter(loader))[2] is None
         pf = Experiment._prefetch(me, loader)
         assert pf.transform is device_prefetch.standardise_raw_batch                # the very function, unwrapped
         ds, loader = data_provider(_ns(tmp_path, device_standardise=False, **kw), "train")
-        assert loader.device_transform is None and ds.iir is None and Experiment._prefetch(me, loader) is loader
+        assert loader.eeg_chain is None and ds.iir is None and Experiment._prefetch(me, loader) is loader
         assert np.array_equal(ds[3][0].numpy(), per_sample_standardise(X[ds.idx[3]]).T)
 
 
@@ -315,7 +315,8 @@ def test_active_stage_travels_with_the_loader_and_the_cpu_item_path_is_the_rule(
     m, s = I(), S()
     X, _, subj = write_shards(str(tmp_path))
     ds, loader = data_provider(_ns(tmp_path, device_standardise=True, eeg_iir="hp=1,notch=50"), "train")
-    assert loader.collate_fn is collate_raw and loader.eeg_iir is ds.iir and ordered_loader(loader).eeg_iir is ds.iir
+    assert loader.collate_fn is collate_raw and loader.eeg_chain.names == ["iir"] and loader.eeg_chain.stages[0] is ds.iir
+    assert ordered_loader(loader).eeg_chain is loader.eeg_chain
     assert ds.iir.pad == 21 and ds.iir.ns == 3 and (ds.enc_in, ds.seq_len) == (6, 64) and len(ds[0]) == 2
     with pytest.raises(ValueError, match="needs rows of more than 64 samples"):
         data_provider(_ns(tmp_path, device_standardise=True, eeg_iir="hp=1,pad=64"), "train")
@@ -326,7 +327,7 @@ def test_active_stage_travels_with_the_loader_and_the_cpu_item_path_is_the_rule(
     for pre in (None, "band=8:30,taps=21"):
         kw = {} if pre is None else dict(eeg_preprocess=pre)
         ds, loader = data_provider(_ns(tmp_path, device_standardise=False, eeg_spatial="ref=car", eeg_iir="hp=1,notch=50", **kw), "train")
-        assert loader.device_transform is None and ds.iir.pad == 21
+        assert loader.eeg_chain is None and ds.iir.pad == 21
         for i in (0, 5):
             v = s.spatial_numpy(X[ds.idx[i]], W0[0].astype(np.float32), dtype=np.float32)
             v = m.iir_numpy(v, ds.iir.table, 21, ds.iir.g0).astype(np.float32)

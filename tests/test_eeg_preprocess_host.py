@@ -312,6 +312,7 @@ def _ns(tmp_path, **kw):
 def test_none_leaves_the_dataset_and_the_loader_as_they_are(tmp_path):
     import speech_imagery_eeg_amd  # noqa: F401
     from data_provider.data_factory import data_provider
+    from data_provider.eeg_chain import EEGChain
     from data_provider.eeg_npy import EEGNpyDataset3Class
     _shards(tmp_path)
     plain = EEGNpyDataset3Class(str(tmp_path), flag="train")
@@ -320,11 +321,11 @@ def test_none_leaves_the_dataset_and_the_loader_as_they_are(tmp_path):
             kw = {} if spec is None else dict(eeg_preprocess=spec)
             ds, loader = data_provider(_ns(tmp_path, device_standardise=raw, **kw), "train")
             assert (ds.seq_len, ds.enc_in, ds.num_classes, ds.raw, ds.pre) == (200, 12, 3, raw, None)      # --target_* stay inert
-            assert loader.device_transform == ("standardise_raw" if raw else None) and not hasattr(loader, "eeg_preprocess")
+            assert (loader.eeg_chain is ds.chain and loader.eeg_chain.names == []) if raw else loader.eeg_chain is None
             assert ds[0][0].shape == ((12, 200) if raw else (200, 12))
             if not raw:
                 assert torch.equal(ds[3][0], plain[3][0])
-    ds = EEGNpyDataset3Class(str(tmp_path), flag="train", preprocess="none", target_channels=8, target_timepoints=120)
+    ds = EEGNpyDataset3Class(str(tmp_path), flag="train", chain=EEGChain(preprocess="none", target_channels=8, target_timepoints=120))
     assert ds.pre is None and ds.seq_len == 200 and torch.equal(ds[3][0], plain[3][0])
 
 
@@ -335,7 +336,7 @@ def test_cpu_loader_path_decimates_fits_and_standardises(tmp_path):
     X = _shards(tmp_path)
     for flag in ("train", "val", "test"):                                    # the three loaders are treated alike
         ds, loader = data_provider(_ns(tmp_path, device_standardise=False, eeg_preprocess="decimate=2,fit"), flag)
-        assert (ds.seq_len, ds.enc_in) == (120, 8) and ds.pre.Tv == 100 and loader.device_transform is None
+        assert (ds.seq_len, ds.enc_in) == (120, 8) and ds.pre.Tv == 100 and loader.eeg_chain is None
         x0, y0 = ds[0]
         assert x0.shape == (100, 8) and x0.dtype == torch.float32 and y0.shape == (1,)
     ds, loader = data_provider(_ns(tmp_path, device_standardise=False, eeg_preprocess="decimate=2,fit"), "test")
@@ -355,6 +356,6 @@ def test_cpu_loader_path_decimates_fits_and_standardises(tmp_path):
     # a raw data set ships raw items and hands the resolved spec to the loader
     ds, loader = data_provider(_ns(tmp_path, device_standardise=True, eeg_preprocess="decimate=2,fit"), "train")
     assert ds[0][0].shape == (12, 200) and (ds.seq_len, ds.enc_in) == (120, 8)
-    assert loader.device_transform == "eeg_preprocess" and loader.eeg_preprocess is ds.pre
+    assert loader.eeg_chain.names == ["preprocess"] and loader.eeg_chain.stages[0] is ds.pre
     xb, yb, none = next(iter(loader))
     assert xb.shape == (16, 12, 200) and none is None

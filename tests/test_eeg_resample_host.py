@@ -315,13 +315,13 @@ def test_default_builds_the_same_objects_and_never_calls_the_op(tmp_path, monkey
     me = SimpleNamespace(device=torch.device("cpu"))
     for kw in ({}, dict(eeg_resample="none"), dict(eeg_resample=None), dict(eeg_resample=""), dict(eeg_resample="rate=500")):
         ds, loader = data_provider(_ns(tmp_path, device_standardise=True, **kw), "train")
-        assert loader.collate_fn is collate_raw and loader.device_transform == "standardise_raw"
-        assert ds.resample is None and not hasattr(loader, "eeg_resample") and not hasattr(ordered_loader(loader), "eeg_resample")
+        assert loader.collate_fn is collate_raw and loader.eeg_chain is ds.chain and loader.eeg_chain.stages == []
+        assert ds.resample is None and ordered_loader(loader).eeg_chain is ds.chain
         assert (ds.enc_in, ds.seq_len) == (6, 64) and len(ds[0]) == 2 and next(iter(loader))[2] is None
         pf = Experiment._prefetch(me, loader)
         assert pf.transform is device_prefetch.standardise_raw_batch                # the very function, unwrapped
         ds, loader = data_provider(_ns(tmp_path, device_standardise=False, **kw), "train")
-        assert loader.device_transform is None and ds.resample is None and Experiment._prefetch(me, loader) is loader
+        assert loader.eeg_chain is None and ds.resample is None and Experiment._prefetch(me, loader) is loader
         assert np.array_equal(ds[3][0].numpy(), per_sample_standardise(X[ds.idx[3]]).T)
         ds, _ = data_provider(_ns(tmp_path, device_standardise=False, eeg_iir="hp=1", eeg_preprocess="band=8:30,taps=21", **kw), "train")
         assert ds.resample is None and (ds.enc_in, ds.seq_len) == (6, 64)
@@ -329,21 +329,25 @@ def test_default_builds_the_same_objects_and_never_calls_the_op(tmp_path, monkey
 
 def test_active_stage_sets_the_shapes_travels_with_the_loader_and_checks_the_rates(tmp_path, capsys):
     import speech_imagery_eeg_amd  # noqa: F401
+    from data_provider import device_prefetch
     from data_provider.data_factory import data_provider, ordered_loader
     from data_provider.eeg_npy import collate_raw
     from exp.experiment_classification import Experiment
     write_shards(str(tmp_path))
     ds, loader = data_provider(_ns(tmp_path, device_standardise=True, eeg_resample="rate=256"), "train")
-    assert loader.collate_fn is collate_raw and loader.eeg_resample is ds.resample and ordered_loader(loader).eeg_resample is ds.resample
+    assert loader.collate_fn is collate_raw and loader.eeg_chain.names == ["resample"] and loader.eeg_chain.stages[0] is ds.resample
+    assert ordered_loader(loader).eeg_chain is loader.eeg_chain
     assert (ds.resample.Tin, ds.resample.Tout, ds.resample.Lp) == (64, 33, 40) and (ds.enc_in, ds.seq_len) == (6, 33)
     assert tuple(ds[0][0].shape) == (6, 64)                                         # raw items keep the shards' length
     pf = Experiment._prefetch(SimpleNamespace(device=torch.device("cpu")), loader)
-    assert pf.transform.__qualname__.startswith("resample_raw_batch")               # the stage wraps the standardisation
+    assert pf.loader is loader and loader.eeg_chain.names == ["resample"]            # the one stage, in front of the standardisation
+    assert pf.transform is not device_prefetch.standardise_raw_batch
     # the FIR stage resolves against Tout: without fit its own Td, with fit the target
     ds, loader = data_provider(_ns(tmp_path, device_standardise=True, eeg_iir="hp=1,notch=50", eeg_resample="rate=256",
                                    eeg_preprocess="band=8:30,sfreq=256,taps=21"), "train")
     assert (ds.enc_in, ds.seq_len, ds.pre.Tout, ds.pre.Tv) == (6, 33, 33, 33) and ds.iir.pad == 21
-    assert loader.device_transform == "eeg_preprocess" and loader.eeg_iir is ds.iir and loader.eeg_resample is ds.resample
+    assert loader.eeg_chain.names == ["iir", "resample", "preprocess"]
+    assert all(a is b for a, b in zip(loader.eeg_chain.stages, (ds.iir, ds.resample, ds.pre)))
     ds, _ = data_provider(_ns(tmp_path, device_standardise=True, eeg_resample="rate=256", eeg_preprocess="band=8:30,sfreq=256,taps=21,decimate=2"),
                           "train")
     assert (ds.seq_len, ds.pre.Tout) == (17, 17)
@@ -382,7 +386,7 @@ def test_the_cpu_item_is_the_rule(tmp_path):
         kw = {} if pre is None else dict(eeg_preprocess=pre)
         ds, loader = data_provider(_ns(tmp_path, device_standardise=False, eeg_spatial="ref=car", eeg_iir="hp=1,notch=50",
                                        eeg_resample="rate=256", **kw), "train")
-        assert loader.device_transform is None and ds.seq_len == 33
+        assert loader.eeg_chain is None and ds.seq_len == 33
         rs = ds.resample
         for i in (0, 5):
             v = s.spatial_numpy(X[ds.idx[i]], W0[0].astype(np.float32), dtype=np.float32)

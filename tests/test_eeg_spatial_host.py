@@ -247,12 +247,12 @@ def test_default_leaves_the_loader_as_it_is(tmp_path):
     os.remove(tmp_path / "subject.npy")
     for kw in ({}, dict(eeg_spatial="none"), dict(eeg_spatial=None)):
         ds, loader = data_provider(_ns(tmp_path, device_standardise=True, **kw), "train")
-        assert loader.collate_fn is collate_raw and loader.device_transform == "standardise_raw"
-        assert not hasattr(loader, "eeg_spatial") and ds.spatial is None and ds.enc_in == 6
-        assert not hasattr(ordered_loader(loader), "eeg_spatial")
+        assert loader.collate_fn is collate_raw and loader.eeg_chain is ds.chain and loader.eeg_chain.stages == []
+        assert ds.spatial is None and ds.enc_in == 6
+        assert ordered_loader(loader).eeg_chain is ds.chain
         assert len(ds[0]) == 2 and len(next(iter(loader))) == 3 and next(iter(loader))[2] is None
         ds, loader = data_provider(_ns(tmp_path, device_standardise=False, **kw), "train")
-        assert loader.device_transform is None and ds.spatial is None
+        assert loader.eeg_chain is None and ds.spatial is None
 
 
 def test_loader_carries_groups_and_the_cpu_item_path_is_the_rule(tmp_path):
@@ -271,8 +271,8 @@ def test_loader_carries_groups_and_the_cpu_item_path_is_the_rule(tmp_path):
         ds, loader = data_provider(_ns(tmp_path, device_standardise=True, eeg_spatial=f"ref=car,matrix={tmp_path / 'm.npy'}"), flag)
         assert ds.enc_in == 4 and ds.groups == 3 and ds.spatial.Cs == 4 and np.array_equal(ds.spatial.labels, labels)
         assert np.array_equal(ds.group, dense) and ds.group.dtype == np.int32        # one dense mapping over the whole file
-        assert loader.collate_fn is collate_raw_group and loader.eeg_spatial is ds.spatial
-        assert loader.device_transform == "standardise_raw" and ordered_loader(loader).eeg_spatial is ds.spatial
+        assert loader.collate_fn is collate_raw_group and loader.eeg_chain.names == ["spatial"] and loader.eeg_chain.stages[0] is ds.spatial
+        assert ordered_loader(loader).eeg_chain is loader.eeg_chain
         xb, yb, gid = next(iter(ordered_loader(loader)))
         n = min(8, len(ds))
         assert xb.shape == (n, 6, 64) and gid.dtype == torch.int32 and gid.tolist() == dense[ds.idx[:n]].tolist()
@@ -284,7 +284,7 @@ def test_loader_carries_groups_and_the_cpu_item_path_is_the_rule(tmp_path):
         kw = {} if pre is None else dict(eeg_preprocess=pre)
         ds, loader = data_provider(_ns(tmp_path, device_standardise=False, eeg_spatial=f"ref=car,matrix={tmp_path / 'm.npy'}", **kw),
                                    "train")
-        assert loader.device_transform is None and ds.enc_in == 4
+        assert loader.eeg_chain is None and ds.enc_in == 4
         for i in (0, 5):
             j = ds.idx[i]
             v = s.spatial_numpy(X[j], W0[dense[j]].astype(np.float32), dtype=np.float32)
@@ -305,22 +305,23 @@ def test_loader_carries_groups_and_the_cpu_item_path_is_the_rule(tmp_path):
 
 def test_groups_without_the_file_with_a_wrong_matrix_and_without_need(tmp_path):
     import speech_imagery_eeg_amd  # noqa: F401
+    from data_provider.eeg_chain import EEGChain
     from data_provider.eeg_npy import EEGNpyDataset
     write_shards(str(tmp_path))
-    ds = EEGNpyDataset(str(tmp_path), flag="train", spatial="ref=car")        # no groups needed: the file is not read
+    ds = EEGNpyDataset(str(tmp_path), flag="train", chain=EEGChain(spatial="ref=car"))        # no groups needed: the file is not read
     assert ds.groups == 1 and not ds.group.any() and ds.spatial.W.shape == (1, 6, 6)
     np.save(tmp_path / "two.npy", np.zeros((2, 4, 6)))
     with pytest.raises(ValueError, match="holds 2 groups, the shards 3"):
-        EEGNpyDataset(str(tmp_path), flag="train", spatial=f"matrix={tmp_path / 'two.npy'}")
+        EEGNpyDataset(str(tmp_path), flag="train", chain=EEGChain(spatial=f"matrix={tmp_path / 'two.npy'}"))
     np.save(tmp_path / "subject.npy", np.zeros(24))                           # float ids
     with pytest.raises(ValueError, match="integer subject ids"):
-        EEGNpyDataset(str(tmp_path), flag="train", spatial="align=euclid")
+        EEGNpyDataset(str(tmp_path), flag="train", chain=EEGChain(spatial="align=euclid"))
     os.remove(tmp_path / "subject.npy")
-    ds = EEGNpyDataset(str(tmp_path), flag="val", spatial="align=euclid")     # only the training split speaks
+    ds = EEGNpyDataset(str(tmp_path), flag="val", chain=EEGChain(spatial="align=euclid"))     # only the training split speaks
     assert ds.groups == 1 and not ds.group.any()
     said = []
-    ds._init_spatial("align=euclid", str(tmp_path), 24, said.append)
-    assert ds.groups == 1 and len(said) == 1 and "one group" in said[0]
+    again = EEGChain(spatial="align=euclid").resolve(6, 64, str(tmp_path), 24, notice=said.append)
+    assert again.stage("spatial").groups == 1 and not again.group.any() and len(said) == 1 and "one group" in said[0]
 
 
 def test_experiment_fits_saves_and_builds_for_cs_channels_on_the_cpu(tmp_path, monkeypatch):

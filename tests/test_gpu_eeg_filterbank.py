@@ -131,7 +131,8 @@ def test_ops_refusals_on_the_device():
 def test_prefetcher_with_the_bank_transform_equals_the_cpu_loader_path(tmp_path, envelope):
     dev = _dev()
     ops, F = _mods()
-    from data_provider.device_prefetch import DevicePrefetcher, preprocess_raw_batch
+    from data_provider.device_prefetch import DevicePrefetcher
+    from data_provider.eeg_chain import EEGChain
     from data_provider.eeg_npy import EEGNpyDataset3Class, collate_raw
     from data_provider.uea import collate_fn
     rng = np.random.RandomState(1)
@@ -139,13 +140,13 @@ def test_prefetcher_with_the_bank_transform_equals_the_cpu_loader_path(tmp_path,
     np.save(tmp_path / "X.npy", X)
     np.save(tmp_path / "y.npy", rng.randint(0, 39, size=50))
     spec = "bank=8:13+13:30+30:45,decimate=2,fit" + (",envelope" if envelope else "")
-    kw = dict(preprocess=spec, target_channels=8, target_timepoints=120)
+    kw = dict(chain=EEGChain(preprocess=spec, target_channels=8, target_timepoints=120))
     cpu = EEGNpyDataset3Class(str(tmp_path), flag="train", **kw)
     raw = EEGNpyDataset3Class(str(tmp_path), flag="train", raw=True, **kw)
     assert (raw.seq_len, raw.enc_in, raw.pre.Tv) == (120, 24, 100) and isinstance(raw.pre, F.ResolvedBank)
     want = list(torch.utils.data.DataLoader(cpu, batch_size=16, shuffle=False, collate_fn=lambda b: collate_fn(b, max_len=cpu.seq_len)))
     loader = torch.utils.data.DataLoader(raw, batch_size=16, shuffle=False, collate_fn=collate_raw, pin_memory=True)
-    got = list(DevicePrefetcher(loader, dev, transform=preprocess_raw_batch(raw.pre, dev)))
+    got = list(DevicePrefetcher(loader, dev, transform=raw.chain.device_transform(dev)))
     assert len(got) == len(want)
     for (a, b, m), (c, d, n) in zip(got, want):
         assert a.is_cuda and a.shape == c.shape == (a.shape[0], 120, 24)

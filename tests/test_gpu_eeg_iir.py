@@ -116,21 +116,21 @@ def test_prefetcher_spatial_iir_preprocess_equals_the_cpu_item_path(tmp_path, pr
     from conftest import parity
     dev, s, m = _dev(), S(), I()
     _ops()
-    from data_provider.device_prefetch import (DevicePrefetcher, iir_raw_batch, preprocess_raw_batch, spatial_raw_batch,
-                                               standardise_raw_batch)
+    from data_provider.device_prefetch import DevicePrefetcher
+    from data_provider.eeg_chain import EEGChain
     from data_provider.eeg_npy import EEGNpyDataset, collate_raw_group, per_sample_standardise
     from data_provider.uea import collate_fn
     from utils.eeg_filter import filterbank_numpy, pad_time
     X, y, subj = write_shards(str(tmp_path))
-    kw = dict(spatial="ref=car", iir=IIR) if pre is None else dict(spatial="ref=car", iir=IIR, preprocess=pre)
+    kw = dict(chain=EEGChain(spatial="ref=car", iir=IIR, preprocess=pre))
     cpu = EEGNpyDataset(str(tmp_path), flag="train", **kw)
     raw = EEGNpyDataset(str(tmp_path), flag="train", raw=True, **kw)
     assert raw.iir.pad == 21 and raw.iir.ns == 3 and (raw.enc_in, raw.seq_len) == (cpu.enc_in, cpu.seq_len) == (6, 64)
     W = raw.spatial.W
     want = list(torch.utils.data.DataLoader(cpu, batch_size=8, shuffle=False, collate_fn=lambda b: collate_fn(b, max_len=cpu.seq_len)))
     loader = torch.utils.data.DataLoader(raw, batch_size=8, shuffle=False, collate_fn=collate_raw_group, pin_memory=True)
-    inner = standardise_raw_batch if pre is None else preprocess_raw_batch(raw.pre, dev)
-    got = list(DevicePrefetcher(loader, dev, transform=spatial_raw_batch(torch.from_numpy(W).to(dev), iir_raw_batch(raw.iir, inner))))
+    assert raw.chain.names == ["spatial", "iir"] + ([] if pre is None else ["preprocess"])
+    got = list(DevicePrefetcher(loader, dev, transform=raw.chain.device_transform(dev)))
     assert len(got) == len(want) == 3
     for i, ((a, b, ma), (c, d, n)) in enumerate(zip(got, want)):
         j = raw.idx[8 * i:8 * i + 8]
@@ -156,7 +156,6 @@ def test_harness_trains_with_the_stage_fits_the_alignment_behind_it_and_records_
     dev = _dev()
     import speech_imagery_eeg_amd  # noqa: F401
     import run as driver
-    from data_provider.device_prefetch import iir_post
     from exp.experiment_classification import Experiment
     s, m = S(), I()
     write_shards(str(tmp_path))
@@ -175,11 +174,11 @@ def test_harness_trains_with_the_stage_fits_the_alignment_behind_it_and_records_
     rec = json.load(open(os.path.join(exp.checkpoint_dir, m.FILE_NAME)))
     assert m.parse_eeg_iir(rec["spec"]) == iir.spec and rec["pad"] == 21 and np.array_equal(np.asarray(rec["table"]), iir.table)
     batches = list(exp.train_data.raw_batches(8))
-    host = s.fit_alignment(batches, st.W0, 3, 1e-6, notice=None, post=iir_post(iir))              # numpy float64 on filtered rows
+    host = s.fit_alignment(batches, st.W0, 3, 1e-6, notice=None, post=exp.train_data.chain.alignment_post(dev))              # numpy float64 on filtered rows
     plain = s.fit_alignment(batches, st.W0, 3, 1e-6, notice=None)
     d_host = float(np.abs(st.W - host).max()) / float(np.abs(host).max())
     d_plain = float(np.abs(st.W - plain).max()) / float(np.abs(plain).max())
     print(f"eeg_iir alignment: device fit vs host fit on filtered rows {d_host:.3e}, vs the fit without the stage {d_plain:.3e}")
     assert d_host <= 1e-5 and d_plain > 1e-2
     on_dev = [(torch.from_numpy(x).to(dev), None, torch.from_numpy(g).to(dev)) for x, _, g in batches]
-    assert s.fit_alignment(on_dev, st.W0, 3, 1e-6, notice=None, post=iir_post(iir)).tobytes() == st.W.tobytes()
+    assert s.fit_alignment(on_dev, st.W0, 3, 1e-6, notice=None, post=exp.train_data.chain.alignment_post(dev)).tobytes() == st.W.tobytes()

@@ -211,12 +211,13 @@ def test_prefetcher_with_the_composed_transform_equals_the_cpu_loader_path(tmp_p
     from conftest import NORTH_STAR_TOL, parity
     dev, s = _dev(), S()
     _ops()
-    from data_provider.device_prefetch import DevicePrefetcher, preprocess_raw_batch, spatial_raw_batch, standardise_raw_batch
+    from data_provider.device_prefetch import DevicePrefetcher
+    from data_provider.eeg_chain import EEGChain
     from data_provider.eeg_npy import EEGNpyDataset, collate_raw_group, per_sample_standardise
     from data_provider.uea import collate_fn
     from utils.eeg_filter import filterbank_numpy, pad_time
     X, y, subj = write_shards(str(tmp_path))
-    kw = dict(spatial=spec) if pre is None else dict(spatial=spec, preprocess=pre)
+    kw = dict(chain=EEGChain(spatial=spec, preprocess=pre))
     cpu = EEGNpyDataset(str(tmp_path), flag="train", **kw)
     raw = EEGNpyDataset(str(tmp_path), flag="train", raw=True, **kw)
     assert raw.enc_in == cpu.enc_in == 6 and raw.groups == (3 if "align" in spec else 1)
@@ -229,8 +230,8 @@ def test_prefetcher_with_the_composed_transform_equals_the_cpu_loader_path(tmp_p
     W = raw.spatial.W
     want = list(torch.utils.data.DataLoader(cpu, batch_size=8, shuffle=False, collate_fn=lambda b: collate_fn(b, max_len=cpu.seq_len)))
     loader = torch.utils.data.DataLoader(raw, batch_size=8, shuffle=False, collate_fn=collate_raw_group, pin_memory=True)
-    inner = standardise_raw_batch if pre is None else preprocess_raw_batch(raw.pre, dev)
-    got = list(DevicePrefetcher(loader, dev, transform=spatial_raw_batch(torch.from_numpy(W).to(dev), inner)))
+    assert raw.chain.names == ["spatial"] + ([] if pre is None else ["preprocess"])
+    got = list(DevicePrefetcher(loader, dev, transform=raw.chain.device_transform(dev)))           # built behind the fit: it reads W
     assert len(got) == len(want) == 3
     for i, ((a, b, m), (c, d, n)) in enumerate(zip(got, want)):
         j = raw.idx[8 * i:8 * i + 8]
@@ -262,7 +263,8 @@ def test_a_run_without_the_flag_launches_neither_kernel(tmp_path):
     dev = _dev()
     _ops()
     from ign_hip import _lib
-    from data_provider.device_prefetch import DevicePrefetcher, spatial_raw_batch, standardise_raw_batch
+    from data_provider.device_prefetch import DevicePrefetcher, standardise_raw_batch
+    from data_provider.eeg_chain import EEGChain
     from data_provider.eeg_npy import EEGNpyDataset, collate_raw, collate_raw_group
     write_shards(str(tmp_path))
     _lib.timing_enable(True)
@@ -272,10 +274,9 @@ def test_a_run_without_the_flag_launches_neither_kernel(tmp_path):
         plain = list(DevicePrefetcher(loader, dev, transform=standardise_raw_batch))
         torch.cuda.synchronize()
         assert _lib.timing_read("eeg_spatial")[1] == 0 and _lib.timing_read("eeg_gram")[1] == 0
-        on = EEGNpyDataset(str(tmp_path), flag="train", raw=True, spatial="matrix=" + _identity(tmp_path))
+        on = EEGNpyDataset(str(tmp_path), flag="train", raw=True, chain=EEGChain(spatial="matrix=" + _identity(tmp_path)))
         loader = torch.utils.data.DataLoader(on, batch_size=8, shuffle=False, collate_fn=collate_raw_group)
-        same = list(DevicePrefetcher(loader, dev, transform=spatial_raw_batch(torch.from_numpy(on.spatial.W).to(dev),
-                                                                               standardise_raw_batch)))
+        same = list(DevicePrefetcher(loader, dev, transform=on.chain.device_transform(dev)))
         torch.cuda.synchronize()
         assert _lib.timing_read("eeg_spatial")[1] == 3 and _lib.timing_read("eeg_gram")[1] == 0
     finally:

@@ -240,7 +240,7 @@ def test_ordered_loader_yields_dataset_order_and_leaves_the_rng_alone():
     from data_provider.device_prefetch import DevicePrefetcher, TensorBatchLoader
     ds = _Rows(23)
     shuffled = torch.utils.data.DataLoader(ds, batch_size=4, shuffle=True, collate_fn=_collate)
-    shuffled.device_transform, shuffled.eeg_preprocess = 'eeg_preprocess', object()
+    shuffled.eeg_chain = object()
     sharded = TensorBatchLoader(ds, 4, shuffle=True, sampler=RankShardSampler(23, 1, 2, True, seed=5), pin_memory=False)
     plain = TensorBatchLoader(ds, 4, shuffle=True, pin_memory=False)
     torch.manual_seed(3)
@@ -255,9 +255,9 @@ def test_ordered_loader_yields_dataset_order_and_leaves_the_rng_alone():
         inner = out.loader if isinstance(out, DevicePrefetcher) else out
         assert inner.batch_size == 4 and inner.dataset is ds
     out = ordered_loader(shuffled)
-    assert out.collate_fn is _collate and out.device_transform == 'eeg_preprocess' and out.eeg_preprocess is shuffled.eeg_preprocess
+    assert out.collate_fn is _collate and out.eeg_chain is shuffled.eeg_chain
     assert next(iter(out))[2].dtype == torch.bool
-    assert ordered_loader(plain).device_transform is None
+    assert ordered_loader(plain).eeg_chain is None
     pre = ordered_loader(DevicePrefetcher(shuffled, "cpu", transform=_collate))
     assert pre.transform is _collate and pre.loader.collate_fn is _collate
     with pytest.raises(TypeError):
