@@ -187,6 +187,34 @@ size_t ign_eeg_resample_lds_bytes(int Tin, int up, int Lp);
 int ign_eeg_resample_nct(const float* x_nct, const float* tab, float* out_nct, int B, int C, int Tin, int Tout, int up, int down, int hl,
                          int Lp, int edge, void* stream);
 
+/* Artifact stage in FRONT of the spatial filter (csrc/ign_eeg_artifact.hip; run.py --eeg_artifact; ops.eeg_artifact; the rule in
+ * numpy: utils/eeg_artifact.py:artifact_numpy): robust row statistics, a verdict per electrode, a clamp of the good rows, the bad
+ * rows rebuilt from the good ones.  x (B,C,T) fp32 raw, out (B,C,T) fp32, stats (B,C,2) fp32 (m, s), flags (B,C) u8 (0, or 3 for a
+ * row with a non-finite sample), verdict (B,C) u8: 0 good, 1 flat, 2 noisy, 3 non-finite, 4 unrepaired; w (C,C) fp32 non-negative
+ * neighbour weights on the device, or NULL: all ones (the diagonal is never read).  med = the LOWER median, the element of rank
+ * (n-1)/2.  Per sample:
+ *   m_c = med(x[c]) (+0 for -0);  s_c = med(|x[c] - m_c|), each difference rounded once;  a non-finite row: flag 3, stats (0,0)
+ *   ref = med(s_c over the finite rows);  flat: s_c <= fl(flat*ref);  noisy: s_c > fl(noisy*ref);  no good row left: every bad row
+ *   gets 4 and is clamped only (a non-finite one: zeros)
+ *   good rows, clip > 0:  r = fl(fl(clip*1.4826f)*s_c);  lo = fl(m_c - r);  hi = fl(m_c + r);  y = x < lo ? lo : x > hi ? hi : x
+ *   bad row c:  y[c,t] = (sum_j w[c,j]*fl(y[j,t] - m_j)) / (sum_j w[c,j]),  j over the good rows ascending, j != c, one fmaf chain;
+ *   the weights' sum is rounded once; without a good j of positive weight: all ones over the good rows
+ * A non-positive clip, flat or noisy means the key is absent.  ign_eeg_artifact_stats_nct is one launch: the row as ordered keys and the
+ * rank element found by a bitwise select (32 counting passes), exact whatever the ties -- rows of up to 2048 samples in registers, one
+ * wave per row, no LDS; longer rows staged in LDS, one workgroup per row (ign_eeg_artifact_lds_bytes(): what a row of T samples costs
+ * when it is staged; 0 for a T the launcher refuses).  ign_eeg_artifact_apply_nct is two launches: the verdicts (one workgroup per sample), then tiles of
+ * (all C, 16..64 samples) whose clamped good rows go through LDS.  No atomics, no workspace beyond stats / flags, two calls give the
+ * same bits; every element of stats, flags, out and verdict is written; a row's statistics do not depend on B, C or its position, a
+ * sample's output not on B or its position.
+ * IGN_E_ARG: null x / stats / flags / out / verdict, non-positive dimension.  IGN_E_TOOBIG: T > IGN_EEG_ARTIFACT_MAX_ROW,
+ * C > IGN_EEG_ARTIFACT_MAX_CHANNELS, B*C beyond the launch grid.  Nothing is launched on an error.                                  */
+#define IGN_EEG_ARTIFACT_MAX_ROW      16384
+#define IGN_EEG_ARTIFACT_MAX_CHANNELS 1024
+size_t ign_eeg_artifact_lds_bytes(int T);
+int ign_eeg_artifact_stats_nct(const float* x_nct, float* stats, unsigned char* flags, int B, int C, int T, void* stream);
+int ign_eeg_artifact_apply_nct(const float* x_nct, const float* stats, const unsigned char* flags, const float* w, float* out_nct,
+                               unsigned char* verdict, int B, int C, int T, float clip, float flat, float noisy, void* stream);
+
 /* Shapelet transform of ONE length group: sliding-window distance + gate, never materialising (B,Tw,K,C,L).
  * Replaces IGN/model/Shapelet.py:60-84 (GATE_RBF) / :96-111 (GATE_LTS).   Tw = (T-L)/stride + 1.
  *   xn_bct   (B,C,T)    normalised input

@@ -1,10 +1,10 @@
 """The EEG front end as ONE ordered chain, from the flags to the prefetch stream (``--data EEG`` / ``EEG3``):
 
-    spatial -> iir -> resample -> preprocess (-> standardise: always last, inside the preprocess stage when there is one)
+    artifact -> spatial -> iir -> resample -> preprocess (-> standardise: always last, inside the preprocess stage when there is one)
 
-``EEGChain`` is the parsed form (the four specs, ``--target_channels`` / ``--target_timepoints``, the cross-flag rules in ``check``),
+``EEGChain`` is the parsed form (the five specs, ``--target_channels`` / ``--target_timepoints``, the cross-flag rules in ``check``),
 ``EEGChain.resolve`` gives the resolved form, ``ResolvedChain``: the ACTIVE stages only, in that order.  A stage is the object that owns
-its data (``SpatialStage``, ``ResolvedIIR``, ``ResolvedResample``, ``Resolved`` / ``ResolvedBank``), with a ``name`` and four methods:
+its data (``ResolvedArtifact``, ``SpatialStage``, ``ResolvedIIR``, ``ResolvedResample``, ``Resolved`` / ``ResolvedBank``), with a ``name`` and four methods:
 
     out_shape(C, T) -> (C, T)      the shape that leaves the stage for the one that enters
     apply_item(x (C,T), group)     the numpy rule of the CPU item path; the preprocess stage returns (Tv, C) standardised
@@ -19,14 +19,16 @@ import numpy as np
 import torch
 
 from data_provider.device_prefetch import standardise_raw_batch
+from utils.eeg_artifact import parse_eeg_artifact, resolve_artifact
 from utils.eeg_filter import parse_eeg_preprocess, resolve
 from utils.eeg_iir import iir_numpy, parse_eeg_iir, resolve_iir
 from utils.eeg_resample import parse_eeg_resample, resolve_resample, same_rate
 from utils.eeg_spatial import SpatialStage, compose, load_matrix, needs_groups, parse_eeg_spatial
 
-ORDER = ('spatial', 'iir', 'resample', 'preprocess')
+ORDER = ('artifact', 'spatial', 'iir', 'resample', 'preprocess')
 _ACTS_ON = dict(preprocess="filters the raw CHISCO shards", spatial="acts on the electrodes of the raw CHISCO shards",
-                iir="filters the rows of the raw CHISCO shards", resample="resamples the rows of the raw CHISCO shards")
+                iir="filters the rows of the raw CHISCO shards", resample="resamples the rows of the raw CHISCO shards",
+                artifact="judges the rows of the raw CHISCO shards")
 
 
 def _resolve_spatial(spec, Cin, root_path, n, notice):
@@ -53,25 +55,29 @@ def _resolve_spatial(spec, Cin, root_path, n, notice):
 
 class EEGChain:
     """The parsed form.  Flag texts (or specs already parsed) by keyword; `notice` hears the resampler's "a rate equal to sfreq is
-    no stage" line.  The flags are parsed in the order the driver has always reported a malformed one in."""
+    no stage" line.  The flags are parsed in the order the driver has always reported a malformed one in; --eeg_artifact, the
+    youngest, last."""
 
-    def __init__(self, spatial=None, iir=None, resample=None, preprocess=None, target_channels=None, target_timepoints=None, notice=None):
+    def __init__(self, spatial=None, iir=None, resample=None, preprocess=None, target_channels=None, target_timepoints=None, notice=None,
+                 artifact=None):
         self.preprocess = parse_eeg_preprocess(preprocess)
         self.spatial = parse_eeg_spatial(spatial)
         self.iir = parse_eeg_iir(iir)
         self.resample = parse_eeg_resample(resample, notice=notice)
         self.target_channels, self.target_timepoints = target_channels, target_timepoints
+        self.artifact = parse_eeg_artifact(artifact)
 
     @classmethod
     def from_args(cls, args, notice=None):
-        return cls(*(getattr(args, 'eeg_' + name, None) for name in ORDER), getattr(args, 'target_channels', None),
-                   getattr(args, 'target_timepoints', None), notice)
+        return cls(*(getattr(args, 'eeg_' + name, None) for name in ('spatial', 'iir', 'resample', 'preprocess')),
+                   getattr(args, 'target_channels', None), getattr(args, 'target_timepoints', None), notice,
+                   artifact=getattr(args, 'eeg_artifact', None))
 
     active = property(lambda self: [name for name in ORDER if getattr(self, name).active], doc="the active stages' names, in ORDER")
 
     def check(self, data_name):
         """The cross-flag rules: every active stage needs the raw CHISCO shards, and neighbours along the chain agree on the rate."""
-        for name in ('preprocess', 'spatial', 'iir', 'resample'):
+        for name in ('preprocess', 'spatial', 'iir', 'resample', 'artifact'):
             if getattr(self, name).active and data_name not in ('EEG', 'EEG3'):
                 raise ValueError(f"--eeg_{name} {_ACTS_ON[name]} (--data EEG / EEG3), not --data {data_name}")
         # one walk along the chain with the current rate carried forward.  A rate that a flag names is compared as written; behind
@@ -92,7 +98,9 @@ class EEGChain:
         """Against raw items (Cin, Tin) of the n trials under `root_path` -> ResolvedChain.  `notice`: print for the train split."""
         C, T, stages, group = int(Cin), int(Tin), [], None
         for name in self.active:
-            if name == 'spatial':
+            if name == 'artifact':
+                stage = resolve_artifact(self.artifact, C, T)
+            elif name == 'spatial':
                 stage, group = _resolve_spatial(self.spatial, C, root_path, n, notice)
             elif name == 'iir':
                 stage = resolve_iir(self.iir, T)

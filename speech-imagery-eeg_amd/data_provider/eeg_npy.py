@@ -94,6 +94,7 @@ class EEGNpyDataset(Dataset):
         self.chain = chain.resolve(X.shape[1], X.shape[2], root_path, len(y), notice=print if flag == 'train' else None)
         self.enc_in, self.seq_len = self.chain.shape                 # the models are built for what the items become
         self.spatial, self.iir, self.resample, self.pre = (self.chain.stage(k) for k in ('spatial', 'iir', 'resample', 'preprocess'))
+        self.artifact = self.chain.stage('artifact')
         if self.spatial is not None:
             self.group, self.groups = self.chain.group, self.spatial.groups
 
@@ -102,10 +103,10 @@ class EEGNpyDataset(Dataset):
 
     def raw_batches(self, batch_size):
         """The split's raw trials in data set order as (X (B,C,T) float32, None, gid (B,) int32) host arrays: the pass that fits an
-        alignment when the items themselves are not raw."""
+        alignment, or reports on the artifact stage, when the items themselves are not raw.  gid is None without a spatial stage."""
         for i in range(0, len(self.idx), int(batch_size)):
             j = self.idx[i:i + int(batch_size)]
-            yield np.stack([np.asarray(self.X[k], dtype=np.float32) for k in j]), None, self.group[j]
+            yield np.stack([np.asarray(self.X[k], dtype=np.float32) for k in j]), None, self.group[j] if self.spatial is not None else None
 
     def __getitem__(self, i):
         j = self.idx[i]

@@ -65,6 +65,16 @@ def accuracy_score(pred, true):
     return float((pred == true).mean()) if len(true) else 0.0
 
 
+def _raw_training_batches(exp):
+    """The raw TRAINING trials of an experiment in data set order, un-sharded and un-augmented, as (X (B,C,T), y, gid): on the GPU the
+    loader's own raw batches, moved to the device; else host arrays from the data set."""
+    from data_provider.data_factory import ordered_loader
+    if getattr(exp.train_loader, 'eeg_chain', None) is not None:                  # raw items: the loader's own batches
+        batches = ordered_loader(exp.train_loader)
+        return DevicePrefetcher(batches, exp.device) if exp.device.type == 'cuda' else batches
+    return exp.train_data.raw_batches(exp.args.batch_size)
+
+
 class Experiment(object):
     model_dict = {
         'InterpGN': InterpGN,
@@ -88,6 +98,7 @@ class Experiment(object):
         self._resolve_optim_options()   # --weight_decay / --lr_schedule / --ema: what is refused raises before anything is built
 
         self._load_data()
+        self._report_eeg_artifact()     # --eeg_artifact ...,report: one pass over the raw training trials, before the model is built
         self._get_params_from_data()
         self._resolve_loss_options()
         self._resolve_augment()
@@ -279,6 +290,19 @@ class Experiment(object):
         self.test_data, self.test_loader = data_provider(self.args, flag="test")
         self._fit_eeg_spatial()
 
+    def _report_eeg_artifact(self):
+        """--eeg_artifact ...,report: one ordered pass over the raw training trials before the model is built, through the stage's
+        kernels; counts per electrode the trials judged flat, noisy, non-finite or unrepaired.  Every rank computes the same counts
+        (no collective); rank 0 prints the table, and the counts go into eeg_artifact.json beside the checkpoint.  Without the key
+        nothing runs."""
+        stage = getattr(self.train_data, 'artifact', None)
+        if stage is None or not stage.spec.report:
+            return
+        stage.report_pass(_raw_training_batches(self))
+        if self.rank == 0:
+            for line in stage.report_lines():
+                print(line)
+
     def _fit_eeg_spatial(self):
         """--eeg_spatial align=euclid: one ordered, un-sharded, un-augmented pass over the raw TRAINING trials before the model is
         built (utils.eeg_spatial.fit_alignment: ops.eeg_spatial + ops.eeg_gram per batch on the device, float64 on the host), also
@@ -287,14 +311,12 @@ class Experiment(object):
         stage = getattr(self.train_data, 'spatial', None)
         if stage is None or stage.spec.align == 'none':
             return
-        from data_provider.data_factory import ordered_loader
         from utils.eeg_spatial import fit_alignment
-        if getattr(self.train_loader, 'eeg_chain', None) is not None:             # raw items: the loader's own batches
-            batches = ordered_loader(self.train_loader)
-            if self.device.type == 'cuda':
-                batches = DevicePrefetcher(batches, self.device)
-        else:
-            batches = self.train_data.raw_batches(self.args.batch_size)
+        batches = _raw_training_batches(self)
+        art = getattr(self.train_data, 'artifact', None)
+        if art is not None:                            # --eeg_artifact: the alignment is fitted on the repaired rows
+            fix = art.device_fn(self.device) if self.device.type == 'cuda' else (lambda x, gid: art.apply(np.asarray(x))[0])
+            batches = ((fix(x, gid), y, gid) for x, y, gid in batches)
         W = fit_alignment(batches, stage.W0, stage.groups, stage.spec.rtol, notice=print if self.rank == 0 else None,
                           post=self.train_data.chain.alignment_post(self.device))     # --eeg_iir: the Gram of the filtered rows
         for d in (self.train_data, self.val_data, self.test_data):

@@ -182,6 +182,9 @@ SIGNATURES = {
     "ign_eeg_iir_nct": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, cd, vp]),
     "ign_eeg_resample_lds_bytes": (sz, [ci, ci, ci]),
     "ign_eeg_resample_nct": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp]),
+    "ign_eeg_artifact_lds_bytes": (sz, [ci]),
+    "ign_eeg_artifact_stats_nct": (ci, [vp, vp, vp, ci, ci, ci, vp]),
+    "ign_eeg_artifact_apply_nct": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, cf, cf, cf, vp]),
 }
 
 

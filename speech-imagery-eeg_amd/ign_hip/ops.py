@@ -336,6 +336,52 @@ def eeg_resample(x_nct, tab, *, up, down, half_len, edge="reflect", out=None):
     return y
 
 
+def _artifact_weights(name, w, C):
+    """The neighbour weights as ign_eeg_artifact_apply_nct takes them: None, or a contiguous float32 (C,C) tensor on the GPU without
+    a negative or non-finite entry.  The kernel trusts the values, so they are checked here, on the host, once per tensor."""
+    if w is None:
+        return None
+    if not torch.is_tensor(w) or not w.is_cuda or w.dtype != torch.float32 or tuple(w.shape) != (C, C):
+        what = f"{w.dtype} {tuple(w.shape)} on {w.device}" if torch.is_tensor(w) else type(w).__name__
+        raise _lib.IgnError(f"{name}: neighbors must be a float32 tensor of shape ({C},{C}) on the GPU, got {what}")
+    w = w.contiguous()
+    if getattr(w, "_ign_artifact_checked", None) != w._version:
+        if not bool((torch.isfinite(w) & (w >= 0)).all()):
+            raise _lib.IgnError(f"{name}: neighbors holds a negative or non-finite weight")
+        w._ign_artifact_checked = w._version
+    return w
+
+
+def eeg_artifact(x_nct, clip=None, flat=None, noisy=None, neighbors=None, out=None):
+    """Raw (B,C,T) recordings -> (out (B,C,T) float32, verdict (B,C) uint8, stats (B,C,2) float32) on the GPU
+    (ign_eeg_artifact_stats_nct + ign_eeg_artifact_apply_nct; the rule is utils/eeg_artifact.py:artifact_numpy): per row the lower
+    median m and the median absolute deviation s; per electrode a verdict 0 good, 1 flat (s <= flat * ref), 2 noisy
+    (s > noisy * ref), 3 non-finite, 4 unrepaired, ref the lower median of s over the sample's finite rows; good rows clamped to
+    m +- clip * 1.4826 * s; bad rows rebuilt as the `neighbors`-weighted mean of the centred good rows.  None switches a key off
+    (flat=0: only s = 0 is flat); `neighbors`: (C,C) float32 non-negative on the GPU, None = all ones.  Statistics, verdicts and good
+    rows are bit for bit the numpy rule.  `out`: the out tensor, or (out, verdict, stats), to write into.  A non-contiguous x is
+    copied.  Three launches, no host synchronisation (the weights are checked once per tensor)."""
+    name = "eeg_artifact"
+    _need_gpu(name, x_nct)
+    if x_nct.dim() != 3:
+        raise _lib.IgnError(f"{name}: expected x (B,C,T), got {tuple(x_nct.shape)}")
+    from utils.eeg_artifact import kernel_keys
+    k, f, n = (float(v) for v in kernel_keys(clip, flat, noisy))
+    x = x_nct.contiguous()
+    B, C, T = x.shape
+    w = _artifact_weights(name, neighbors, C)
+    y, verdict, stats = out if isinstance(out, (tuple, list)) else (out, None, None)
+    y = _spatial_out(name, y, (B, C, T), torch.float32, x.device)
+    verdict = _spatial_out(name, verdict, (B, C), torch.uint8, x.device)
+    stats = _spatial_out(name, stats, (B, C, 2), torch.float32, x.device)
+    flags = torch.empty(B, C, device=x.device, dtype=torch.uint8)
+    L = _lib.lib()
+    _lib.check(L.ign_eeg_artifact_stats_nct(_ptr(x), _ptr(stats), _ptr(flags), B, C, T, _stream()), "ign_eeg_artifact_stats_nct")
+    _lib.check(L.ign_eeg_artifact_apply_nct(_ptr(x), _ptr(stats), _ptr(flags), _ptr(w), _ptr(y), _ptr(verdict), B, C, T, k, f, n,
+                                            _stream()), "ign_eeg_artifact_apply_nct")
+    return y, verdict, stats
+
+
 def augment(x, seed, *, lengths=None, shift=0.0, scale=0.0, noise=0.0, channel_drop=0.0, time_mask=0.0):
     """Training augmentation of a contiguous fp32 (B,T,C) batch on the GPU -> a new tensor (ign_augment_btc; the rule is
     csrc/ign_augment.h, restated in utils/augment.py): a circular shift by up to `shift` * length, a per-channel gain in

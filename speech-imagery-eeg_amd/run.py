@@ -42,7 +42,12 @@ Differences, all repairs of fork defects listed in SURVEY section 0:
     ``rate / sfreq`` with a polyphase Kaiser-windowed low-pass (scipy's ``resample_poly``) between ``--eeg_iir`` and
     ``--eeg_preprocess``: 500 -> 256 Hz, which ``decimate=Q`` cannot express; ``seq_len`` becomes ``ceil(T * up / down)``,
     ``--eeg_iir`` names the rate in front of it and ``--eeg_preprocess`` the rate behind it; the default ``none`` changes nothing;
-  * the ``--eeg_*`` stages run in one fixed order: spatial -> iir -> resample -> preprocess -> standardise (data_provider/eeg_chain.py);
+  * ``--eeg_artifact clip=6,flat=0.01,noisy=8,neighbors=PATH.npy,report`` (``--data EEG`` / ``EEG3``; any subset) judges every row of the
+    raw shards by its median and median absolute deviation in front of ``--eeg_spatial``: good rows are clamped to ``clip`` robust
+    standard deviations, flat, noisy and non-finite electrodes are rebuilt from the good ones (``neighbors``: a (C, C) weight matrix),
+    ``report`` counts the verdicts over the training split; nothing is dropped; the default ``none`` changes nothing;
+  * the ``--eeg_*`` stages run in one fixed order: artifact -> spatial -> iir -> resample -> preprocess -> standardise
+    (data_provider/eeg_chain.py);
   * ``--weight_decay WD``, ``--lr_schedule none|constant[,warmup=W]|cosine[,warmup=W][,min=M]`` and ``--ema D`` turn the flat Adam into
     AdamW with a per-optimizer-step schedule evaluated on the device and keep an exponential moving average of the weights that
     validation, early stopping and ``checkpoint.pth`` use (GPU only; all three default to off: the reference's optimizer);
@@ -202,6 +207,16 @@ def build_parser():
                         "5.0) and edge=reflect|zero (default reflect).  up/down is the exact fraction rate/sfreq (256/500 = 64/125); "
                         "rows of T samples leave with ceil(T * up / down); the filter is scipy.signal.resample_poly's, applied to "
                         "the row minus its first sample.  What was applied is written as eeg_resample.json beside the checkpoint")
+    p.add_argument("--eeg_artifact", type=str, default='none',
+                   help="--data EEG / EEG3: an artifact stage on every row of the raw shards, in front of --eeg_spatial, three launches "
+                        "on the device: none, or a comma list of clip=K (good rows are clamped to their median +- K * 1.4826 * MAD), "
+                        "flat=F (in [0, 1): an electrode whose MAD is at most F times the trial's median MAD is flat), noisy=N (> 1: "
+                        "one whose MAD is above N times it is noisy), neighbors=PATH.npy (a (C,C) non-negative weight matrix, e.g. "
+                        "inverse electrode distances; default: all ones) and report (count the verdicts over the training split "
+                        "before the first step and print the worst electrodes).  Flat, noisy and non-finite electrodes are rebuilt "
+                        "as the weighted mean of the trial's good electrodes about their medians; a trial without a good electrode "
+                        "is left clamped.  Medians are lower medians (exact order statistics).  Trials are never dropped.  What was "
+                        "applied, and the report, is written as eeg_artifact.json beside the checkpoint")
     # experiment
     p.add_argument("--lr", type=float, default=5e-3)
     p.add_argument("--lr_decay", action="store_true")
