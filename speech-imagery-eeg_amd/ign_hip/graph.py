@@ -7,6 +7,8 @@ Everything in the library is capture-safe: kernels are enqueued on the current s
 join through events, no launch depends on host state that changes between steps (the optimizer must be
 ``FlatAdam(..., capturable=True)``: device-side step count).  Shapes must stay fixed; a ragged last batch is run eagerly.
 """
+import gc
+
 import torch
 
 
@@ -23,8 +25,19 @@ class GraphedTrainStep:
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self.loss = self.step_fn(*self.static)
+        # No cycle collection inside the capture.  A dead reference cycle can still hold an earlier captured step (an Experiment
+        # holds its graphed step, whose step_fn closes over the Experiment), and the collector frees it whenever it next runs.
+        # Freeing a CUDAGraph synchronises the device on ROCm; while a stream captures that is an error, raised in a destructor,
+        # which ends the process.  So the dead cycles go now, and the collector stays off until the capture has ended.
+        gc.collect()
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(self.graph):
+                self.loss = self.step_fn(*self.static)
+        finally:
+            if gc_was_on:
+                gc.enable()
 
     def __call__(self, *inputs):
         if any(i.shape != s.shape for i, s in zip(inputs, self.static)):

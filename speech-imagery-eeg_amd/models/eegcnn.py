@@ -64,11 +64,12 @@ class EEGcnn(nn.Module):
         T = x.shape[-1]
         total = x.sum()
         pr = k - 1 - pl
-        head = x[..., :pr].sum(dim=(0, 1)).cumsum(0) if pr > 0 else x.new_zeros(0)        # first o samples, o = 1..pr
-        tail = x[..., T - pl:].sum(dim=(0, 1)).flip(0).cumsum(0) if pl > 0 else x.new_zeros(0)   # last o samples
-        left = total - tail.flip(0)            # taps j = 0 .. pl-1  (offset j - pl < 0: the last pl - j samples fall outside)
-        right = total - head                   # taps j = pl+1 .. k-1
-        return torch.cat([left, total.reshape(1), right])
+        nh, nt = min(pr, T), min(pl, T)        # a row shorter than a pad: taps further than T from the centre see no sample at all
+        head = x[..., :nh].sum(dim=(0, 1)).cumsum(0) if nh > 0 else x.new_zeros(0)        # first o samples, o = 1..nh
+        tail = x[..., T - nt:].sum(dim=(0, 1)).flip(0).cumsum(0) if nt > 0 else x.new_zeros(0)   # last o samples, o = 1..nt
+        left = total - tail.flip(0)            # taps j = pl-nt .. pl-1  (offset j - pl < 0: the last pl - j samples fall outside)
+        right = total - head                   # taps j = pl+1 .. pl+nh
+        return torch.cat([x.new_zeros(pl - nt), left, total.reshape(1), right, x.new_zeros(pr - nh)])
 
     _GRAM_INDEX = {}
 
@@ -133,8 +134,17 @@ class EEGcnn(nn.Module):
         F1, k1 = w1.shape
         D = w2.shape[0] // F1
         pl1 = (k1 - 1) // 2
-        x = ops.contiguous_bct(x)                   # (a permuted view of the loader's time-first batch: HIP transpose)
         batch_stats = bn1.training or not bn1.track_running_stats
+        # what the kernels would refuse is refused here: before any launch and before BatchNorm's running statistics move
+        if T + k1 > _ROW_TILE_MAX:
+            raise ops._lib.IgnError(f"EEG-CNN: rows of T={T} samples under k1={k1} taps do not fit the LDS row tile of the "
+                                    f"depthwise kernels (T + k1 <= {_ROW_TILE_MAX})")
+        gram = _BN1_VARIANCE == "gram" and 2 <= k1 <= 128 and T >= k1
+        if batch_stats and not gram and torch.is_grad_enabled() and w1.requires_grad and k1 > conv1_sumsq_max_taps(F1):
+            raise ops._lib.IgnError(f"EEG-CNN: k1={k1} taps with F1={F1} filters cannot train: the BatchNorm-1 variance gradient "
+                                    f"(ign_conv1_sumsq_bwd) takes k1 <= {conv1_sumsq_max_taps(F1)} at this F1; the lag-sum route "
+                                    f"that needs no such pass serves 2 <= k1 <= 128 at T >= k1")
+        x = ops.contiguous_bct(x)                   # (a permuted view of the loader's time-first batch: HIP transpose)
         if batch_stats and _BN1_VARIANCE == "gram" and 2 <= k1 <= 125 and k1 <= T <= 1024 and bn1.weight is not None \
                 and (bn1.momentum is not None or not bn1.track_running_stats):
             # BatchNorm-1's batch statistics are a linear / quadratic form of the filter over statistics of the INPUT (per-tap sums
@@ -155,7 +165,7 @@ class EEGcnn(nn.Module):
         if batch_stats:
             n = B * C * T
             mu1 = (w1 @ self._shifted_sums(x, k1, pl1)) / n
-            if _BN1_VARIANCE == "gram" and k1 <= 128 and T >= k1:
+            if gram:
                 # E[y^2] = w^T G w / n with the window Gram matrix of the INPUT (no pass over the (B,F1,C,T) convolution, and
                 # autograd's gradient 2 G w needs no pass over the data at all); float64 for the difference of two moments
                 with torch.no_grad():
@@ -168,6 +178,8 @@ class EEGcnn(nn.Module):
                 with torch.no_grad():
                     bn1.num_batches_tracked.add_(1)
                     m = bn1.momentum
+                    if m is None:             # nn.BatchNorm with momentum=None: cumulative moving average (as ops.bn_elu_pool)
+                        m = 1.0 / float(bn1.num_batches_tracked)
                     bn1.running_mean.mul_(1 - m).add_(mu1.detach(), alpha=m)
                     bn1.running_var.mul_(1 - m).add_(var1.detach() * (n / (n - 1)), alpha=m)
         else:
@@ -196,6 +208,13 @@ class EEGcnn(nn.Module):
 # beyond 128 or rows shorter than the kernel; tests) = brute-force pass over the un-stored convolution (ign_conv1_sumsq_*:
 # 3.1e10 FMA forward, 6.2e10 backward at the benchmark shape)
 _BN1_VARIANCE = "gram"
+_ROW_TILE_MAX = 8184        # dw_check of csrc/ign_eegcnn.hip: (2 T + 2 k + 16) floats of LDS <= 64 KB
+
+
+def conv1_sumsq_max_taps(F1):
+    """Longest kernel whose BatchNorm-1 variance gradient ign_conv1_sumsq_bwd takes: one lane per (filter, four taps) of up to
+    eight filters in a block of 256  (ceil(k1 / 4) * min(F1, 8) <= 256)."""
+    return 4 * (256 // min(F1, 8))
 
 
 def _encoder_layer_forward(layer, x, n_heads):

@@ -584,6 +584,46 @@ def test_graphed_train_step_equals_eager(scales):
             assert float((v - w).abs().max()) <= 1e-6 * max(1.0, float(v.abs().max())), k
 
 
+def test_graphed_train_step_keeps_the_cycle_collector_out_of_the_capture():
+    """A dead reference cycle may hold an earlier captured step, and freeing a captured graph synchronises the device, which a
+    capturing stream does not allow: GraphedTrainStep collects dead cycles before it captures, keeps the collector off while
+    it captures, and leaves it as it found it."""
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    dev = torch.device("cuda:0")
+    import gc
+    import weakref
+    import speech_imagery_eeg_amd  # noqa
+    from ign_hip.graph import GraphedTrainStep
+
+    class Node:
+        pass
+
+    seen = []
+
+    def step(x):
+        if torch.cuda.is_current_stream_capturing():
+            seen.append((gc.isenabled(), dead() is None))
+        return (x + 1).sum()
+
+    for was_on in (True, False):
+        a, b = Node(), Node()
+        a.other, b.other = b, a
+        dead = weakref.ref(a)
+        del a, b
+        del seen[:]
+        assert gc.isenabled()
+        try:
+            if not was_on:
+                gc.disable()
+            stepper = GraphedTrainStep(step, (torch.zeros(4, device=dev),), warmup=1)
+            assert gc.isenabled() == was_on
+        finally:
+            gc.enable()
+        assert seen == [(False, True)], seen
+        assert float(stepper(torch.ones(4, device=dev))) == 8.0
+
+
 def test_ign_in_autocast_mode_tracks_the_oracle_in_autocast_mode():
     """The reference's DEFAULT mode (bf16 autocast; `--amp` switches it off): the product model inside
     torch.autocast(cuda, bfloat16) against the CPU oracle inside torch.autocast(cpu, bfloat16), same weights and batch.
