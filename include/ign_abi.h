@@ -443,6 +443,39 @@ int ign_augment_btc(const float* x_btc, float* out_btc, const int32_t* len_b, in
 int ign_mix_btc(const float* x_btc, float* out_btc, const int32_t* len_b, const float* lam_b, const int32_t* span_b2, int roll,
                 int B, int T, int C, void* stream);
 
+/* Time, magnitude and window warping of the training batch (csrc/ign_warp.hip; run.py --warp): x (B,T,C) -> out (B,T,C), one launch,
+ * out of place (x == out or overlapping buffers: IGN_E_ARG), no workspace, no atomics, every element of out written once, bitwise
+ * repeatable.  len_b (B) int32 on the DEVICE or NULL (every sample has T steps); n = len_b[b] clamped to 0..T.
+ *   out[b,t,c] = g_b(t) * y,  y = (w == 0) ? x[b,i0,c] : x[b,i0,c] + w * (x[b,i0+1,c] - x[b,i0,c])       for t <  n
+ *                i0 = min(floor(phi_b(t)), n - 2),  w = phi_b(t) - i0   (mwarp == 0: no multiplication)
+ *   out[b,t,c] = x[b,t,c]                                                                              for t >= n (padding)
+ * The rule (csrc/ign_warp.h, the one definition the kernel, ign_warp_map and the numpy restatement utils/warp.py share; every product,
+ * sum and quotient is one fp32 rounding, no fma, so the restatement is bitwise equal).  K = knots, seg = K + 1, control points
+ * i = 0 .. K + 1 at equal spacing over [0, n - 1].  Draws: Philox4x32-10 under key = seed (low word first), last counter word 3:
+ *   counter (b, 0, 0, 3) -> x0, x1, x2: warped iff (x0 >> 8) * 2^-24 < prob (else the sample is copied bit for bit); x1 the window
+ *     start; x2 & 1 the window factor (0 -> 0.5, 1 -> 2);
+ *   speed knot i = word i & 3 of counter (b, 1 + (i >> 2), 0, 3), gain knot i likewise of (b, 4 + (i >> 2), 0, 3);
+ *     u = (word >> 8) * 2^-24, v_i = 1 + twarp * (2 u - 1), m_i = 1 + mwarp * (2 u - 1): positive for rates in [0, 1).
+ *   window map (wwarp = R > 0 and n >= 3): Lw = min(max(floor(R * n), 2), n - 1), a = x1 mod (n - Lw + 1), c = 0.5 or 2,
+ *     Iw(t) = t + (c - 1) * clamp(t - a, 0, Lw) (exact), pos(t) = (Iw(t) * (n - 1)) / Iw(n - 1); else pos(t) = t;
+ *   smooth map (twarp > 0): C_0 = 0, C_{i+1} = C_i + 0.5 * (v_i + v_{i+1}) in order; u = (p * seg) / (n - 1), i = min(floor(u), K),
+ *     f = u - i, I = C_i + (f * v_i + (f * f) * (0.5 * (v_{i+1} - v_i))), smooth(p) = (I * (n - 1)) / C_seg; else smooth(p) = p;
+ *   phi(t) = min(max(smooth(pos(t)), 0), n - 1) for t < n - 1 (the clamp whichever transforms are on) and phi(n - 1) = n - 1;
+ *   gain (mwarp > 0): i, f as above from the integer output step t, g(t) = m_i + f * (m_{i+1} - m_i), one curve for all channels.
+ * The map and the gain depend on (seed, b, n) only: not on c, B, the launch geometry, or which of the other transforms are on.
+ * n < 2 copies the row; a sample not warped by prob and a call with all three rates 0 are exact copies (still one launch).
+ * twarp, mwarp, wwarp outside [0, 1), knots outside 1..IGN_WARP_MAX_KNOTS, prob outside (0, 1], T < 1, a null x / out: IGN_E_ARG;
+ * T > IGN_WARP_MAX_T (t * seg and Iw stay exact in fp32) or T * C >= 2^31 - 65536: IGN_E_TOOBIG.  Nothing is launched on an error.
+ * ign_warp_map: HOST only, nothing is launched and no pointer is a device pointer -- the header's rule for sample b of length n,
+ * for inspection and tests: phi_n (n) and, unless NULL, gain_n (n) host arrays; an unwarped sample gives phi(t) = t, gain 1.
+ * Refusals as above (n < 0 or b < 0: IGN_E_ARG; n > IGN_WARP_MAX_T: IGN_E_TOOBIG).                                               */
+#define IGN_WARP_MAX_KNOTS 8
+#define IGN_WARP_MAX_T     (1 << 20)
+int ign_warp_btc(const float* x_btc, float* out_btc, const int32_t* len_b, int B, int T, int C, unsigned long long seed,
+                 float twarp, float mwarp, float wwarp, int knots, float prob, void* stream);
+int ign_warp_map(unsigned long long seed, int b, int n, float twarp, float mwarp, float wwarp, int knots, float prob,
+                 float* phi_n, float* gain_n);
+
 /* Fused attention core softmax(scale * Q K^T) V, exact fp32 on the matrix cores (v_mfma_f32_32x32x2_f32), scores never
  * materialised.  Replaces IGN/layers/SelfAttention_Family.py:56-75 (FullAttention: no mask; dropout 0 here -- dropout p > 0
  * is ign_attn_*_dropout below) and the attention inside nn.TransformerEncoderLayer of IGN/model/eegcnn.py:219-228.

@@ -101,6 +101,7 @@ class Experiment(object):
         self._report_eeg_artifact()     # --eeg_artifact ...,report: one pass over the raw training trials, before the model is built
         self._get_params_from_data()
         self._resolve_loss_options()
+        self._resolve_warp()
         self._resolve_augment()
         self._resolve_mix()
         # host -> device double buffering (and, for raw CHISCO shards, the on-GPU standardise + transpose)
@@ -190,6 +191,38 @@ class Experiment(object):
         if w is not None and self.rank == 0:
             print(f"class weights ({self.args.class_weight if spec == 'balanced' else 'given'}): "
                   f"{[round(float(v), 4) for v in w]}")
+
+    def _resolve_warp(self):
+        """--warp -> self._warp_spec (None when off: nothing is parsed beyond the word and the training loops do nothing extra -- no
+        launch, no mask sum, no seed arithmetic) and the base seed of utils.augment.step_seed, by --augment's rule: --seed when it
+        is >= 0, else torch's initial seed (reading it does not advance the generator)."""
+        text = getattr(self.args, 'warp', None)
+        self._warp_spec = None
+        if text is None or (isinstance(text, str) and text.strip().lower() in ('', 'none')):
+            return
+        from utils.warp import parse_warp
+        spec = parse_warp(text)
+        if not spec.active:
+            return
+        self._warp_spec = spec
+        seed = int(getattr(self.args, 'seed', -1))
+        self._warp_base = seed if seed >= 0 else int(torch.initial_seed())
+        if self.rank == 0:
+            print(f"warp: {', '.join(f'{k}={v:g}' for k, v in spec._asdict().items() if v and (k != 'prob' or v != 1.0))}")
+
+    def _warp(self, batch_x, padding_mask, train_step):
+        """The training batch of step `train_step`, warped along time on the device in one launch (ops.warp; seed = step_seed(base,
+        rank, step), so ranks draw different warps and the eager and captured loops the same ones), in front of _augment.  Each
+        sample is warped inside its own length -- the keep-mask's row sum, taken on the device without a host sync; an all-ones mask
+        gives what no lengths give -- so the padding and the mask stay as they are.  Labels and regression targets are per trial and
+        do not move.  Training only: validation, test, saliency, the k-means initialisation, the projection, the alignment fit and
+        the artifact report never call it."""
+        if self._warp_spec is None:
+            return batch_x
+        from utils.augment import step_seed
+        lengths = padding_mask.sum(1).to(torch.int32)
+        return ign_ops.warp(batch_x.contiguous(), step_seed(self._warp_base, self.rank, train_step), lengths=lengths,
+                            **self._warp_spec._asdict())
 
     def _resolve_augment(self):
         """--augment -> self._augment_spec (None when off: the training loops then do nothing extra -- no launch, no mask sum, no
@@ -415,6 +448,7 @@ class Experiment(object):
         for batch_x, label, padding_mask in self.train_loader:
             train_step += 1
             batch_x, label, padding_mask = self._to_device(batch_x, label, padding_mask)
+            batch_x = self._warp(batch_x, padding_mask, train_step)
             batch_x = self._augment(batch_x, padding_mask, train_step)
             batch_x, soft = self._mix(batch_x, label, padding_mask, train_step)
             with torch.autocast(device_type=self.device.type, dtype=torch.bfloat16, enabled=amp):
@@ -552,6 +586,7 @@ class Experiment(object):
         for batch_x, label, padding_mask in self.train_loader:
             train_step += 1
             batch_x, label, padding_mask = self._to_device(batch_x, label, padding_mask)
+            batch_x = self._warp(batch_x, padding_mask, train_step)         # outside the graph, as the two calls below
             batch_x = self._augment(batch_x, padding_mask, train_step)      # outside the graph: its static input takes this batch
             batch_x, soft = self._mix(batch_x, label, padding_mask, train_step)     # likewise; label_b / lam are static inputs too
             inputs = (batch_x, label, padding_mask, *soft)

@@ -171,6 +171,8 @@ SIGNATURES = {
     "ign_loss_mix_fwd_bwd_reg": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, cf, cf, vp]),
     "ign_augment_btc": (ci, [vp, vp, vp, ci, ci, ci, ctypes.c_ulonglong, cf, cf, cf, ctypes.c_uint, cf, vp]),
     "ign_mix_btc": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
+    "ign_warp_btc": (ci, [vp, vp, vp, ci, ci, ci, ctypes.c_ulonglong, cf, cf, cf, ci, cf, vp]),
+    "ign_warp_map": (ci, [ctypes.c_ulonglong, ci, ci, cf, cf, cf, ci, cf, c_f, c_f]),
     "ign_eeg_preprocess_ws_bytes": (sz, [ci, ci, ci, ci, ci, ci, ci]),
     "ign_eeg_preprocess_nct_to_btc": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, vp]),
     "ign_eeg_filterbank_ws_bytes": (sz, [ci, ci, ci, ci, ci, ci, ci, ci]),

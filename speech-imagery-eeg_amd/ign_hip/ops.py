@@ -420,6 +420,38 @@ def augment(x, seed, *, lengths=None, shift=0.0, scale=0.0, noise=0.0, channel_d
     return out
 
 
+def warp(x, seed, lengths=None, twarp=0.0, mwarp=0.0, wwarp=0.0, knots=4, prob=1.0):
+    """Time, magnitude and window warping of a contiguous fp32 (B,T,C) batch on the GPU -> a new tensor (ign_warp_btc; the rule is
+    csrc/ign_warp.h, restated in utils/warp.py): every sample is resampled along time through its own monotone map -- a smooth
+    speed curve through `knots` interior knots in 1 +- `twarp`, and one window of `wwarp` * length stretched or compressed by 2 -- and
+    scaled by a smooth gain curve in 1 +- `mwarp` shared by its channels; a sample is warped with probability `prob`, else copied.
+    `lengths`: int32 (B,) on the GPU -- everything happens inside each sample's own length and the padding is copied through;
+    None: every sample has T steps.  `seed`: a 64-bit host integer; the same seed gives the same output to the bit.  Rates lie in
+    [0, 1), knots in 1..8, prob in (0, 1].  One launch, also when every rate is 0 (a copy).
+    Refused for an input that requires a gradient (a training batch never does) and during graph capture (the seed is a host
+    value: a replay would repeat one warp)."""
+    name = "warp"
+    _need_gpu(name, x)
+    if x.dim() != 3 or not x.is_contiguous():
+        raise _lib.IgnError(f"{name}: expected a contiguous (B,T,C) tensor, got shape {tuple(x.shape)} strides {x.stride()}")
+    if x.requires_grad:
+        raise _lib.IgnError(f"{name}: the input requires a gradient; warping acts on data (there is no backward pass)")
+    if torch.cuda.is_current_stream_capturing():
+        raise _lib.IgnError(f"{name} inside a hipGraph capture: the per-call seed would be frozen into the graph (warp the batch "
+                            f"before the captured step)")
+    from utils.warp import check_spec
+    check_spec(twarp, mwarp, wwarp, knots, prob, who=name)
+    B, T, C = x.shape
+    out = torch.empty_like(x)
+    if B == 0:
+        return out
+    if lengths is not None:
+        lengths = _lengths(name, lengths, B)
+    _lib.check(_lib.lib().ign_warp_btc(_ptr(x), _ptr(out), _ptr(lengths), B, T, C, int(seed) & 0xFFFFFFFFFFFFFFFF, twarp, mwarp,
+                                       wwarp, int(knots), prob, _stream()), "ign_warp_btc")
+    return out
+
+
 def mix(x, lam, roll, span=None, lengths=None):
     """Mixup / CutMix of a contiguous fp32 (B,T,C) batch on the GPU -> a new tensor (ign_mix_btc; the rule is restated in
     utils/mix.py:mix_reference): sample b is blended with its partner p = (b + roll) mod B as lam[b] * x[b] + (1 - lam[b]) * x[p],

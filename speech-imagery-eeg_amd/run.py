@@ -23,6 +23,10 @@ Differences, all repairs of fork defects listed in SURVEY section 0:
   * ``--mix mixup=0.4[,cutmix=1][,prob=0.5]`` mixes every TRAINING sample with a partner of its batch on the device in one launch
     (mixup: a Beta(A, A) blend; cutmix: a time span of the partner) and trains on the soft labels (InterpGN: still one fused loss
     launch, also under ``--hipgraph``); classification only; validation / test never mix; the default ``none`` changes nothing;
+  * ``--warp twarp=0.2[,mwarp=0.1][,wwarp=0.1][,knots=4][,prob=0.5]`` (any subset of the three rates) warps every TRAINING sample
+    along time on the device in one launch, in front of ``--augment``: a smooth random speed curve (twarp), a smooth random gain
+    curve shared by the channels (mwarp) and one window stretched or compressed by 2 (wwarp), each inside the sample's own length;
+    classification and regression; validation / test never warp; the default ``none`` changes nothing;
   * ``--eeg_preprocess band=8:30,decimate=2,fit`` (``--data EEG`` / ``EEG3``; any subset of sfreq=F, band=LO:HI, decimate=Q, taps=M,
     edge=reflect|zero, fit) filters the raw CHISCO shards with a zero-phase FIR band-pass, decimates them and, with ``fit``, crops /
     zero-pads them to ``--target_channels`` x ``--target_timepoints`` in front of the standardisation -- on the device in the
@@ -168,6 +172,14 @@ def build_parser():
                         "replaces one time span of a sample by its partner's instead of blending; with both keys each mixed sample "
                         "takes one of the two with probability 1/2; prob in (0, 1] is the chance that a sample is mixed at all.  "
                         "Partners are a random roll of the batch.  Classification only.  Reproducible from --seed")
+    p.add_argument("--warp", type=str, default='none',
+                   help="time, magnitude and window warping of the training batch on the device, one launch per step in front of "
+                        "--augment: none, or twarp=R[,mwarp=R][,wwarp=R][,knots=K][,prob=P] with any subset of the three rates.  "
+                        "twarp=R resamples every sample through a smooth monotone time map whose local speed lies in 1 +- R; mwarp=R "
+                        "multiplies it by a smooth gain curve in 1 +- R, one curve for all channels; wwarp=R stretches or compresses "
+                        "one window of R * length by 2 and rescales the sample to its length; rates in [0, 1).  knots=K (1..8, "
+                        "default 4) interior knots of the two curves; prob in (0, 1] is the chance that a sample is warped at all.  "
+                        "Reproducible from --seed")
     p.add_argument("--eeg_preprocess", type=str, default='none',
                    help="--data EEG / EEG3: preprocessing of the raw shards in front of the standardisation, on the device: none, or a "
                         "comma list of sfreq=F (Hz, default 500), band=LO:HI (Hz, either side may be empty), decimate=Q, taps=M "
@@ -284,6 +296,8 @@ def check_args(args):
     check_loss_options(args, _num_class_from_flags(args))
     from utils.augment import parse_augment
     parse_augment(getattr(args, 'augment', None))
+    from utils.warp import parse_warp
+    parse_warp(getattr(args, 'warp', None))
     from utils.mix import parse_mix
     if parse_mix(getattr(args, 'mix', None)).active and getattr(args, 'task_name', 'classification') == 'regression':
         raise ValueError("--mix with --task_name regression: mixup / CutMix mix class labels through the cross-entropy tails; the "
