@@ -22,6 +22,18 @@
 #endif
 template <int TT> struct FwdJ { static constexpr int J = (TT <= 8) ? 8 : 4; };
 
+// The K_T = 5 L1 kernels of these TT (the benchmark's four; the only ones measured on the device) have a TWIN for the
+// common case -- RBF gate, the row in one pass, one wave per block -- picked by shp_fwd_launch.  The twin knows npass == 1 and the
+// gate at compile time, so nothing loop-invariant is carried across the distance loop, and that leaves room for a window that is
+// never copied: it lives in a register ring of W = J * ceil((TT + J - 1) / J) slots and the step loop is unrolled by its period
+// P = W / J.  Everywhere else the window is shifted down by J registers per step (W = TT + J - 1, P = 1).
+constexpr unsigned FWD_TWIN_TTS = (1u << 8) | (1u << 11) | (1u << 13) | (1u << 15);
+template <int TT, bool TWIN> struct FwdWin {
+    static constexpr int J = FwdJ<TT>::J;
+    static constexpr int W = TWIN ? ((TT + J - 1 + J - 1) / J) * J : TT + J - 1;     // register slots of the window
+    static constexpr int P = TWIN ? W / J : 1;                                       // steps until the ring is back at slot 0
+};
+
 // Wave reductions on the DPP path (pure VALU): two quad permutes, row_half_mirror, row_mirror, row_bcast:15, row_bcast:31.
 // After the four in-row steps every lane of a 16-lane row holds the row's result; the two broadcast steps leave the
 // 64-lane result in the last row, i.e. in LANE 63 -- the only lane that writes the row's outputs.  `__shfl_xor` compiles
@@ -64,7 +76,7 @@ __device__ __forceinline__ float wave_bcast_l63(float v) {
 // The body of one block; (bx, by) play the role of blockIdx.x / .y (kept as parameters: round 2's one-grid bank kernel called the
 // same body with a remapped block index, measured slower and was removed -- DESIGN 4.1b).  The calling kernel's ONLY argument must be
 // the ShpFwdArgs block `a`: the epilogue re-reads it from offset 0 of the kernarg segment.
-template <int TT, int KT, int DIST>
+template <int TT, int KT, int DIST, bool TWIN>
 __device__ __forceinline__ void shp_fwd_body(const ShpFwdArgs& a, const int bx, const int by, float* smem) {
     constexpr int J = FwdJ<TT>::J;
     const int wpb = blockDim.x >> 6;
@@ -112,7 +124,8 @@ __device__ __forceinline__ void shp_fwd_body(const ShpFwdArgs& a, const int bx, 
     // park them in LDS between passes, so the hot loop's register budget is acc + window only.
     float* park = smem + (blockDim.x >> 6) * a.xs_len + threadIdx.x;    // [5*KT][blockDim.x], npass > 1 only
 
-    for (int pass = 0; pass < a.npass; ++pass) {
+    const int npass = TWIN ? 1 : a.npass;
+    for (int pass = 0; pass < npass; ++pass) {
         const int tl = (pass * 64 + lane) * TT;     // first window owned by this lane
         const float* xl = xs + tl * a.stride;       // stride != 1 only with TT == 1
         float acc[KT][TT];
@@ -120,7 +133,9 @@ __device__ __forceinline__ void shp_fwd_body(const ShpFwdArgs& a, const int bx, 
         for (int k = 0; k < KT; ++k)
 #pragma unroll
             for (int t = 0; t < TT; ++t) acc[k][t] = 0.f;
-        float xw[TT + J - 1];
+        // The sliding window: sample j0 + i of the lane sits in slot (ph * J + i) % W, ph = step number mod P (FwdWin).
+        constexpr int W = FwdWin<TT, TWIN>::W, P = FwdWin<TT, TWIN>::P;
+        float xw[W];
 #pragma unroll
         for (int i = 0; i < TT - 1; ++i) xw[i] = xl[i];
         // cosine / pearson (Shapelet.py:64-69): the distance is 1 - <x_win, w> / (norms); the window norms are
@@ -133,46 +148,76 @@ __device__ __forceinline__ void shp_fwd_body(const ShpFwdArgs& a, const int bx, 
             for (int k = 0; k < KT; ++k) wn2[k] = 0.f;
         }
 
+        // One step of J samples as a macro, so that both loop forms below compile exactly as if it were written in place; S0 = slot of
+        // sample j0, a constant after unrolling.  All KT*J shapelet values of the step are requested up front (s_load, wave-uniform);
+        // with the barrier nothing is scheduled across: one exposed scalar-cache latency per step instead of one per shapelet.
+        // wv is the SGPR operand; cosine / pearson run the same loop as a sliding dot product.
+#define IGN_FWD_STEP(S0) do { \
+        const int s0 = (S0); \
+_Pragma("unroll") \
+            for (int jj = 0; jj < J; ++jj) xw[(s0 + TT - 1 + jj) % W] = xl[j0 + TT - 1 + jj]; \
+            float wvs[J][KT]; \
+_Pragma("unroll") \
+            for (int k = 0; k < KT; ++k) \
+_Pragma("unroll") \
+                for (int jj = 0; jj < J; ++jj) wvs[jj][k] = wk[k * wks + j0 + jj]; \
+            if constexpr (TT <= IGN_FWD_BARRIER_TT) __builtin_amdgcn_sched_barrier(0); \
+_Pragma("unroll") \
+            for (int jj = 0; jj < J; ++jj) { \
+_Pragma("unroll") \
+                for (int k = 0; k < KT; ++k) { \
+                    const float wv = wvs[jj][k]; \
+                    if (DIST >= DIST_COS) wn2[k] = fmaf(wv, wv, wn2[k]); \
+_Pragma("unroll") \
+                    for (int t = 0; t < TT; ++t) { \
+                        if (DIST >= DIST_COS) { \
+                            acc[k][t] = fmaf(xw[(s0 + t + jj) % W], wv, acc[k][t]); \
+                        } else { \
+                            const float df = xw[(s0 + t + jj) % W] - wv; \
+                            if (DIST == DIST_L1) acc[k][t] += fabsf(df); \
+                            else                 acc[k][t] = fmaf(df, df, acc[k][t]); \
+                        } \
+                    } \
+                } \
+                if (DIST >= DIST_COS) { \
+_Pragma("unroll") \
+                    for (int t = 0; t < TT; ++t) { \
+                        xsq[t] = fmaf(xw[(s0 + t + jj) % W], xw[(s0 + t + jj) % W], xsq[t]); \
+                        if (DIST == DIST_PEARSON) xsm[t] += xw[(s0 + t + jj) % W]; \
+                    } \
+                } \
+            } \
+        } while (0)
         int j0 = 0;
-        for (; j0 + J <= L; j0 += J) {
+        if constexpr (!TWIN) {
+            for (; j0 + J <= L; j0 += J) {
+                IGN_FWD_STEP(0);
 #pragma unroll
-            for (int jj = 0; jj < J; ++jj) xw[TT - 1 + jj] = xl[j0 + TT - 1 + jj];
-            // all KT*J shapelet values of this step are requested up front (s_load, wave-uniform); with the barrier nothing is
-            // scheduled across: one exposed scalar-cache latency per step instead of one per shapelet
-            float wvs[J][KT];
+                for (int i = 0; i < TT - 1; ++i) xw[i] = xw[i + J];
+            }
+        } else {
+            int rot = 0;
+            for (bool more = true; more;) {
 #pragma unroll
-            for (int k = 0; k < KT; ++k)
-#pragma unroll
-                for (int jj = 0; jj < J; ++jj) wvs[jj][k] = wk[k * wks + j0 + jj];
-            if constexpr (TT <= IGN_FWD_BARRIER_TT) __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int jj = 0; jj < J; ++jj) {
-#pragma unroll
-                for (int k = 0; k < KT; ++k) {
-                    const float wv = wvs[jj][k];                     // SGPR operand
-                    if (DIST >= DIST_COS) wn2[k] = fmaf(wv, wv, wn2[k]);
-#pragma unroll
-                    for (int t = 0; t < TT; ++t) {
-                        if (DIST >= DIST_COS) {
-                            acc[k][t] = fmaf(xw[t + jj], wv, acc[k][t]);         // sliding dot product
-                        } else {
-                            const float df = xw[t + jj] - wv;
-                            if (DIST == DIST_L1) acc[k][t] += fabsf(df);
-                            else                 acc[k][t] = fmaf(df, df, acc[k][t]);
-                        }
-                    }
-                }
-                if (DIST >= DIST_COS) {
-#pragma unroll
-                    for (int t = 0; t < TT; ++t) {
-                        xsq[t] = fmaf(xw[t + jj], xw[t + jj], xsq[t]);
-                        if (DIST == DIST_PEARSON) xsm[t] += xw[t + jj];
-                    }
+                for (int ph = 0; ph < P; ++ph) {
+                    if (j0 + J > L) { rot = ph; more = false; break; }
+                    IGN_FWD_STEP(ph * J);
+                    j0 += J;
                 }
             }
+            if (j0 < L) {                           // the tail below expects the window at slot 0 again
+                float xr[TT > 1 ? TT - 1 : 1];
 #pragma unroll
-            for (int i = 0; i < TT - 1; ++i) xw[i] = xw[i + J];
+                for (int ph = 0; ph < P; ++ph)
+                    if (rot == ph) {
+#pragma unroll
+                        for (int i = 0; i < TT - 1; ++i) xr[i] = xw[(ph * J + i) % W];
+                    }
+#pragma unroll
+                for (int i = 0; i < TT - 1; ++i) xw[i] = xr[i];
+            }
         }
+#undef IGN_FWD_STEP
         for (; j0 < L; ++j0) {                      // L % J tail, one sample at a time
             xw[TT - 1] = xl[j0 + TT - 1];
 #pragma unroll
@@ -217,8 +262,8 @@ __device__ __forceinline__ void shp_fwd_body(const ShpFwdArgs& a, const int bx, 
         kargs_p ae = (kargs_p)__builtin_amdgcn_kernarg_segment_ptr();
         asm volatile("" : "+s"(ae));
         const int nvalid = min(TT, max(0, ae->Tw - tl));
-        const bool lds_store = (ae->npass == 1) && ae->d;          // x row no longer needed: reuse its LDS as a transpose buffer
-        const bool last_pass = pass + 1 == ae->npass;
+        const bool lds_store = (TWIN || ae->npass == 1) && ae->d;          // x row no longer needed: reuse its LDS as a transpose buffer
+        const bool last_pass = TWIN || pass + 1 == ae->npass;
 #pragma unroll
         for (int k = 0; k < KT; ++k) {
             float rb, rd, rZ, rM;
@@ -249,7 +294,7 @@ __device__ __forceinline__ void shp_fwd_body(const ShpFwdArgs& a, const int bx, 
 #pragma unroll
                 for (int t = 0; t < TT; ++t) dv[t] = (t < nvalid) ? acc[k][t] * ae->invL : 1e18f;
             }
-            if (ae->gate == GATE_RBF) {
+            if (TWIN || ae->gate == GATE_RBF) {
 #pragma unroll
                 for (int t = 0; t < TT; ++t) {
                     const float u = ae->eps * dv[t];
@@ -318,7 +363,7 @@ __device__ __forceinline__ void shp_fwd_body(const ShpFwdArgs& a, const int bx, 
                 IGN_ARGMAX_STEP(DPP_BCAST31, 0xc);
                 float dmin = wave_min_l63(rd);
                 float Z = rZ, M = rM;
-                if (ae->gate == GATE_LTS) {
+                if (!TWIN && ae->gate == GATE_LTS) {
                     dmin = wave_bcast_l63(dmin);                  // every lane rescales its partial sums to the row minimum
                     const float sc = (rd < INFINITY) ? __expf(dmin - rd) : 0.f;
                     Z *= sc; M *= sc;
@@ -330,7 +375,7 @@ __device__ __forceinline__ void shp_fwd_body(const ShpFwdArgs& a, const int bx, 
                     const size_t col = (size_t)be * ae->ld + ae->col0 + (size_t)kk * ae->C + c;
                     const size_t sidx = ((size_t)be * ae->K + kk) * ae->C + c;
                     float pout;
-                    if (ae->gate == GATE_RBF) {
+                    if (TWIN || ae->gate == GATE_RBF) {
                         pout = best;                       // = p[t*] * (1 + s - s): Shapelet.py:81-82
                     } else {
                         const float th = ae->thr[(size_t)kk * ae->C + c];
@@ -347,14 +392,21 @@ __device__ __forceinline__ void shp_fwd_body(const ShpFwdArgs& a, const int bx, 
     }
 }
 
-template <int TT, int KT, int DIST>
+template <int TT, int KT, int DIST, bool TWIN = false>
 __global__ void __launch_bounds__(256, 4) shp_fwd_kernel(const ShpFwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    shp_fwd_body<TT, KT, DIST>(a, blockIdx.x, blockIdx.y, smem);
+    shp_fwd_body<TT, KT, DIST, TWIN>(a, blockIdx.x, blockIdx.y, smem);
 }
 
 template <int TT, int KT, int DIST>
 static void shp_fwd_launch(const ShpFwdArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
+    // the twin (FWD_TWIN_TTS): K_T = 5, L1, RBF gate, one pass, one wave per block
+    if constexpr (((FWD_TWIN_TTS >> TT) & 1u) != 0 && KT == 5 && DIST == DIST_L1) {
+        if (a.gate == GATE_RBF && a.npass == 1 && block.x == 64 && lds <= 64 * 1024) {
+            hipLaunchKernelGGL((shp_fwd_kernel<TT, KT, DIST, true>), grid, block, lds, s, a);
+            return;
+        }
+    }
     if (lds > 64 * 1024)      // long rows (EigenWorms: T = 17 984 = 72 KB): a CU of gfx950 has 160 KB of LDS, the default cap is 64
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&shp_fwd_kernel<TT, KT, DIST>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
