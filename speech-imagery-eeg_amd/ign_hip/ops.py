@@ -958,6 +958,23 @@ def _bl_strides(t, name):
     return t.stride(0), t.stride(1)
 
 
+def _attn_operand_ok(t):
+    """What the attention entry points take as q / k / v (attn_check): a dense (H, E) block, batch and sequence strides that are
+    positive multiples of 4 elements, a 16-byte aligned base."""
+    return (t.stride(3) == 1 and t.stride(2) == t.shape[3] and t.stride(0) > 0 and t.stride(0) % 4 == 0
+            and t.stride(1) > 0 and t.stride(1) % 4 == 0 and t.data_ptr() % 16 == 0)
+
+
+def _attn_operand(t):
+    """t itself where the kernels can read it in place (a strided view of a packed projection), else a copy.  A batch-expanded
+    operand (stride 0) is copied; so is one that torch already calls contiguous but the kernels refuse (a misaligned base, a
+    size-1 axis with stride 0), which `.contiguous()` would hand back unchanged."""
+    if _attn_operand_ok(t):
+        return t
+    c = t.contiguous()
+    return c if _attn_operand_ok(c) else t.clone(memory_format=torch.contiguous_format)
+
+
 # Attention dropout (include/ign_abi.h, "Attention dropout"): arithmetic selectors of ign_attn_fwd_dropout / ign_attn_bwd_dropout
 ATTN_MATH_F32, ATTN_MATH_X6, ATTN_MATH_BF16, ATTN_MATH_H3 = 0, 1, 2, 3
 
@@ -985,9 +1002,18 @@ def _dropout_seed(p):
     return lo | (hi << 32)
 
 
-def _attn_arith(E, autocast, bwd):
+def _attn_arith(E, autocast, bwd, grad=False):
     """The arithmetic (ATTN_MATH_*) of the attention forward (bwd False) or backward at head width E: the one place that reads
-    ATTN_MATH; the split kernels follow the dense layers (_dense_arith) onto the fp16 planes."""
+    ATTN_MATH; the split kernels follow the dense layers (_dense_arith) onto the fp16 planes.
+    grad: the forward of a call that will be differentiated.  Where the backward runs the fp32-MFMA kernels (E = 128) that forward
+    runs them too: the backward forms p = exp(s - lse) from ITS scores, and dq = scale sum_j p_j (dP_j - delta) k_j cancels over the
+    keys only as far as lse and delta = dO . out come from the same p.  An lse from the split forward differs per key by the fp32
+    rounding of the score (2e-6 at |s| = 20), which rows of nearly collinear keys amplify (9e-5 of max |dq| against 1e-5 with one
+    family: tests/test_gpu_attn_edges.py, the rising / falling regimes).  Up to E = 64 forward and backward share a family.
+    The caller passes ctx.needs_input_grad, which ignores the grad mode: a leaf that requires grad takes this forward under
+    torch.no_grad() too (slower, never wrong).  Cost at E = 128: DESIGN 4.4."""
+    if grad and not bwd and _attn_arith(E, autocast, True) == ATTN_MATH_F32:
+        return ATTN_MATH_F32
     if autocast and E <= 64:
         return ATTN_MATH_BF16     # inside an autocast region (the reference's default mode): operands rounded to bf16, one product
     if ATTN_MATH == "bf16x6" and _dense_arith(False) == GEMM_H3 and E <= 64:
@@ -1052,21 +1078,20 @@ class AttentionFn(torch.autograd.Function):
         _need_gpu("attention", q, k, v)
         B, L, H, E = q.shape
         S = k.shape[1]
-        fix = lambda t: t if (t.stride(3) == 1 and t.stride(2) == E and t.stride(0) % 4 == 0 and t.stride(1) % 4 == 0
-                              and t.data_ptr() % 16 == 0) else t.contiguous()
-        q, k, v = fix(q), fix(k), fix(v)
+        q, k, v = _attn_operand(q), _attn_operand(k), _attn_operand(v)
         out = torch.empty(B, L, H, E, device=q.device, dtype=torch.float32)
         lse = torch.empty(B, H, L, device=q.device, dtype=torch.float32)
         ctx.strides = (*_bl_strides(q, "q"), *_bl_strides(k, "k"), *_bl_strides(v, "v"))
         autocast = torch.is_autocast_enabled()
-        ctx.arith, ctx.bwd_arith = _attn_arith(E, autocast, False), _attn_arith(E, autocast, True)
+        ctx.arith = _attn_arith(E, autocast, False, any(ctx.needs_input_grad[:3]))
+        ctx.bwd_arith = _attn_arith(E, autocast, True)
         ctx.p, ctx.seed, ctx.scale = float(dropout_p), int(seed), float(scale)
         ctx.bounds = (tensor_bound(q), tensor_bound(k), tensor_bound(v)) if ctx.arith == ATTN_MATH_H3 else (None,) * 3
         _attn_fwd(ctx, q, k, v, out, lse)
         ctx.save_for_backward(q, k, v, out, lse)
         if not need_weights:
             return out
-        # the map of this call: same q / k (after `fix`), lse, arithmetic, bounds and seed as the forward above
+        # the map of this call: same q / k (after _attn_operand), lse, arithmetic, bounds and seed as the forward above
         attn = torch.empty(B, H, L, S, device=q.device, dtype=torch.float32)
         _lib.check(_lib.lib().ign_attn_probs(_ptr(q), _ptr(k), _ptr(lse), _ptr(attn), B, L, S, H, E, *ctx.strides[:4], ctx.scale,
                                              _stream(), ctx.arith, _ptr(ctx.bounds[0]), _ptr(ctx.bounds[1]), ctx.p, ctx.seed),
