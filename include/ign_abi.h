@@ -602,7 +602,9 @@ int ign_attn_probs(const float* q, const float* k, const float* lse, float* attn
  * Replaces nn.Linear at IGN/model/Shapelet.py:171,200 (SBM head), IGN/model/Transformer.py:72,109,
  * IGN/model/FullyConvNet.py:50,58.  Backward: gX (B,ldx) and/or gW (N,F), gbias (N) (any may be NULL); sums over the
  * batch run in ascending order, gX sums the classes in ascending order (deterministic).  One launch per call at any N
- * (N > 16: 16-class chunks as an extra grid dimension).  gW stages g in LDS: B*N <= 10240 for N <= 16, B <= 640 above.  */
+ * (N > 16: 16-class chunks as an extra grid dimension).  gW stages g in LDS: B*N <= 10240 for N <= 16, B <= 640 above
+ * (IGN_E_TOOBIG otherwise, whichever outputs are asked for).  gbias is written by the weight-gradient blocks: with gW NULL it
+ * is not touched.                                                                                                          */
 int ign_head_fwd(const float* X, const float* W, const float* bias, float* out, int B, int F, int N, long long ldx,
                  void* stream);
 int ign_head_bwd(const float* g_out, const float* X, const float* W, float* gX, float* gW, float* gbias,
@@ -679,8 +681,10 @@ int ign_diversity_fwd_bwd(const float* w_kcl, float* loss_part_c, float* gw_kcl,
  * gradients in ONE launch:  loss_out[0] = lambda_reg * mean|W| + lambda_div * sum_g diversity_g  (G = 0 skips the diversity
  * term, as the reference does for lambda_div <= 0);  gW_reg (nW) = lambda_reg * sign(W) / nW (sign(0) = 0);  gw_kcl[g] (K,C,L) =
  * lambda_div * d diversity_g / d w.  Per-block partials are combined in a fixed order by the block that finishes last (bitwise
- * reproducible).  workspace: ign_sbm_reg_workspace_bytes() bytes, ZERO-FILLED ONCE by the caller and then owned by one model on
- * one stream (the kernel re-arms its ticket counter itself).  G <= 8, K <= 16.                                             */
+ * reproducible).  workspace: ign_sbm_reg_workspace_bytes() bytes, ZERO-FILLED ONCE by the caller and then owned by one stream;
+ * never written by anyone else.  Layout: word 0 is the ticket counter (0 between calls: the kernel re-arms it), words 1 .. 3 are
+ * spare, the partials start at word 4.  Because the ticket does not move with the number of blocks, a buffer sized for the largest
+ * configuration serves calls of ANY smaller (G, C, nW) in any order -- each call writes its loss.  G <= 8, K <= 16.          */
 size_t ign_sbm_reg_workspace_bytes(int G, int C, long long nW);
 int ign_sbm_reg_fwd_bwd(const float* W, float* gW_reg, long long nW, float lambda_reg, int G, const float* const* w_kcl,
                         float* const* gw_kcl, const int* K, const int* L, int C, float lambda_div, float eps, float* loss_out,

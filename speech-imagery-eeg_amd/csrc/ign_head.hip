@@ -361,6 +361,7 @@ __global__ void __launch_bounds__(256) diversity_kernel(const float* __restrict_
 // a fixed tree), so the result is bitwise reproducible although the arrival order is not.  Cross-block visibility follows the
 // producer / consumer recipe of the MI355X guide (agent-scope release before the ticket, acquire after it, sc1 loads).
 constexpr int REG_GMAX = 8;
+constexpr int REG_TICKET_WORD = 0, REG_PARTS_WORD = 4;      // workspace words: [ticket, 3 spare, nblk partials]
 struct RegTable {
     const float* w[REG_GMAX];
     float* gw[REG_GMAX];
@@ -449,8 +450,10 @@ extern "C" int ign_sbm_reg_fwd_bwd(const float* W, float* gW_reg, long long nW, 
     const int nwb = (int)((nW + 1023) / 1024);
     const int nblk = G * C + nwb;
     if (nblk <= 0) { ign_set_error("%s: nothing to do", who); return IGN_E_ARG; }
-    float* parts = (float*)workspace;
-    unsigned int* ticket = (unsigned int*)(parts + nblk);      // the caller zero-fills the workspace ONCE; the kernel re-arms it
+    // The caller zero-fills the workspace ONCE; the kernel re-arms it.  The ticket is word REG_TICKET_WORD whatever nblk is, so calls
+    // of different sizes may follow each other on one buffer (behind the partials it would sit on a stale partial of a larger call).
+    unsigned int* ticket = (unsigned int*)workspace + REG_TICKET_WORD;
+    float* parts = (float*)workspace + REG_PARTS_WORD;
     IgnScopedTimer tm("sbm_reg", (hipStream_t)stream);
     hipLaunchKernelGGL(sbm_reg_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, t, G, C, W, gW_reg, nW, nwb, lambda_reg,
                        lambda_div, eps, parts, ticket, loss_out);
