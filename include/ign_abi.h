@@ -476,6 +476,32 @@ int ign_warp_btc(const float* x_btc, float* out_btc, const int32_t* len_b, int B
 int ign_warp_map(unsigned long long seed, int b, int n, float twarp, float mwarp, float wwarp, int knots, float prob,
                  float* phi_n, float* gain_n);
 
+/* Evidence maps (csrc/ign_evidence.hip, rule: csrc/ign_evidence.h; utils/evidence.py, run.py --evidence): the logit of class
+ * n_b = target[b] laid out over the input, from what the forward already produced.  No workspace, no atomics, every output element
+ * written exactly once (zeros included), bitwise repeatable.  target (B) int32 and scale (B) float32 (NULL: no scaling) on the DEVICE.
+ *
+ * ign_shapelet_evidence_bank: the linear-head shapelet expert.  p, t (B,ld) = P and Tstar of the bank forward, W (N,ld) the head's
+ *   weight, feature f = col0[g] + k*C + c, window [t*stride_g, t*stride_g + L_g) on electrode c.  out (B,T,C):
+ *     out[b,s,c] = scale[b] * sum over g, then k ascending, of fl(fl(W[n_b,f] * p[b,f]) * invL[g]) where the window covers s,
+ *   summed from 0.0f, one fp32 rounding per operation (no fma); invL[g] = 1.0f / L[g] is the HOST's.  A feature with t outside
+ *   [0, Tw_g), Tw_g = (T - L_g) / stride_g + 1, (t = -1: no window under --mask_padding) and a sample whose target lies outside
+ *   [0, N) contribute nothing.  Host tables K, L, stride, col0, invL of G groups.  G outside 1..8, col0 / ld that do not tile the
+ *   row as col0[g+1] = col0[g] + K[g]*C with ld the total, L[g] outside 1..T, stride < 1, a null pointer: IGN_E_ARG;
+ *   T*C >= 2^31 - 65536: IGN_E_TOOBIG.  Nothing is launched on an error.
+ * ign_bn_relu_cam_fwd: the FCN expert, on block 3's time axis.  y_last (B,Tl,Cl) the raw output of the last convolution, a, b (Cl)
+ *   the BatchNorm affine, head_w (N,Cl):  cam[b,t] = scale[b] * (1/Tl) * sum_c head_w[n_b,c] * relu(fma(a_c, y, b_c)), so that
+ *   sum_t cam[b,t] + bias[n_b] is the expert's logit.  One read of y_last; the sum over c runs in a fixed order inside a wave.
+ *   Cl % 4 == 0, Cl <= 1024 as the other ign_bn_* entry points; a target outside [0, N) gives a zero row.
+ * ign_cam_spread: cam (B,Tl) -> out (B,T), T = Tl + R - 1, each cam[b,t] spread evenly over the R input samples it saw:
+ *     out[b,s] = fl(invR * sum_{t = max(0, s-R+1)}^{min(s, Tl-1)} cam[b,t]),  t ascending from 0.0f, invR = 1.0f / R the HOST's.
+ *   R < 1 or Tl < 1: IGN_E_ARG.                                                                                                 */
+int ign_shapelet_evidence_bank(const float* p, const int32_t* t, const float* W, const int32_t* target, const float* scale, int ld,
+                               int G, const int* K, const int* L, const int* stride, const int* col0, const float* invL, float* out,
+                               int B, int T, int C, int N, void* stream);
+int ign_bn_relu_cam_fwd(const float* y_last, const float* a, const float* b, const float* head_w, const int32_t* target,
+                        const float* scale, float* cam, int B, int Tl, int Cl, int N, void* stream);
+int ign_cam_spread(const float* cam, float* out, int B, int Tl, int R, float invR, void* stream);
+
 /* Fused attention core softmax(scale * Q K^T) V, exact fp32 on the matrix cores (v_mfma_f32_32x32x2_f32), scores never
  * materialised.  Replaces IGN/layers/SelfAttention_Family.py:56-75 (FullAttention: no mask; dropout 0 here -- dropout p > 0
  * is ign_attn_*_dropout below) and the attention inside nn.TransformerEncoderLayer of IGN/model/eegcnn.py:219-228.

@@ -807,6 +807,25 @@ class Experiment(object):
             return torch.empty(0, self.args.seq_len, self.args.enc_in)
         return torch.cat(out)
 
+    def evidence(self, loader=None, target=None, explain="sbm"):
+        """Evidence maps over `loader` (default: the test loader) -> utils.evidence.Evidence of host tensors concatenated over the
+        batches: per sample the share of a class logit that comes from every (time, electrode) through the shapelet expert (N,T,C),
+        from every time step through the FCN expert (N,T) and from the bias (utils.evidence.evidence_map; SBM / LTS / InterpGN).
+        `target`: an int, or None for each sample's predicted class.  `explain`: "sbm", "gated" (with --gating_value, as test
+        applies it) or "dnn".  The loader's padding mask reaches the shapelet expert (--mask_padding)."""
+        import dataclasses
+        from utils.evidence import Evidence, evidence_map
+        parts = []
+        for batch_x, label, padding_mask in (self.test_loader if loader is None else loader):
+            if batch_x.size(0) == 0:
+                continue
+            batch_x, _, padding_mask = self._to_device(batch_x, label, padding_mask)
+            ev = evidence_map(self.model, batch_x, target, explain=explain, gating_value=self.args.gating_value, mask=padding_mask)
+            parts.append({f.name: getattr(ev, f.name) for f in dataclasses.fields(ev)})
+        if not parts:
+            return Evidence()
+        return Evidence(**{k: (torch.cat([p[k].cpu() for p in parts]) if parts[0][k] is not None else None) for k in parts[0]})
+
     def test(self, save_csv=True, result_dir=None):
         """-> (test_loss, ClassificationResult, None)   (:828-1138; ``gating_value`` is applied here only)."""
         if result_dir is not None:

@@ -173,6 +173,9 @@ SIGNATURES = {
     "ign_mix_btc": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
     "ign_warp_btc": (ci, [vp, vp, vp, ci, ci, ci, ctypes.c_ulonglong, cf, cf, cf, ci, cf, vp]),
     "ign_warp_map": (ci, [ctypes.c_ulonglong, ci, ci, cf, cf, cf, ci, cf, c_f, c_f]),
+    "ign_shapelet_evidence_bank": (ci, [vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
+    "ign_bn_relu_cam_fwd": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
+    "ign_cam_spread": (ci, [vp, vp, ci, ci, ci, cf, vp]),
     "ign_eeg_preprocess_ws_bytes": (sz, [ci, ci, ci, ci, ci, ci, ci]),
     "ign_eeg_preprocess_nct_to_btc": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, vp]),
     "ign_eeg_filterbank_ws_bytes": (sz, [ci, ci, ci, ci, ci, ci, ci, ci]),

@@ -85,7 +85,7 @@ class FcnBodyFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, states_arith, *params):
         L = _lib.lib()
-        states, arith, has_head, input_grad = states_arith
+        states, arith, has_head, input_grad, keep = states_arith
         head_w, head_b = (params[-2], params[-1]) if has_head else (None, None)
         if has_head:
             params = params[:-2]
@@ -181,6 +181,9 @@ class FcnBodyFn(torch.autograd.Function):
             shapes.append((Co, Ci, k, Tin, Tout))
             pa, pb = a, bb
         y_last = inputs[-1]
+        if keep is not None:
+            # opt-in (FullyConvNetwork.keep_last): what the pooling launch below reads, for ops.fcn_cam -- references, no copy
+            keep.last_block = (y_last, pa, pb)
         Cl, Tl = y_last.shape[2], y_last.shape[1]
         pooled = torch.empty(B, Cl, **f32)
         head = None
@@ -324,14 +327,17 @@ class FcnBodyFn(torch.autograd.Function):
         return (gx, None, *grads, *head_grads)
 
 
-def fcn_body(x, blocks, math=None, head=None, input_grad=False):
+def fcn_body(x, blocks, math=None, head=None, input_grad=False, keep=None):
     """x (B,T,C) float32 on the GPU; blocks = [(conv1d, batchnorm1d), ...] -> pooled (B, C_last).
     `math`: arithmetic of the GEMMs (see CONV_MATH, _fcn_arith); default = "bf16" inside an autocast region, else CONV_MATH.
     `head`: an nn.Linear over the pooled channels (<= ops.HEAD_NMAX outputs) -> its logits (B, N) are returned instead, computed by the
     pooling launch.
     `input_grad`: with it (and x.requires_grad) the backward also returns dL/dx -- block 1's data-gradient GEMM into the raw series
     (ign_clconv_dgrad_input*).  Off (the default) an input that requires a gradient makes the backward raise: inputs are data.  The
-    parameter gradients are the same bits either way; with every parameter frozen the backward is input-only (no weight gradient)."""
+    parameter gradients are the same bits either way; with every parameter frozen the backward is input-only (no weight gradient).
+    `keep`: an object (the FullyConvNetwork with `keep_last` on) on which this forward leaves `last_block = (y_last, a_last, b_last)`:
+    the raw output of the last convolution and that block's BatchNorm affine, as the pooling launch reads them.  None (the default):
+    nothing is kept, and no launch or allocation differs."""
     states = [BnState(bn) for _, bn in blocks]            # (the step counters are bumped by the node's prologue launch)
     arith = _fcn_arith(math, torch.is_autocast_enabled(), states)
     params = []
@@ -345,5 +351,5 @@ def fcn_body(x, blocks, math=None, head=None, input_grad=False):
         if head.weight.shape[0] > ops.HEAD_NMAX:
             raise _lib.IgnError(f"fcn_body: the fused head covers up to {ops.HEAD_NMAX} outputs")
         # (a head without bias passes a None placeholder: autograd.Function accepts non-tensor inputs)
-        return FcnBodyFn.apply(x, (states, arith, True, bool(input_grad)), *params, head.weight, head.bias)
-    return FcnBodyFn.apply(x, (states, arith, False, bool(input_grad)), *params)
+        return FcnBodyFn.apply(x, (states, arith, True, bool(input_grad), keep), *params, head.weight, head.bias)
+    return FcnBodyFn.apply(x, (states, arith, False, bool(input_grad), keep), *params)

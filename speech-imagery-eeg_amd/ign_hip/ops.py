@@ -876,6 +876,130 @@ def shapelet_project_bank(xn, d, t, w_shapes, strides, sample0, states=None):
     return new
 
 
+def _evidence_target(name, target, B, N, bad=None):
+    """The explained class per sample as the evidence kernels take it: int32 (B,) on the GPU, every entry inside [0, N).  `bad`: a
+    further 0-dim device flag with the message to raise when it is set, read in the same device-to-host copy."""
+    if not torch.is_tensor(target) or not target.is_cuda or target.dtype not in (torch.int32, torch.int64) \
+            or tuple(target.shape) != (B,):
+        what = f"{target.dtype} {tuple(target.shape)} on {target.device}" if torch.is_tensor(target) else type(target).__name__
+        raise _lib.IgnError(f"{name}: target must be an integer tensor of shape ({B},) on the GPU, got {what}")
+    flags = [((target < 0) | (target >= N)).any()] + ([bad[0]] if bad is not None else [])
+    flags = torch.stack(flags).tolist()
+    if flags[0]:
+        raise _lib.IgnError(f"{name}: target outside [0, {N}): {target.tolist()}")
+    if bad is not None and flags[1]:
+        raise _lib.IgnError(f"{name}: {bad[1]()}")
+    return target.to(torch.int32).contiguous()
+
+
+_EVIDENCE_TW = {}          # (device, Ks, Ls, strides, C, T) -> int32 (ld,): windows per feature column, for the check of t
+
+
+def _evidence_scale(name, scale, B):
+    if scale is None:
+        return None
+    _need_gpu(name, scale)
+    if tuple(scale.shape) != (B,):
+        raise _lib.IgnError(f"{name}: scale must be a float32 tensor of shape ({B},), got {tuple(scale.shape)}")
+    return scale.detach().contiguous()
+
+
+def shapelet_evidence(p, t, W, target, Ks, Ls, strides, C, T, scale=None):
+    """The linear-head shapelet expert's share of the logit of class target[b], laid out over the input (ign_shapelet_evidence_bank;
+    the rule is csrc/ign_evidence.h, restated in utils/evidence.py:evidence_rule and equal to it bit for bit) -> (B,T,C) float32.
+    `p` (B,ld) float32 and `t` (B,ld) int32: P and Tstar of shapelet_bank(..., return_tstar=True), feature order g*K*C + k*C + c;
+    `W` (N,ld) the head's weight; `target` (B,) integer tensor on the GPU; `Ks`, `Ls`, `strides`: shapelets, length and window step
+    of each length group; `scale`: None or a float32 (B,) factor per sample (the gate value), applied once after the sum.
+    Feature f contributes fl(fl(W[n_b,f] * p[b,f]) * fl(1/L_g)) to every sample of its matched window [t*stride, t*stride + L) on its electrode;
+    t = -1 (no window under --mask_padding) contributes nothing.  Nothing is launched when an argument is refused: a target outside
+    [0, N), a `t` outside [-1, Tw_g), shapes that do not fit.  No gradient."""
+    name = "shapelet_evidence"
+    _need_gpu(name, p, W, scale)
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.int32:
+        what = f"{t.dtype} on {t.device}" if torch.is_tensor(t) else type(t).__name__
+        raise _lib.IgnError(f"{name}: t must be an int32 tensor on the GPU, got {what}")
+    G = len(Ks)
+    if not 1 <= G <= BANK_MAX_GROUPS or len(Ls) != G or len(strides) != G:
+        raise _lib.IgnError(f"{name}: {G} groups (1..{BANK_MAX_GROUPS}) with {len(Ls)} lengths and {len(strides)} strides")
+    Ks, Ls, strides, C, T = [int(k) for k in Ks], [int(v) for v in Ls], [int(s) for s in strides], int(C), int(T)
+    if C < 1 or T < 1 or min(Ks) < 1 or min(strides) < 1 or min(Ls) < 1 or max(Ls) > T:
+        raise _lib.IgnError(f"{name}: K={Ks} L={Ls} stride={strides} do not fit C={C}, T={T}")
+    ld = sum(Ks) * C
+    if p.dim() != 2 or p.shape[1] != ld or t.shape != p.shape or W.dim() != 2 or W.shape[1] != ld:
+        raise _lib.IgnError(f"{name}: p, t must be (B,{ld}) and W (N,{ld}) for K={Ks}, C={C}; got {tuple(p.shape)}, {tuple(t.shape)}, "
+                            f"{tuple(W.shape)}")
+    B, N = p.shape[0], W.shape[0]
+    out = torch.empty(B, T, C, device=p.device, dtype=torch.float32)
+    if B == 0:
+        return out
+    p, t, W = p.detach().contiguous(), t.contiguous(), W.detach().contiguous()
+    Tws = [(T - Ls[g]) // strides[g] + 1 for g in range(G)]
+    col0s = [sum(Ks[:g]) * C for g in range(G)]
+    key = (p.device, tuple(Ks), tuple(Ls), tuple(strides), C, T)
+    tw = _EVIDENCE_TW.get(key)
+    if tw is None:
+        if len(_EVIDENCE_TW) >= 16:
+            _EVIDENCE_TW.clear()
+        tw = _EVIDENCE_TW[key] = torch.cat([torch.full((Ks[g] * C,), Tws[g], dtype=torch.int32) for g in range(G)]).to(p.device)
+    # device data is checked here, with the target, in one device-to-host copy: the launch below trusts neither
+    target = _evidence_target(name, target, B, N, bad=(((t < -1) | (t >= tw)).any(), lambda: (
+        f"a match location outside [-1, Tw_g) with Tw = {Tws}: per group (min, max) = "
+        f"{[(int(t[:, c0:c0 + k * C].min()), int(t[:, c0:c0 + k * C].max())) for c0, k in zip(col0s, Ks)]}")))
+    scale = _evidence_scale(name, scale, B)
+    ints, floats = ctypes.c_int * G, ctypes.c_float * G
+    import numpy as np
+    invL = [float(np.float32(1.0) / np.float32(v)) for v in Ls]
+    _lib.check(_lib.lib().ign_shapelet_evidence_bank(_ptr(p), _ptr(t), _ptr(W), _ptr(target), _ptr(scale), ld, G, ints(*Ks), ints(*Ls),
+                                                     ints(*strides), ints(*col0s), floats(*invL), _ptr(out), B, T, C, N, _stream()),
+               "ign_shapelet_evidence_bank")
+    return out
+
+
+def fcn_cam(y_last, a, b, head_w, target, scale=None):
+    """Class activation map of the FCN expert on its last block's time axis (ign_bn_relu_cam_fwd) -> (B,Tl) float32:
+    cam[b,t] = scale[b] * (1/Tl) * sum_c head_w[target[b], c] * relu(a_c * y_last[b,t,c] + b_c), so cam.sum(1) + bias[target] is the
+    expert's logit.  `y_last` (B,Tl,Cl) the raw output of the last convolution and `a`, `b` (Cl,) its eval-mode BatchNorm affine
+    (what FullyConvNetwork.keep_last leaves in `last_block`), `head_w` (N,Cl), `target` (B,) integer tensor on the GPU, `scale` None
+    or float32 (B,).  Cl % 4 == 0, Cl <= 1024.  No gradient."""
+    name = "fcn_cam"
+    _need_gpu(name, y_last, a, b, head_w, scale)
+    if y_last.dim() != 3 or head_w.dim() != 2:
+        raise _lib.IgnError(f"{name}: y_last must be (B,Tl,Cl) and head_w (N,Cl), got {tuple(y_last.shape)} and {tuple(head_w.shape)}")
+    B, Tl, Cl = y_last.shape
+    N = head_w.shape[0]
+    if Cl % 4 or not 4 <= Cl <= 1024 or Tl < 1 or tuple(a.shape) != (Cl,) or tuple(b.shape) != (Cl,) or head_w.shape[1] != Cl:
+        raise _lib.IgnError(f"{name}: y_last {tuple(y_last.shape)} needs Tl >= 1, Cl % 4 == 0, Cl <= 1024, a and b of shape ({Cl},) and "
+                            f"head_w (N,{Cl}); got a {tuple(a.shape)}, b {tuple(b.shape)}, head_w {tuple(head_w.shape)}")
+    cam = torch.empty(B, Tl, device=y_last.device, dtype=torch.float32)
+    if B == 0:
+        return cam
+    target = _evidence_target(name, target, B, N)
+    scale = _evidence_scale(name, scale, B)
+    _lib.check(_lib.lib().ign_bn_relu_cam_fwd(_ptr(y_last.detach().contiguous()), _ptr(a.detach().contiguous()),
+                                              _ptr(b.detach().contiguous()), _ptr(head_w.detach().contiguous()), _ptr(target),
+                                              _ptr(scale), _ptr(cam), B, Tl, Cl, N, _stream()), "ign_bn_relu_cam_fwd")
+    return cam
+
+
+def cam_spread(cam, R):
+    """cam (B,Tl) on the FCN's last time axis -> (B,T) on the input axis, T = Tl + R - 1 (ign_cam_spread): every cam[b,t] spread
+    evenly over the R = k1 + k2 + k3 - 2 input samples it saw, out[b,s] = fl(fl(1/R) * sum_{t = max(0,s-R+1)}^{min(s,Tl-1)} cam[b,t])
+    with t ascending -- bitwise equal to utils/evidence.py:cam_spread_rule; out.sum(1) is cam.sum(1) up to rounding."""
+    name = "cam_spread"
+    _need_gpu(name, cam)
+    R = int(R)
+    if cam.dim() != 2 or cam.shape[1] < 1 or R < 1:
+        raise _lib.IgnError(f"{name}: cam must be (B,Tl) with Tl >= 1 and R >= 1, got {tuple(cam.shape)} and R={R}")
+    B, Tl = cam.shape
+    out = torch.empty(B, Tl + R - 1, device=cam.device, dtype=torch.float32)
+    if B == 0:
+        return out
+    import numpy as np
+    _lib.check(_lib.lib().ign_cam_spread(_ptr(cam.detach().contiguous()), _ptr(out), B, Tl, R, float(np.float32(1.0) / np.float32(R)),
+                                         _stream()), "ign_cam_spread")
+    return out
+
+
 class SbmFn(torch.autograd.Function):
     """The shapelet bottleneck model behind the instance norm as ONE autograd node: shapelet bank (every length group) ->
     linear class head (optional) -> both regularisers (IGN/model/Shapelet.py:190-210, 217-230).

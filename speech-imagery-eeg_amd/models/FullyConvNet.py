@@ -18,6 +18,10 @@ class FullyConvNetwork(nn.Module):
     # Opt-in: with it an input that requires a gradient gets one (block 1's data-gradient GEMM into the raw series,
     # ign_clconv_dgrad_input*; utils.saliency sets it for explain="gated" / "dnn").  Off, the backward refuses: inputs are data.
     input_grad = False
+    # Opt-in: while it is true every forward leaves `last_block = (y_last, a_last, b_last)` on the module -- the raw output of block 3's
+    # convolution and its BatchNorm affine, what the pooling launch reads -- for the class activation map (ops.fcn_cam;
+    # utils.evidence sets it for the duration of one call).  Off, nothing is kept and the forward is launch for launch what it was.
+    keep_last = False
 
     def __init__(self, configs):
         super().__init__()
@@ -36,6 +40,7 @@ class FullyConvNetwork(nn.Module):
         # handed to a library convolution
         x = x if x.dtype == torch.float32 else x.float()
         blocks = [(b[0], b[1]) for b in (self.block1, self.block2, self.block3)]
+        keep = self if self.keep_last else None
         if ops.head_fits(x.shape[0], self.fc.weight.shape[0]) and not torch.is_autocast_enabled():
-            return fcn.fcn_body(x, blocks, head=self.fc, input_grad=self.input_grad)      # class head inside the pooling launch
-        return ops.head_linear(fcn.fcn_body(x, blocks, input_grad=self.input_grad), self.fc.weight, self.fc.bias)
+            return fcn.fcn_body(x, blocks, head=self.fc, input_grad=self.input_grad, keep=keep)   # class head inside the pooling launch
+        return ops.head_linear(fcn.fcn_body(x, blocks, input_grad=self.input_grad, keep=keep), self.fc.weight, self.fc.bias)

@@ -27,6 +27,10 @@ Differences, all repairs of fork defects listed in SURVEY section 0:
     along time on the device in one launch, in front of ``--augment``: a smooth random speed curve (twarp), a smooth random gain
     curve shared by the channels (mwarp) and one window stretched or compressed by 2 (wwarp), each inside the sample's own length;
     classification and regression; validation / test never warp; the default ``none`` changes nothing;
+  * ``--evidence sbm|gated|dnn`` writes ``evidence.npz`` beside the test results after the test: per test sample the predicted
+    class's logit laid out over time and electrodes (the shapelet expert's (N,T,C) map, the FCN expert's (N,T) map and its bias),
+    which sum to that logit, plus eta, logit, target and contrib (utils/evidence.py); needs ``--sbm_cls linear``; the default
+    ``none`` imports and launches nothing;
   * ``--eeg_preprocess band=8:30,decimate=2,fit`` (``--data EEG`` / ``EEG3``; any subset of sfreq=F, band=LO:HI, decimate=Q, taps=M,
     edge=reflect|zero, fit) filters the raw CHISCO shards with a zero-phase FIR band-pass, decimates them and, with ``fit``, crops /
     zero-pads them to ``--target_channels`` x ``--target_timepoints`` in front of the standardisation -- on the device in the
@@ -180,6 +184,13 @@ def build_parser():
                         "one window of R * length by 2 and rescales the sample to its length; rates in [0, 1).  knots=K (1..8, "
                         "default 4) interior knots of the two curves; prob in (0, 1] is the chance that a sample is warped at all.  "
                         "Reproducible from --seed")
+    p.add_argument("--evidence", type=str, default='none', choices=('none', 'sbm', 'gated', 'dnn'),
+                   help="after the test, write evidence.npz beside the test results: per test sample the share of the predicted "
+                        "class's logit that comes from every (time, electrode) through the shapelet expert (sbm, (N,T,C)), from "
+                        "every time step through the FCN expert (dnn, (N,T)) and from its bias (remainder), which sum to the logit; "
+                        "plus eta, logit, target and contrib = W[target] * p, the reference's ranking key of the shapelets.  sbm: the "
+                        "interpretable expert of SBM / LTS / InterpGN; dnn: the FCN expert; gated: the mixture InterpGN predicts "
+                        "with, --gating_value applied.  Needs --sbm_cls linear (the other heads are not additive in p)")
     p.add_argument("--eeg_preprocess", type=str, default='none',
                    help="--data EEG / EEG3: preprocessing of the raw shards in front of the standardisation, on the device: none, or a "
                         "comma list of sfreq=F (Hz, default 500), band=LO:HI (Hz, either side may be empty), decimate=Q, taps=M "
@@ -388,6 +399,17 @@ def main(argv=None):
                 pickle.dump({'test_loss': test_loss, 'test_metrics': test_metrics, 'test_df': test_df,
                              'args': vars(args)}, f)
             print(f"accuracy: {test_metrics.accuracy:.4f}  loss: {test_metrics.loss:.4f}")
+        if rank == 0 and getattr(args, 'evidence', 'none') != 'none':
+            write_evidence(experiment, args.evidence, f"{os.path.dirname(ckpt)}/evidence.npz")
+
+
+def write_evidence(experiment, explain, path):
+    """--evidence: the maps of Experiment.evidence over the test set as one .npz (the fields of utils.evidence.Evidence that apply)."""
+    import dataclasses
+    ev = experiment.evidence(explain=explain)
+    arrays = {f.name: getattr(ev, f.name).numpy() for f in dataclasses.fields(ev) if getattr(ev, f.name) is not None}
+    np.savez(path, **arrays)
+    print(f"evidence ({explain}): {', '.join(f'{k} {v.shape}' for k, v in arrays.items())} -> {path}")
 
 
 if __name__ == "__main__":

@@ -19,22 +19,23 @@ from models.Shapelet import ShapeBottleneckModel
 EXPLAIN = ("sbm", "gated", "dnn")
 
 
-def _interpretable_expert(model):
+def _interpretable_expert(model, who="input_saliency"):
     if isinstance(model, InterpGN):
         return model.sbm
     if isinstance(model, ShapeBottleneckModel):
         return model
-    raise TypeError(f"input_saliency explains a shapelet expert (SBM, LTS or the SBM inside InterpGN), not {type(model).__name__}")
+    raise TypeError(f"{who} explains a shapelet expert (SBM, LTS or the SBM inside InterpGN), not {type(model).__name__}")
 
 
-def _fcn_expert(model, explain):
-    """The FCN expert behind explain="gated" / "dnn"; the other deep experts have no input-gradient kernels."""
+def _fcn_expert(model, explain, who="input_saliency"):
+    """The FCN expert behind explain="gated" / "dnn"; the other deep experts have no input-gradient (or class-activation) kernels.
+    `who`: the caller named in the error (utils.evidence shares the dispatch)."""
     fcn = model.deep_model if isinstance(model, InterpGN) else model if (explain == "dnn" and isinstance(model, FullyConvNetwork)) else None
     if fcn is None:
         want = "an InterpGN" if explain == "gated" else "an InterpGN or a FullyConvNetwork"
-        raise TypeError(f'input_saliency(explain="{explain}") needs {want} with the FCN deep expert, not {type(model).__name__}')
+        raise TypeError(f'{who}(explain="{explain}") needs {want} with the FCN deep expert, not {type(model).__name__}')
     if not isinstance(fcn, FullyConvNetwork):
-        raise TypeError(f'input_saliency(explain="{explain}"): FCN is the supported deep expert (--dnn_type FCN), '
+        raise TypeError(f'{who}(explain="{explain}"): FCN is the supported deep expert (--dnn_type FCN), '
                         f'not {type(fcn).__name__}')
     return fcn
 
