@@ -502,6 +502,31 @@ int ign_bn_relu_cam_fwd(const float* y_last, const float* a, const float* b, con
                         const float* scale, float* cam, int B, int Tl, int Cl, int N, void* stream);
 int ign_cam_spread(const float* cam, float* out, int B, int Tl, int R, float invR, void* stream);
 
+/* Faithfulness curves (csrc/ign_faithfulness.hip; rule: utils/faithfulness.py rank_rule / perturb_rule; run.py --faithfulness): rank
+ * the cells of every sample by a score map and replace the top k by a baseline -- the deletion / insertion test of an explanation.
+ * score (B,T,Cs) float32, Cs == C (a score per cell) or Cs == 1 (a score per time step, applied to every electrode); flat index
+ * i = t*Cs + c; sample b has n_b = clamp(len_b[b], 0, T) * Cs valid scores (len_b NULL: T * Cs).  All arrays on the DEVICE.
+ *   key(v): u = bits(v); sign set: ~u, else u | 0x80000000 -- a total order on bit patterns (-0 below +0, positive NaNs above +inf,
+ *           nothing special-cased).  Element i precedes i' iff key_i > key_i', or the keys are equal and i < i'.
+ *   selected(b, i, j): i < n_b and (key_i > thr_key[b,j] or (key_i == thr_key[b,j] and i <= thr_idx[b,j])).
+ * ign_rank_threshold: k (B,nk) int32, clamped to [0, n_b] on the device -> thr_key, thr_idx (B,nk) int32 (thr_key holds the uint32
+ *   key's bits): key and flat index of the k-th element in the order above, so that exactly min(k, n_b) elements are selected and
+ *   the sets of ascending k are nested; k = 0 gives (0xffffffff, -1).  One workgroup per sample, an 8-bit radix select over the
+ *   key then over the index bits among tied keys, integer LDS counters only: no workspace, no float atomics, bitwise repeatable, a
+ *   sample's result independent of the batch around it.  nk outside 1..IGN_RANK_MAX_K, a null pointer (len_b may be), a
+ *   non-positive dimension: IGN_E_ARG; T*Cs >= 2^31 - 65536: IGN_E_TOOBIG.
+ * ign_perturb_btc: x (B,T,C) -> out (B,T,C), out of place (overlapping buffers: IGN_E_ARG): for t < len_b, out[b,t,c] = fill[b,c]
+ *   (fill (B,C), NULL: 0.0f) where selected(b, t*Cs + (Cs == C ? c : 0), j) != (insert != 0), elsewhere -- and for t >= len_b -- the
+ *   bits of x[b,t,c].  j is a HOST integer: the launch can be captured.  One read of x and score, one write of out.  Cs not in
+ *   {1, C}, nk outside 1..IGN_RANK_MAX_K, j outside [0, nk), a null x / score / thr_key / thr_idx / out, a non-positive dimension:
+ *   IGN_E_ARG; T*C >= 2^31 - 65536: IGN_E_TOOBIG.
+ * Nothing is launched on an error.  Timing labels rank_threshold, perturb.                                                        */
+#define IGN_RANK_MAX_K 32
+int ign_rank_threshold(const float* score_bts, const int32_t* k_bj, const int32_t* len_b, int32_t* thr_key_bj, int32_t* thr_idx_bj,
+                       int B, int T, int Cs, int nk, void* stream);
+int ign_perturb_btc(const float* x_btc, const float* score_bts, const int32_t* thr_key_bj, const int32_t* thr_idx_bj, int j, int nk,
+                    const float* fill_bc, const int32_t* len_b, float* out_btc, int insert, int B, int T, int C, int Cs, void* stream);
+
 /* Fused attention core softmax(scale * Q K^T) V, exact fp32 on the matrix cores (v_mfma_f32_32x32x2_f32), scores never
  * materialised.  Replaces IGN/layers/SelfAttention_Family.py:56-75 (FullAttention: no mask; dropout 0 here -- dropout p > 0
  * is ign_attn_*_dropout below) and the attention inside nn.TransformerEncoderLayer of IGN/model/eegcnn.py:219-228.

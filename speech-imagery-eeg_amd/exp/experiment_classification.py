@@ -826,6 +826,23 @@ class Experiment(object):
             return Evidence()
         return Evidence(**{k: (torch.cat([p[k].cpu() for p in parts]) if parts[0][k] is not None else None) for k in parts[0]})
 
+    def faithfulness(self, loader=None, target=None, **spec):
+        """Deletion / insertion curves over `loader` (default: the test loader) -> utils.faithfulness.Faithfulness of host tensors
+        concatenated over the batches, the summary numbers taken over all samples.  `spec`: the keyword arguments of
+        utils.faithfulness.faithfulness_curves (explain, attributions, steps, mode, fill, unit, seed); --gating_value is applied as
+        test applies it and the loader's padding mask reaches the model (--mask_padding).  The random ranking of batch i is seeded
+        with seed + i."""
+        from utils.faithfulness import Faithfulness, concat, faithfulness_curves
+        seed = int(spec.pop("seed", 0))
+        parts = []
+        for batch_x, label, padding_mask in (self.test_loader if loader is None else loader):
+            if batch_x.size(0) == 0:
+                continue
+            batch_x, _, padding_mask = self._to_device(batch_x, label, padding_mask)
+            parts.append(faithfulness_curves(self.model, batch_x, mask=padding_mask, target=target, seed=seed + len(parts),
+                                             gating_value=self.args.gating_value, **spec))
+        return concat(parts) if parts else Faithfulness()
+
     def test(self, save_csv=True, result_dir=None):
         """-> (test_loss, ClassificationResult, None)   (:828-1138; ``gating_value`` is applied here only)."""
         if result_dir is not None:

@@ -176,6 +176,8 @@ SIGNATURES = {
     "ign_shapelet_evidence_bank": (ci, [vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
     "ign_bn_relu_cam_fwd": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
     "ign_cam_spread": (ci, [vp, vp, ci, ci, ci, cf, vp]),
+    "ign_rank_threshold": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
+    "ign_perturb_btc": (ci, [vp, vp, vp, vp, ci, ci, vp, vp, vp, ci, ci, ci, ci, ci, vp]),
     "ign_eeg_preprocess_ws_bytes": (sz, [ci, ci, ci, ci, ci, ci, ci]),
     "ign_eeg_preprocess_nct_to_btc": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, vp]),
     "ign_eeg_filterbank_ws_bytes": (sz, [ci, ci, ci, ci, ci, ci, ci, ci]),

@@ -1000,6 +1000,87 @@ def cam_spread(cam, R):
     return out
 
 
+RANK_MAX_K = 32               # IGN_RANK_MAX_K (include/ign_abi.h): most thresholds one ign_rank_threshold call finds per sample
+
+
+def _need_plain(name, what, t, dtype, dim):
+    """An input of the faithfulness ops: a contiguous tensor of `dtype` with `dim` axes on the GPU that needs no gradient."""
+    if not torch.is_tensor(t) or not t.is_cuda:
+        where = f"on {t.device}" if torch.is_tensor(t) else type(t).__name__
+        raise _lib.IgnError(f"{name}: {what} must be a tensor on the GPU, got {where} (there is no CPU path: the numpy restatement "
+                            f"lives in utils/faithfulness.py)")
+    if t.dtype != dtype:
+        raise _lib.IgnError(f"{name}: {what} must be {dtype}, got {t.dtype}")
+    if t.dim() != dim or not t.is_contiguous():
+        raise _lib.IgnError(f"{name}: {what} must be a contiguous tensor with {dim} axes, got shape {tuple(t.shape)} strides "
+                            f"{t.stride()}")
+    if t.requires_grad:
+        raise _lib.IgnError(f"{name}: {what} requires a gradient; ranking and perturbing act on data (there is no backward pass)")
+
+
+def rank_threshold(score, k, lengths=None):
+    """Per sample the thresholds of its top-k sets under a score map (ign_rank_threshold; the rule is utils/faithfulness.py:rank_rule,
+    equal to it bit for bit) -> (thr_key, thr_idx), both int32 (B,nk); thr_key holds the bits of the uint32 key.
+    `score`: float32 (B,T,Cs) -- a score per cell (Cs = C) or per time step (Cs = 1), flat index i = t*Cs + c; `k`: int32 (B,nk),
+    nk <= RANK_MAX_K, clamped to [0, n_b] on the device; `lengths`: int32 (B,) or None -- sample b has n_b = clamp(len_b, 0, T) * Cs
+    scores.  Elements are ordered by descending key (the order-preserving uint32 of the float's bits: -0 below +0, NaNs at the
+    ends), ties to the lowest flat index; the k-th element's (key, index) is returned, (0xffffffff, -1) for k = 0.  Everything is
+    device data: no host sync, one launch for all nk thresholds."""
+    name = "rank_threshold"
+    _need_plain(name, "score", score, torch.float32, 3)
+    _need_plain(name, "k", k, torch.int32, 2)
+    B, T, Cs = score.shape
+    nk = k.shape[1]
+    if k.shape[0] != B or not 1 <= nk <= RANK_MAX_K:
+        raise _lib.IgnError(f"{name}: k must be ({B}, nk) with nk in 1..{RANK_MAX_K}, got {tuple(k.shape)}")
+    thr_key = torch.empty(B, nk, device=score.device, dtype=torch.int32)
+    thr_idx = torch.empty(B, nk, device=score.device, dtype=torch.int32)
+    if B == 0:
+        return thr_key, thr_idx
+    if lengths is not None:
+        lengths = _lengths(name, lengths, B)
+    _lib.check(_lib.lib().ign_rank_threshold(_ptr(score), _ptr(k), _ptr(lengths), _ptr(thr_key), _ptr(thr_idx), B, T, Cs, nk,
+                                             _stream()), "ign_rank_threshold")
+    return thr_key, thr_idx
+
+
+def perturb(x, score, thr_key, thr_idx, j, fill=None, insert=False, lengths=None):
+    """The batch with each sample's top-k cells replaced (ign_perturb_btc; the rule is utils/faithfulness.py:perturb_rule, equal to it
+    bit for bit) -> a new (B,T,C) tensor.  `x`: float32 (B,T,C); `score`: the map the thresholds were taken from, (B,T,C) or (B,T,1);
+    `thr_key`, `thr_idx`: int32 (B,nk) of rank_threshold; `j`: a host integer in [0, nk), the column used; `fill`: float32 (B,C) or
+    None for 0.0; `insert`: keep the selected cells and replace the others; `lengths`: int32 (B,) or None -- from lengths[b] on the
+    sample is copied through.  A cell is selected iff key > thr_key, or key == thr_key and its flat index <= thr_idx.  Every argument
+    but `j` and `insert` is device data, so the call may be captured."""
+    name = "perturb"
+    _need_plain(name, "x", x, torch.float32, 3)
+    _need_plain(name, "score", score, torch.float32, 3)
+    _need_plain(name, "thr_key", thr_key, torch.int32, 2)
+    _need_plain(name, "thr_idx", thr_idx, torch.int32, 2)
+    B, T, C = x.shape
+    Cs = score.shape[2]
+    if tuple(score.shape[:2]) != (B, T) or Cs not in (1, C):
+        raise _lib.IgnError(f"{name}: score must be ({B},{T},{C}) or ({B},{T},1) for x {tuple(x.shape)}, got {tuple(score.shape)}")
+    nk = thr_key.shape[1]
+    if thr_key.shape[0] != B or thr_idx.shape != thr_key.shape or not 1 <= nk <= RANK_MAX_K:
+        raise _lib.IgnError(f"{name}: thr_key and thr_idx must be ({B}, nk) with nk in 1..{RANK_MAX_K}, got {tuple(thr_key.shape)} "
+                            f"and {tuple(thr_idx.shape)}")
+    j = int(j)
+    if not 0 <= j < nk:
+        raise _lib.IgnError(f"{name}: j = {j} outside [0, {nk})")
+    if fill is not None:
+        _need_plain(name, "fill", fill, torch.float32, 2)
+        if tuple(fill.shape) != (B, C):
+            raise _lib.IgnError(f"{name}: fill must be ({B},{C}), got {tuple(fill.shape)}")
+    out = torch.empty_like(x)
+    if B == 0:
+        return out
+    if lengths is not None:
+        lengths = _lengths(name, lengths, B)
+    _lib.check(_lib.lib().ign_perturb_btc(_ptr(x), _ptr(score), _ptr(thr_key), _ptr(thr_idx), j, nk, _ptr(fill), _ptr(lengths),
+                                          _ptr(out), int(bool(insert)), B, T, C, Cs, _stream()), "ign_perturb_btc")
+    return out
+
+
 class SbmFn(torch.autograd.Function):
     """The shapelet bottleneck model behind the instance norm as ONE autograd node: shapelet bank (every length group) ->
     linear class head (optional) -> both regularisers (IGN/model/Shapelet.py:190-210, 217-230).

@@ -31,6 +31,11 @@ Differences, all repairs of fork defects listed in SURVEY section 0:
     class's logit laid out over time and electrodes (the shapelet expert's (N,T,C) map, the FCN expert's (N,T) map and its bias),
     which sum to that logit, plus eta, logit, target and contrib (utils/evidence.py); needs ``--sbm_cls linear``; the default
     ``none`` imports and launches nothing;
+  * ``--faithfulness explain=sbm|gated|dnn[,attr=evidence+saliency+random][,steps=10][,mode=deletion|insertion][,fill=mean|zero]
+    [,unit=cell|time][,seed=0]`` writes ``faithfulness.json`` (the spec, the mean curves, AUC / AOPC / flip fraction per attribution
+    and the gap to the random ranking) and ``faithfulness.npz`` (the per-sample curves) beside the test results after the test: the
+    deletion / insertion test of the explanations (utils/faithfulness.py), ranking and perturbation on the device
+    (``ign_rank_threshold``, ``ign_perturb_btc``); classification only; the default ``none`` parses, imports and launches nothing;
   * ``--eeg_preprocess band=8:30,decimate=2,fit`` (``--data EEG`` / ``EEG3``; any subset of sfreq=F, band=LO:HI, decimate=Q, taps=M,
     edge=reflect|zero, fit) filters the raw CHISCO shards with a zero-phase FIR band-pass, decimates them and, with ``fit``, crops /
     zero-pads them to ``--target_channels`` x ``--target_timepoints`` in front of the standardisation -- on the device in the
@@ -191,6 +196,13 @@ def build_parser():
                         "plus eta, logit, target and contrib = W[target] * p, the reference's ranking key of the shapelets.  sbm: the "
                         "interpretable expert of SBM / LTS / InterpGN; dnn: the FCN expert; gated: the mixture InterpGN predicts "
                         "with, --gating_value applied.  Needs --sbm_cls linear (the other heads are not additive in p)")
+    p.add_argument("--faithfulness", type=str, default='none',
+                   help="after the test, write faithfulness.json and faithfulness.npz beside the test results: deletion / insertion "
+                        "curves of the explanations over the test set.  none, or explain=sbm|gated|dnn followed by any of "
+                        "attr=evidence+saliency+random (the rankings compared), steps=N (1..31 fractions j/N, default 10), "
+                        "mode=deletion|insertion, fill=mean|zero (what replaces a cell: its electrode's mean over the sample, or "
+                        "0), unit=cell|time (rank cells, or whole time steps), seed=S (of the random ranking).  evidence needs "
+                        "--sbm_cls linear; saliency refuses what input gradients refuse.  Classification only")
     p.add_argument("--eeg_preprocess", type=str, default='none',
                    help="--data EEG / EEG3: preprocessing of the raw shards in front of the standardisation, on the device: none, or a "
                         "comma list of sfreq=F (Hz, default 500), band=LO:HI (Hz, either side may be empty), decimate=Q, taps=M "
@@ -313,6 +325,11 @@ def check_args(args):
     if parse_mix(getattr(args, 'mix', None)).active and getattr(args, 'task_name', 'classification') == 'regression':
         raise ValueError("--mix with --task_name regression: mixup / CutMix mix class labels through the cross-entropy tails; the "
                          "CRPS tails have no soft-label form")
+    if str(getattr(args, 'faithfulness', 'none')).strip().lower() != 'none':
+        from utils.faithfulness import parse_faithfulness
+        parse_faithfulness(args.faithfulness)
+        if getattr(args, 'task_name', 'classification') != 'classification':
+            raise ValueError("--faithfulness with --task_name regression: the curves follow a class logit; classification only")
     from data_provider.eeg_chain import EEGChain
     EEGChain.from_args(args).check(getattr(args, 'data', None))      # the --eeg_* flags: the data they need, the rates they name
     from utils.optim_rule import check_optim_options
@@ -401,6 +418,8 @@ def main(argv=None):
             print(f"accuracy: {test_metrics.accuracy:.4f}  loss: {test_metrics.loss:.4f}")
         if rank == 0 and getattr(args, 'evidence', 'none') != 'none':
             write_evidence(experiment, args.evidence, f"{os.path.dirname(ckpt)}/evidence.npz")
+        if rank == 0 and str(getattr(args, 'faithfulness', 'none')).strip().lower() != 'none':
+            write_faithfulness(experiment, args.faithfulness, os.path.dirname(ckpt))
 
 
 def write_evidence(experiment, explain, path):
@@ -410,6 +429,23 @@ def write_evidence(experiment, explain, path):
     arrays = {f.name: getattr(ev, f.name).numpy() for f in dataclasses.fields(ev) if getattr(ev, f.name) is not None}
     np.savez(path, **arrays)
     print(f"evidence ({explain}): {', '.join(f'{k} {v.shape}' for k, v in arrays.items())} -> {path}")
+
+
+def write_faithfulness(experiment, spec, out_dir):
+    """--faithfulness: the curves of Experiment.faithfulness over the test set as faithfulness.json (spec, mean curves, summary
+    numbers) and faithfulness.npz (per-sample curves)."""
+    import json
+    from utils.faithfulness import parse_faithfulness, to_arrays, to_json
+    spec = parse_faithfulness(spec)
+    f = experiment.faithfulness(**spec._asdict())
+    if f.target is None:
+        print("faithfulness: the test loader is empty, nothing written")
+        return
+    with open(f"{out_dir}/faithfulness.json", 'w') as fh:
+        json.dump(to_json(f, spec), fh, indent=1, sort_keys=True)
+    np.savez(f"{out_dir}/faithfulness.npz", **to_arrays(f))
+    print(f"faithfulness ({spec.explain}, {spec.mode}, {f.target.shape[0]} samples): " +
+          ', '.join(f'{a}: auc {f.auc[a]:.4f} aopc {f.aopc[a]:.4f} flip {f.flip[a]:.3f}' for a in f.auc) + f" -> {out_dir}")
 
 
 if __name__ == "__main__":
