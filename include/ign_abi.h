@@ -527,6 +527,30 @@ int ign_rank_threshold(const float* score_bts, const int32_t* k_bj, const int32_
 int ign_perturb_btc(const float* x_btc, const float* score_bts, const int32_t* thr_key_bj, const int32_t* thr_idx_bj, int j, int nk,
                     const float* fill_bc, const int32_t* len_b, float* out_btc, int insert, int B, int T, int C, int Cs, void* stream);
 
+/* Occlusion maps (csrc/ign_occlusion.hip; rule: utils/occlusion.py occlude_rule / spread_rule; run.py --occlusion): hide a window of
+ * time on a group of electrodes, run the model on the copies, lay the falls of the class score back over the hidden cells -- an
+ * attribution that needs a forward pass only, for every model.  The time grid is the HOST's and the same for every sample: windows of
+ * W steps every S steps, 1 <= S <= W <= T, nt = ceil((T - W) / S) + 1 of them; gid (C) int32 in [0, G) names each electrode's group;
+ * patch p = i * G + g hides window i on group g; sample b has n_b = clamp(len_b[b], 0, T) steps (len_b NULL: T).  Arrays on the DEVICE.
+ *   hidden(b, p, t, c): gid[c] == g(p) and i(p) * S <= t < min(i(p) * S + W, n_b).
+ * ign_occlude_btc: x (B,T,C) -> out (B*Pc,T,C), row b*Pc + q the copy of sample b under patch p0 + q: the bits of fill[b,c] (fill
+ *   (B,C), NULL: 0.0f) where hidden, elsewhere the bits of x[b,t,c].  One read of x, Pc writes; out of place (overlapping buffers:
+ *   IGN_E_ARG); every scalar is a HOST integer: the launch can be captured.  p0 < 0, Pc < 1, p0 + Pc > nt*G: IGN_E_ARG;
+ *   B*Pc*T*C >= 2^31 - 65536: IGN_E_TOOBIG.  A gid outside [0, G) matches no patch.
+ * ign_occlusion_spread: drop (B, nt*G) -> out (B,T,C): for t < n_b
+ *     out[b,t,c] = fl(fl(sum_i drop[b, i*G + gid[c]]) * inv_k[cnt]),  i = max(0, ceil((t-W+1)/S)) .. min(nt-1, t/S) ascending, each
+ *   addition one float add starting from the first term, cnt their number, inv_k (ceil(W/S) + 1) the HOST's table inv_k[k] = 1.0f / k
+ *   (inv_k[0] unused); for t >= n_b, +0.0f.  A gather, a lane per cell: no atomics, no workspace, bitwise repeatable, a sample's map
+ *   independent of the batch around it.  ceil(W/S) > IGN_OCC_MAX_COVER: IGN_E_ARG.  gid is the caller's to check; a value outside
+ *   [0, G) is clamped before it indexes.
+ * Both: a null pointer (fill_bc and len_b may be), a non-positive dimension, G < 1, S < 1, S > W, W > T, nt not the grid's value:
+ *   IGN_E_ARG; T*C >= 2^31 - 65536: IGN_E_TOOBIG.  Nothing is launched on an error.  Timing labels occlude, occlusion_spread.   */
+#define IGN_OCC_MAX_COVER 64
+int ign_occlude_btc(const float* x_btc, const float* fill_bc, const int32_t* len_b, const int32_t* gid_c, float* out, int p0, int Pc,
+                    int G, int W, int S, int nt, int B, int T, int C, void* stream);
+int ign_occlusion_spread(const float* drop_bp, const int32_t* gid_c, const int32_t* len_b, const float* inv_k, float* out_btc, int G,
+                         int W, int S, int nt, int B, int T, int C, void* stream);
+
 /* Fused attention core softmax(scale * Q K^T) V, exact fp32 on the matrix cores (v_mfma_f32_32x32x2_f32), scores never
  * materialised.  Replaces IGN/layers/SelfAttention_Family.py:56-75 (FullAttention: no mask; dropout 0 here -- dropout p > 0
  * is ign_attn_*_dropout below) and the attention inside nn.TransformerEncoderLayer of IGN/model/eegcnn.py:219-228.

@@ -829,7 +829,8 @@ class Experiment(object):
     def faithfulness(self, loader=None, target=None, **spec):
         """Deletion / insertion curves over `loader` (default: the test loader) -> utils.faithfulness.Faithfulness of host tensors
         concatenated over the batches, the summary numbers taken over all samples.  `spec`: the keyword arguments of
-        utils.faithfulness.faithfulness_curves (explain, attributions, steps, mode, fill, unit, seed); --gating_value is applied as
+        utils.faithfulness.faithfulness_curves (explain, attributions, steps, mode, fill, unit, seed and, for the "occlusion"
+        attribution, window, stride, groups; explain="model" serves whatever --model built); --gating_value is applied as
         test applies it and the loader's padding mask reaches the model (--mask_padding).  The random ranking of batch i is seeded
         with seed + i."""
         from utils.faithfulness import Faithfulness, concat, faithfulness_curves
@@ -842,6 +843,23 @@ class Experiment(object):
             parts.append(faithfulness_curves(self.model, batch_x, mask=padding_mask, target=target, seed=seed + len(parts),
                                              gating_value=self.args.gating_value, **spec))
         return concat(parts) if parts else Faithfulness()
+
+    def occlusion(self, loader=None, target=None, **spec):
+        """Occlusion maps over `loader` (default: the test loader) -> utils.occlusion.Occlusion of host tensors concatenated over the
+        batches (map (N,T,C), drop (N,P), target (N,), base (N,)); every field None for an empty loader.  `spec`: the keyword
+        arguments of utils.occlusion.occlusion_map (explain, window, stride, groups, fill, score, rows); explain="model" runs whatever
+        --model built through utils.occlusion.model_logits, the calling convention of `_forward` at test time; --gating_value is
+        applied as test applies it and the loader's padding mask reaches the model (--mask_padding)."""
+        from utils.occlusion import Occlusion, occlusion_map
+        parts = []
+        for batch_x, label, padding_mask in (self.test_loader if loader is None else loader):
+            if batch_x.size(0) == 0:
+                continue
+            batch_x, _, padding_mask = self._to_device(batch_x, label, padding_mask)
+            parts.append(occlusion_map(self.model, batch_x, mask=padding_mask, target=target, gating_value=self.args.gating_value, **spec))
+        if not parts:
+            return Occlusion()
+        return Occlusion(*(torch.cat([getattr(p, name).cpu() for p in parts]) for name in Occlusion._fields))
 
     def test(self, save_csv=True, result_dir=None):
         """-> (test_loss, ClassificationResult, None)   (:828-1138; ``gating_value`` is applied here only)."""

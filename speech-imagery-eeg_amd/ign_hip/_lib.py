@@ -178,6 +178,8 @@ SIGNATURES = {
     "ign_cam_spread": (ci, [vp, vp, ci, ci, ci, cf, vp]),
     "ign_rank_threshold": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
     "ign_perturb_btc": (ci, [vp, vp, vp, vp, ci, ci, vp, vp, vp, ci, ci, ci, ci, ci, vp]),
+    "ign_occlude_btc": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp]),
+    "ign_occlusion_spread": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]),
     "ign_eeg_preprocess_ws_bytes": (sz, [ci, ci, ci, ci, ci, ci, ci]),
     "ign_eeg_preprocess_nct_to_btc": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, vp]),
     "ign_eeg_filterbank_ws_bytes": (sz, [ci, ci, ci, ci, ci, ci, ci, ci]),

@@ -1081,6 +1081,101 @@ def perturb(x, score, thr_key, thr_idx, j, fill=None, insert=False, lengths=None
     return out
 
 
+OCC_MAX_COVER = 64            # IGN_OCC_MAX_COVER (include/ign_abi.h): most windows over one time step that ign_occlusion_spread adds
+
+
+_OCC_CONST = {}               # (kind, bytes, device) -> the device copy of a small host table; kept, so a captured launch's pointer stays good
+
+
+def _occ_const(kind, host, device):
+    key = (kind, host.tobytes(), str(device))
+    if key not in _OCC_CONST:
+        _OCC_CONST[key] = torch.from_numpy(host).to(device)
+    return _OCC_CONST[key]
+
+
+def _occ_gid(name, gid, groups, C, device):
+    """The electrode groups as the kernels take them, an int32 (C,) tensor on `device`, made from -- and checked on -- HOST data (a
+    sequence, a numpy array or a CPU tensor): the kernels never index with a value outside [0, groups).  The device copy of a table
+    is made once, so a second call copies nothing and may be captured."""
+    import numpy as np
+    groups = int(groups)
+    if torch.is_tensor(gid) and gid.is_cuda:
+        raise _lib.IgnError(f"{name}: gid must be host data (it is checked on the host before any launch), got a tensor on {gid.device}")
+    host = np.asarray(gid)
+    if host.shape != (C,) or host.dtype.kind not in "iu":
+        raise _lib.IgnError(f"{name}: gid must be {C} integers, one group per electrode, got {host.dtype} {host.shape}")
+    if groups < 1 or (host < 0).any() or (host >= groups).any():
+        raise _lib.IgnError(f"{name}: gid must lie in [0, groups) with groups = {groups} >= 1, got {int(host.min())} .. {int(host.max())}")
+    return _occ_const("gid", np.ascontiguousarray(host, dtype=np.int32), device), groups
+
+
+def occlude(x, p0, count, gid, groups, window, stride, fill=None, lengths=None):
+    """`count` occluded copies of every sample (ign_occlude_btc; the rule is utils/occlusion.py:occlude_rule, equal to it bit for bit)
+    -> a new (B*count, T, C) tensor, row b*count + q the copy of sample b under patch p0 + q.  `x`: float32 (B,T,C); `gid`: C integers
+    in [0, groups), a host array (or a tensor, copied to the host and checked there); `window`, `stride`: the time grid of
+    utils.occlusion.grid (0: the whole series / the window); patch p = i*groups + g hides steps [i*S, min(i*S + W, len_b)) of the
+    electrodes in group g behind `fill` (float32 (B,C), None: 0.0); `lengths`: int32 (B,) or None.  One read of x, `count` writes;
+    every scalar is a host integer, so the call may be captured."""
+    from utils.occlusion import grid
+    name = "occlude"
+    _need_plain(name, "x", x, torch.float32, 3)
+    B, T, C = x.shape
+    W, S, nt = grid(T, window, stride)
+    gid_d, G = _occ_gid(name, gid, groups, C, x.device)
+    p0, count = int(p0), int(count)
+    if p0 < 0 or count < 1 or p0 + count > nt * G:
+        raise _lib.IgnError(f"{name}: patches {p0} .. {p0 + count - 1} outside [0, {nt * G}) ({nt} windows x {G} groups)")
+    if fill is not None:
+        _need_plain(name, "fill", fill, torch.float32, 2)
+        if tuple(fill.shape) != (B, C):
+            raise _lib.IgnError(f"{name}: fill must be ({B},{C}), got {tuple(fill.shape)}")
+    out = torch.empty(B * count, T, C, device=x.device, dtype=torch.float32)
+    if B == 0:
+        return out
+    if lengths is not None:
+        lengths = _lengths(name, lengths, B)
+    _lib.check(_lib.lib().ign_occlude_btc(_ptr(x), _ptr(fill), _ptr(lengths), _ptr(gid_d), _ptr(out), p0, count, G, W, S, nt, B, T, C,
+                                          _stream()), "ign_occlude_btc")
+    return out
+
+
+def occlusion_spread(drop, gid, groups, window, stride, T, lengths=None):
+    """The drops of the class score laid back over the cells that were hidden (ign_occlusion_spread; the rule is
+    utils/occlusion.py:spread_rule, equal to it bit for bit) -> a new (B,T,C) tensor.  `drop`: float32 (B, nt*groups), column
+    i*groups + g the drop under window i on group g; `gid`, `groups`, `window`, `stride`, `lengths` as in `occlude`.  A cell inside
+    the sample's length takes the mean of the drops of the windows over its step on its electrode's group (added in ascending window
+    order, times the host's float32 1 / count); beyond the length the map is +0.0."""
+    import numpy as np
+    from utils.occlusion import grid
+    name = "occlusion_spread"
+    _need_plain(name, "drop", drop, torch.float32, 2)
+    T = int(T)
+    if T < 1:
+        raise _lib.IgnError(f"{name}: T = {T}, need at least one time step")
+    W, S, nt = grid(T, window, stride)
+    cover = -(-W // S)
+    if cover > OCC_MAX_COVER:
+        raise _lib.IgnError(f"{name}: window {W} / stride {S} put {cover} windows over a step, more than {OCC_MAX_COVER} "
+                            f"(IGN_OCC_MAX_COVER)")
+    C = len(gid) if hasattr(gid, "__len__") else -1
+    gid_d, G = _occ_gid(name, gid, groups, C, drop.device)
+    B = drop.shape[0]
+    if drop.shape[1] != nt * G:
+        raise _lib.IgnError(f"{name}: drop must be ({B}, {nt * G}) for {nt} windows x {G} groups, got {tuple(drop.shape)}")
+    out = torch.empty(B, T, C, device=drop.device, dtype=torch.float32)
+    if B == 0:
+        return out
+    if lengths is not None:
+        lengths = _lengths(name, lengths, B)
+    inv = np.zeros(cover + 1, np.float32)
+    inv[1:] = np.float32(1.0) / np.arange(1, cover + 1, dtype=np.float32)
+    inv_d = _occ_const("inv", inv, drop.device)
+    _lib.check(_lib.lib().ign_occlusion_spread(_ptr(drop), _ptr(gid_d), _ptr(lengths), _ptr(inv_d), _ptr(out), G, W, S, nt, B, T, C,
+                                               _stream()), "ign_occlusion_spread")
+    return out
+
+
 class SbmFn(torch.autograd.Function):
     """The shapelet bottleneck model behind the instance norm as ONE autograd node: shapelet bank (every length group) ->
     linear class head (optional) -> both regularisers (IGN/model/Shapelet.py:190-210, 217-230).

@@ -36,6 +36,13 @@ Differences, all repairs of fork defects listed in SURVEY section 0:
     and the gap to the random ranking) and ``faithfulness.npz`` (the per-sample curves) beside the test results after the test: the
     deletion / insertion test of the explanations (utils/faithfulness.py), ranking and perturbation on the device
     (``ign_rank_threshold``, ``ign_perturb_btc``); classification only; the default ``none`` parses, imports and launches nothing;
+    ``explain=model`` with ``attr=occlusion+random`` (and ``window=``, ``stride=``, ``groups=``) draws the curves for every model;
+  * ``--occlusion explain=model|sbm|gated|dnn[,window=W][,stride=S][,groups=all|each|PATH.npy][,fill=mean|zero][,score=logit|prob]
+    [,rows=256]`` writes ``occlusion.npz`` beside the test results after the test: per test sample how far the predicted class's
+    score falls when a window of time on a group of electrodes is hidden, laid back over the hidden cells (``map`` (N,T,C), ``drop``
+    (N,P), ``target``, ``base``, ``gid`` and the grid; utils/occlusion.py) -- an attribution that needs a forward pass only, for
+    every model (``explain=model``), head, distance and deep expert; the copies and the gather back run on the device
+    (``ign_occlude_btc``, ``ign_occlusion_spread``); classification only; the default ``none`` parses, imports and launches nothing;
   * ``--eeg_preprocess band=8:30,decimate=2,fit`` (``--data EEG`` / ``EEG3``; any subset of sfreq=F, band=LO:HI, decimate=Q, taps=M,
     edge=reflect|zero, fit) filters the raw CHISCO shards with a zero-phase FIR band-pass, decimates them and, with ``fit``, crops /
     zero-pads them to ``--target_channels`` x ``--target_timepoints`` in front of the standardisation -- on the device in the
@@ -202,7 +209,16 @@ def build_parser():
                         "attr=evidence+saliency+random (the rankings compared), steps=N (1..31 fractions j/N, default 10), "
                         "mode=deletion|insertion, fill=mean|zero (what replaces a cell: its electrode's mean over the sample, or "
                         "0), unit=cell|time (rank cells, or whole time steps), seed=S (of the random ranking).  evidence needs "
-                        "--sbm_cls linear; saliency refuses what input gradients refuse.  Classification only")
+                        "--sbm_cls linear; saliency refuses what input gradients refuse.  attr may also name occlusion (see "
+                        "--occlusion; its grid is window=W, stride=S, groups=all|each|PATH.npy), and explain=model with "
+                        "attr=occlusion+random draws the curves for any model, head and distance.  Classification only")
+    p.add_argument("--occlusion", type=str, default='none',
+                   help="after the test, write occlusion.npz beside the test results: occlusion maps over the test set.  none, or "
+                        "explain=model|sbm|gated|dnn (model: whatever --model built, as the test runs it; the rest as --evidence) "
+                        "followed by any of window=W, stride=S (time steps; 0 = the whole series / the window), "
+                        "groups=all|each|PATH.npy (electrodes hidden together: all of them, one at a time, or an int array (C,) of "
+                        "group ids), fill=mean|zero, score=logit|prob, rows=R (occluded copies per forward, default 256).  Works "
+                        "for every model, head and distance.  Classification only")
     p.add_argument("--eeg_preprocess", type=str, default='none',
                    help="--data EEG / EEG3: preprocessing of the raw shards in front of the standardisation, on the device: none, or a "
                         "comma list of sfreq=F (Hz, default 500), band=LO:HI (Hz, either side may be empty), decimate=Q, taps=M "
@@ -330,6 +346,11 @@ def check_args(args):
         parse_faithfulness(args.faithfulness)
         if getattr(args, 'task_name', 'classification') != 'classification':
             raise ValueError("--faithfulness with --task_name regression: the curves follow a class logit; classification only")
+    if str(getattr(args, 'occlusion', 'none')).strip().lower() != 'none':
+        from utils.occlusion import parse_occlusion
+        parse_occlusion(args.occlusion)
+        if getattr(args, 'task_name', 'classification') != 'classification':
+            raise ValueError("--occlusion with --task_name regression: the maps follow a class score; classification only")
     from data_provider.eeg_chain import EEGChain
     EEGChain.from_args(args).check(getattr(args, 'data', None))      # the --eeg_* flags: the data they need, the rates they name
     from utils.optim_rule import check_optim_options
@@ -420,6 +441,8 @@ def main(argv=None):
             write_evidence(experiment, args.evidence, f"{os.path.dirname(ckpt)}/evidence.npz")
         if rank == 0 and str(getattr(args, 'faithfulness', 'none')).strip().lower() != 'none':
             write_faithfulness(experiment, args.faithfulness, os.path.dirname(ckpt))
+        if rank == 0 and str(getattr(args, 'occlusion', 'none')).strip().lower() != 'none':
+            write_occlusion(experiment, args.occlusion, f"{os.path.dirname(ckpt)}/occlusion.npz")
 
 
 def write_evidence(experiment, explain, path):
@@ -446,6 +469,20 @@ def write_faithfulness(experiment, spec, out_dir):
     np.savez(f"{out_dir}/faithfulness.npz", **to_arrays(f))
     print(f"faithfulness ({spec.explain}, {spec.mode}, {f.target.shape[0]} samples): " +
           ', '.join(f'{a}: auc {f.auc[a]:.4f} aopc {f.aopc[a]:.4f} flip {f.flip[a]:.3f}' for a in f.auc) + f" -> {out_dir}")
+
+
+def write_occlusion(experiment, spec, path):
+    """--occlusion: the maps of Experiment.occlusion over the test set as one .npz (map, drop, target, base, gid and the grid)."""
+    from utils.occlusion import parse_occlusion, to_arrays
+    spec = parse_occlusion(spec)
+    occ = experiment.occlusion(**spec._asdict())
+    if occ.map is None:
+        print("occlusion: the test loader is empty, nothing written")
+        return
+    arrays = to_arrays(occ, spec, occ.map.shape[1], occ.map.shape[2])
+    np.savez(path, **arrays)
+    print(f"occlusion ({spec.explain}, {int(arrays['windows'])} windows x {int(arrays['groups'])} groups, {occ.map.shape[0]} samples): "
+          f"{', '.join(f'{k} {v.shape}' for k, v in arrays.items())} -> {path}")
 
 
 if __name__ == "__main__":

@@ -26,7 +26,9 @@ import numpy as np
 from utils.flag_items import FlagItems
 
 MAX_STEPS = 31                                          # steps + 1 thresholds per sample <= IGN_RANK_MAX_K = ops.RANK_MAX_K
-ATTRIBUTIONS = ("evidence", "saliency", "random")
+ATTRIBUTIONS = ("evidence", "saliency", "random")       # the default request
+ALLOWED_ATTRIBUTIONS = ATTRIBUTIONS + ("occlusion",)    # what may be asked for under explain=sbm|gated|dnn
+MODEL_ATTRIBUTIONS = ("occlusion", "random")            # ... and under explain=model: the attributions that need only a forward pass
 MODES = ("deletion", "insertion")
 FILLS = ("mean", "zero")
 UNITS = ("cell", "time")
@@ -108,21 +110,28 @@ class FaithSpec(NamedTuple):
     fill: str = "mean"
     unit: str = "cell"
     seed: int = 0
+    window: int = 0                                     # the grid of the "occlusion" attribution (utils.occlusion.grid)
+    stride: int = 0
+    groups: str = "all"
 
 
-_GRAMMAR = ("none | explain=sbm|gated|dnn[,attr=evidence+saliency+random][,steps=N][,mode=deletion|insertion][,fill=mean|zero]"
-            "[,unit=cell|time][,seed=S]")
-_ITEMS = FlagItems("--faithfulness", _GRAMMAR, ("explain", "attr", "steps", "mode", "fill", "unit", "seed"))
-_EXPLAIN = ("sbm", "gated", "dnn")                      # utils.saliency.EXPLAIN, restated: this parser imports no torch
+_GRAMMAR = ("none | explain=sbm|gated|dnn|model[,attr=evidence+saliency+random+occlusion][,steps=N][,mode=deletion|insertion]"
+            "[,fill=mean|zero][,unit=cell|time][,seed=S][,window=W][,stride=S][,groups=all|each|PATH.npy]")
+_ITEMS = FlagItems("--faithfulness", _GRAMMAR, ("explain", "attr", "steps", "mode", "fill", "unit", "seed", "window", "stride", "groups"))
+_EXPLAIN = ("sbm", "gated", "dnn", "model")             # utils.saliency.EXPLAIN restated (this parser imports no torch), and the whole model
 
 
-def check_spec(explain, attributions, steps, mode, fill, unit, seed=0, who="--faithfulness"):
+def check_spec(explain, attributions, steps, mode, fill, unit, seed=0, window=0, stride=0, groups="all", who="--faithfulness"):
     """The domain of ``faithfulness_curves`` (what it refuses with ValueError)."""
     if explain not in _EXPLAIN:
         raise ValueError(f"{who}: explain must be one of {_EXPLAIN}, got {explain!r}")
     attributions = tuple(attributions)
-    if not attributions or len(set(attributions)) != len(attributions) or any(a not in ATTRIBUTIONS for a in attributions):
-        raise ValueError(f"{who}: attributions must be distinct names from {ATTRIBUTIONS}, got {attributions!r}")
+    allowed = MODEL_ATTRIBUTIONS if explain == "model" else ALLOWED_ATTRIBUTIONS
+    if not attributions or len(set(attributions)) != len(attributions) or any(a not in allowed for a in attributions):
+        raise ValueError(f"{who}: attributions must be distinct names from {allowed} under explain={explain}, got {attributions!r}")
+    if "occlusion" in attributions:
+        from utils.occlusion import check_grid_spec
+        check_grid_spec(window, stride, groups, who)
     if int(steps) != steps or not 1 <= int(steps) <= MAX_STEPS:
         raise ValueError(f"{who}: steps must be an integer in 1..{MAX_STEPS}, got {steps}")
     for what, v, allowed in (("mode", mode, MODES), ("fill", fill, FILLS), ("unit", unit, UNITS)):
@@ -143,14 +152,14 @@ def parse_faithfulness(spec):
         return None
     got = {}
     for key, val in _ITEMS.items(text):
-        if key in ("steps", "seed"):
+        if key in ("steps", "seed", "window", "stride"):
             got[key] = _ITEMS.integer(key, val)
         elif key == "attr":
             got["attributions"] = tuple(a.strip() for a in val.split("+"))
         else:
             got[key] = val
     if "explain" not in got:
-        raise ValueError(f"--faithfulness: {text!r} names no explain=sbm|gated|dnn{_ITEMS.tail}")
+        raise ValueError(f"--faithfulness: {text!r} names no explain=sbm|gated|dnn|model{_ITEMS.tail}")
     out = FaithSpec(**got)
     check_spec(*out)
     return out
@@ -207,9 +216,13 @@ def concat(parts):
     return summarize(out)
 
 
-def _scores(name, model, x, mask, idx, explain, gating_value, gen):
+def _scores(name, model, x, mask, idx, explain, gating_value, gen, fill="mean", window=0, stride=0, groups="all"):
     """The score map (B,T,Cs) of one attribution for the classes `idx`."""
     import torch
+    if name == "occlusion":
+        from utils import occlusion
+        return occlusion.occlusion_map(model, x, mask=mask, target=idx, explain=explain, window=window, stride=stride, groups=groups,
+                                       fill=fill, gating_value=gating_value).map
     if name == "evidence":
         from utils import evidence
         ev = evidence.evidence_map(model, x, target=idx, explain=explain, gating_value=gating_value, mask=mask)
@@ -225,7 +238,7 @@ def _scores(name, model, x, mask, idx, explain, gating_value, gen):
 
 
 def faithfulness_curves(model, x, mask=None, target=None, explain="sbm", attributions=ATTRIBUTIONS, steps=10, mode="deletion",
-                        fill="mean", unit="cell", seed=0, gating_value=None):
+                        fill="mean", unit="cell", seed=0, window=0, stride=0, groups="all", gating_value=None):
     """-> Faithfulness, every tensor on x's device: the explained class's logit and probability of every sample with the top
     j / steps of its cells (``unit="cell"``) or time steps (``unit="time"``: the scores are summed over the electrodes) replaced, for
     j = 0 .. steps and every attribution in ``attributions``:
@@ -234,10 +247,14 @@ def faithfulness_curves(model, x, mask=None, target=None, explain="sbm", attribu
                   score per time step whatever the unit) or, for "gated", sbm + dnn / C per cell;
       "saliency"  |utils.saliency.input_saliency|; what that refuses (cosine / pearson distances) is refused here with its own error,
                   and like it the gradient is taken on the padded batch, without the mask;
-      "random"    torch.rand on the device under a generator seeded with ``seed``.
+      "random"    torch.rand on the device under a generator seeded with ``seed``;
+      "occlusion" utils.occlusion.occlusion_map on the grid ``window`` / ``stride`` / ``groups`` with the same ``fill``: the mean fall
+                  of the class logit over the patches that hid a cell.  Not in the default request.
 
     ``model``, ``explain``, ``gating_value``, ``mask`` and the TypeErrors / ValueErrors of the dispatch are evidence_map's, the
-    linear-head requirement included.  ``target`` (an int, a (B,) tensor, None: the predicted class) is resolved once, from the
+    linear-head requirement included -- except that a bilinear or attention head is accepted when nothing but "occlusion" and
+    "random" is asked for, which need no additivity.  ``explain="model"`` runs the whole model as Experiment.test calls it (every
+    model of the registry: any head, distance and deep expert, EEGCNN, the DNN baselines) and allows those two attributions only.  ``target`` (an int, a (B,) tensor, None: the predicted class) is resolved once, from the
     unperturbed forward, and shared by every attribution.  ``fill="mean"`` replaces a cell by the mean of its electrode over the
     sample's own length, ``"zero"`` by 0.  With ``mask_padding`` on, the lengths come from ``mask``: only a sample's own steps are
     ranked and replaced.  k[b,j] = (j * n_b) // steps cells are replaced at fraction j / steps.
@@ -247,18 +264,12 @@ def faithfulness_curves(model, x, mask=None, target=None, explain="sbm", attribu
     import torch
     from ign_hip import ops
     from utils.evidence import _resolve_target
-    from utils.saliency import _fcn_expert, _interpretable_expert
+    from utils.occlusion import explained_forward, mean_fill
     who = "faithfulness_curves"
-    check_spec(explain, attributions, steps, mode, fill, unit, seed, who=who)
+    check_spec(explain, attributions, steps, mode, fill, unit, seed, window, stride, groups, who=who)
     attributions, steps = tuple(attributions), int(steps)
-    sbm = fcn = None
-    if explain == "sbm":
-        sbm = scope = _interpretable_expert(model, who)
-    else:
-        fcn = _fcn_expert(model, explain, who)
-        scope = model if explain == "gated" else fcn
-        sbm = model.sbm if explain == "gated" else None
-    if sbm is not None and sbm.configs.sbm_cls != 'linear':
+    run, scope, sbm = explained_forward(model, explain, who, gating_value)
+    if explain != "model" and sbm is not None and sbm.configs.sbm_cls != 'linear' and not set(attributions) <= set(MODEL_ATTRIBUTIONS):
         raise ValueError(f"{who}: --sbm_cls {sbm.configs.sbm_cls} is not additive in the shapelet activations p, so no evidence map "
                          f"exists; the curves share evidence_map's dispatch and need the linear head")
     if x.dim() != 3:
@@ -266,11 +277,7 @@ def faithfulness_curves(model, x, mask=None, target=None, explain="sbm", attribu
     B, T, C = x.shape
 
     def forward(xb):
-        if explain == "sbm":
-            return sbm(xb, mask)[0].float()
-        if explain == "dnn":
-            return fcn(xb).float()
-        return model(xb, mask, None, None, gating_value=gating_value)[0].float()
+        return run(xb, mask)
 
     modes = [(mod, mod.training) for mod in scope.modules()]
     out = Faithfulness(mode=mode)
@@ -282,20 +289,13 @@ def faithfulness_curves(model, x, mask=None, target=None, explain="sbm", attribu
             lengths = sbm.padding_lengths((mask,)) if sbm is not None else None
             if lengths is not None:
                 lengths = lengths.clamp(0, T).to(torch.int32).contiguous()
-            fill_bc = None
-            if fill == "mean":
-                if lengths is None:
-                    fill_bc = xf.mean(1)
-                else:
-                    keep = (torch.arange(T, device=x.device)[None, :] < lengths[:, None]).to(xf.dtype)
-                    fill_bc = (xf * keep[:, :, None]).sum(1) / lengths.clamp(min=1).to(xf.dtype)[:, None]
-                fill_bc = fill_bc.contiguous()
+            fill_bc = mean_fill(xf, lengths) if fill == "mean" else None
             steps_j = torch.arange(steps + 1, device=x.device, dtype=torch.int64)
             gen = torch.Generator(device=x.device).manual_seed(int(seed))
             out.fractions = steps_j.double() / steps
             out.target = idx
             for name in attributions:
-                score = _scores(name, model, xf, mask, idx, explain, gating_value, gen)
+                score = _scores(name, model, xf, mask, idx, explain, gating_value, gen, fill, window, stride, groups)
                 if unit == "time" and score.shape[2] != 1:
                     score = score.sum(2, keepdim=True)
                 score = score.detach().float().contiguous()
@@ -323,7 +323,11 @@ def faithfulness_curves(model, x, mask=None, target=None, explain="sbm", attribu
 def to_json(f, spec):
     """What faithfulness.json holds: the spec, the mean curves and the summary numbers."""
     names = list(f.logit)
-    return dict(spec=dict(spec._asdict(), attributions=list(spec.attributions)), samples=int(f.target.shape[0]),
+    doc = dict(spec._asdict(), attributions=list(spec.attributions))
+    if "occlusion" not in spec.attributions:                # the grid belongs to that attribution alone
+        for key in ("window", "stride", "groups"):
+            del doc[key]
+    return dict(spec=doc, samples=int(f.target.shape[0]),
                 fractions=[float(v) for v in f.fractions],
                 mean_logit={a: [float(v) for v in f.logit[a].double().mean(1)] for a in names},
                 mean_prob={a: [float(v) for v in f.prob[a].double().mean(1)] for a in names},
