@@ -791,21 +791,27 @@ class Experiment(object):
         self.model.train()
         return loss, acc
 
+    def _explain_batches(self, loader):
+        """The non-empty batches of `loader` (default: the test loader) on the device -> (batch_x, padding_mask): the one loop of
+        the four explanation methods below."""
+        for batch_x, label, padding_mask in (self.test_loader if loader is None else loader):
+            if batch_x.size(0):
+                batch_x, _, padding_mask = self._to_device(batch_x, label, padding_mask)
+                yield batch_x, padding_mask
+
+    @staticmethod
+    def _on_host(parts, fields):
+        """Per-batch results -> {field: its tensors concatenated over the batches on the host; None where the results hold None}"""
+        return {k: None if getattr(parts[0], k) is None else torch.cat([getattr(p, k).cpu() for p in parts]) for k in fields}
+
     def saliency(self, loader=None, target=None, explain="sbm"):
         """Input saliency over `loader` (default: the test loader) -> one host tensor (N,T,C): per sample the gradient of a class
         logit w.r.t. the input series (utils.saliency.input_saliency; SBM / LTS / InterpGN).
         `target`: an int, or None for each sample's predicted class.  `explain`: "sbm" (the interpretable expert, the default),
         "gated" (the mixture an InterpGN with the FCN expert predicts with) or "dnn" (the FCN expert's logits)."""
         from utils.saliency import input_saliency
-        out = []
-        for batch_x, label, padding_mask in (self.test_loader if loader is None else loader):
-            if batch_x.size(0) == 0:
-                continue
-            batch_x, _, _ = self._to_device(batch_x, label, padding_mask)
-            out.append(input_saliency(self.model, batch_x, target, explain=explain).cpu())
-        if not out:
-            return torch.empty(0, self.args.seq_len, self.args.enc_in)
-        return torch.cat(out)
+        out = [input_saliency(self.model, batch_x, target, explain=explain).cpu() for batch_x, _ in self._explain_batches(loader)]
+        return torch.cat(out) if out else torch.empty(0, self.args.seq_len, self.args.enc_in)
 
     def evidence(self, loader=None, target=None, explain="sbm"):
         """Evidence maps over `loader` (default: the test loader) -> utils.evidence.Evidence of host tensors concatenated over the
@@ -815,16 +821,9 @@ class Experiment(object):
         applies it) or "dnn".  The loader's padding mask reaches the shapelet expert (--mask_padding)."""
         import dataclasses
         from utils.evidence import Evidence, evidence_map
-        parts = []
-        for batch_x, label, padding_mask in (self.test_loader if loader is None else loader):
-            if batch_x.size(0) == 0:
-                continue
-            batch_x, _, padding_mask = self._to_device(batch_x, label, padding_mask)
-            ev = evidence_map(self.model, batch_x, target, explain=explain, gating_value=self.args.gating_value, mask=padding_mask)
-            parts.append({f.name: getattr(ev, f.name) for f in dataclasses.fields(ev)})
-        if not parts:
-            return Evidence()
-        return Evidence(**{k: (torch.cat([p[k].cpu() for p in parts]) if parts[0][k] is not None else None) for k in parts[0]})
+        parts = [evidence_map(self.model, batch_x, target, explain=explain, gating_value=self.args.gating_value, mask=padding_mask)
+                 for batch_x, padding_mask in self._explain_batches(loader)]
+        return Evidence(**self._on_host(parts, [f.name for f in dataclasses.fields(Evidence)])) if parts else Evidence()
 
     def faithfulness(self, loader=None, target=None, **spec):
         """Deletion / insertion curves over `loader` (default: the test loader) -> utils.faithfulness.Faithfulness of host tensors
@@ -835,31 +834,21 @@ class Experiment(object):
         with seed + i."""
         from utils.faithfulness import Faithfulness, concat, faithfulness_curves
         seed = int(spec.pop("seed", 0))
-        parts = []
-        for batch_x, label, padding_mask in (self.test_loader if loader is None else loader):
-            if batch_x.size(0) == 0:
-                continue
-            batch_x, _, padding_mask = self._to_device(batch_x, label, padding_mask)
-            parts.append(faithfulness_curves(self.model, batch_x, mask=padding_mask, target=target, seed=seed + len(parts),
-                                             gating_value=self.args.gating_value, **spec))
+        parts = [faithfulness_curves(self.model, batch_x, mask=padding_mask, target=target, seed=seed + i,
+                                     gating_value=self.args.gating_value, **spec)
+                 for i, (batch_x, padding_mask) in enumerate(self._explain_batches(loader))]
         return concat(parts) if parts else Faithfulness()
 
     def occlusion(self, loader=None, target=None, **spec):
         """Occlusion maps over `loader` (default: the test loader) -> utils.occlusion.Occlusion of host tensors concatenated over the
         batches (map (N,T,C), drop (N,P), target (N,), base (N,)); every field None for an empty loader.  `spec`: the keyword
         arguments of utils.occlusion.occlusion_map (explain, window, stride, groups, fill, score, rows); explain="model" runs whatever
-        --model built through utils.occlusion.model_logits, the calling convention of `_forward` at test time; --gating_value is
+        --model built through utils.explain.model_logits, the calling convention of `_forward` at test time; --gating_value is
         applied as test applies it and the loader's padding mask reaches the model (--mask_padding)."""
         from utils.occlusion import Occlusion, occlusion_map
-        parts = []
-        for batch_x, label, padding_mask in (self.test_loader if loader is None else loader):
-            if batch_x.size(0) == 0:
-                continue
-            batch_x, _, padding_mask = self._to_device(batch_x, label, padding_mask)
-            parts.append(occlusion_map(self.model, batch_x, mask=padding_mask, target=target, gating_value=self.args.gating_value, **spec))
-        if not parts:
-            return Occlusion()
-        return Occlusion(*(torch.cat([getattr(p, name).cpu() for p in parts]) for name in Occlusion._fields))
+        parts = [occlusion_map(self.model, batch_x, mask=padding_mask, target=target, gating_value=self.args.gating_value, **spec)
+                 for batch_x, padding_mask in self._explain_batches(loader)]
+        return Occlusion(**self._on_host(parts, Occlusion._fields)) if parts else Occlusion()
 
     def test(self, save_csv=True, result_dir=None):
         """-> (test_loss, ClassificationResult, None)   (:828-1138; ``gating_value`` is applied here only)."""

@@ -1044,6 +1044,14 @@ def rank_threshold(score, k, lengths=None):
     return thr_key, thr_idx
 
 
+def _fill_bc(name, fill, B, C):
+    """The replacement values of `perturb` and `occlude`: None (0.0) or a plain float32 (B,C) tensor."""
+    if fill is not None:
+        _need_plain(name, "fill", fill, torch.float32, 2)
+        if tuple(fill.shape) != (B, C):
+            raise _lib.IgnError(f"{name}: fill must be ({B},{C}), got {tuple(fill.shape)}")
+
+
 def perturb(x, score, thr_key, thr_idx, j, fill=None, insert=False, lengths=None):
     """The batch with each sample's top-k cells replaced (ign_perturb_btc; the rule is utils/faithfulness.py:perturb_rule, equal to it
     bit for bit) -> a new (B,T,C) tensor.  `x`: float32 (B,T,C); `score`: the map the thresholds were taken from, (B,T,C) or (B,T,1);
@@ -1067,10 +1075,7 @@ def perturb(x, score, thr_key, thr_idx, j, fill=None, insert=False, lengths=None
     j = int(j)
     if not 0 <= j < nk:
         raise _lib.IgnError(f"{name}: j = {j} outside [0, {nk})")
-    if fill is not None:
-        _need_plain(name, "fill", fill, torch.float32, 2)
-        if tuple(fill.shape) != (B, C):
-            raise _lib.IgnError(f"{name}: fill must be ({B},{C}), got {tuple(fill.shape)}")
+    _fill_bc(name, fill, B, C)
     out = torch.empty_like(x)
     if B == 0:
         return out
@@ -1126,10 +1131,7 @@ def occlude(x, p0, count, gid, groups, window, stride, fill=None, lengths=None):
     p0, count = int(p0), int(count)
     if p0 < 0 or count < 1 or p0 + count > nt * G:
         raise _lib.IgnError(f"{name}: patches {p0} .. {p0 + count - 1} outside [0, {nt * G}) ({nt} windows x {G} groups)")
-    if fill is not None:
-        _need_plain(name, "fill", fill, torch.float32, 2)
-        if tuple(fill.shape) != (B, C):
-            raise _lib.IgnError(f"{name}: fill must be ({B},{C}), got {tuple(fill.shape)}")
+    _fill_bc(name, fill, B, C)
     out = torch.empty(B * count, T, C, device=x.device, dtype=torch.float32)
     if B == 0:
         return out
@@ -1146,8 +1148,7 @@ def occlusion_spread(drop, gid, groups, window, stride, T, lengths=None):
     i*groups + g the drop under window i on group g; `gid`, `groups`, `window`, `stride`, `lengths` as in `occlude`.  A cell inside
     the sample's length takes the mean of the drops of the windows over its step on its electrode's group (added in ascending window
     order, times the host's float32 1 / count); beyond the length the map is +0.0."""
-    import numpy as np
-    from utils.occlusion import grid
+    from utils.occlusion import grid, inv_table
     name = "occlusion_spread"
     _need_plain(name, "drop", drop, torch.float32, 2)
     T = int(T)
@@ -1168,9 +1169,7 @@ def occlusion_spread(drop, gid, groups, window, stride, T, lengths=None):
         return out
     if lengths is not None:
         lengths = _lengths(name, lengths, B)
-    inv = np.zeros(cover + 1, np.float32)
-    inv[1:] = np.float32(1.0) / np.arange(1, cover + 1, dtype=np.float32)
-    inv_d = _occ_const("inv", inv, drop.device)
+    inv_d = _occ_const("inv", inv_table(cover), drop.device)
     _lib.check(_lib.lib().ign_occlusion_spread(_ptr(drop), _ptr(gid_d), _ptr(lengths), _ptr(inv_d), _ptr(out), G, W, S, nt, B, T, C,
                                                _stream()), "ign_occlusion_spread")
     return out

@@ -76,6 +76,7 @@ Differences, all repairs of fork defects listed in SURVEY section 0:
   * multi-GPU is one process per GPU: ``python -m torch.distributed.run --nproc-per-node N run.py ...``.
 """
 import argparse
+import importlib
 import os
 import pickle
 import random
@@ -341,16 +342,12 @@ def check_args(args):
     if parse_mix(getattr(args, 'mix', None)).active and getattr(args, 'task_name', 'classification') == 'regression':
         raise ValueError("--mix with --task_name regression: mixup / CutMix mix class labels through the cross-entropy tails; the "
                          "CRPS tails have no soft-label form")
-    if str(getattr(args, 'faithfulness', 'none')).strip().lower() != 'none':
-        from utils.faithfulness import parse_faithfulness
-        parse_faithfulness(args.faithfulness)
-        if getattr(args, 'task_name', 'classification') != 'classification':
-            raise ValueError("--faithfulness with --task_name regression: the curves follow a class logit; classification only")
-    if str(getattr(args, 'occlusion', 'none')).strip().lower() != 'none':
-        from utils.occlusion import parse_occlusion
-        parse_occlusion(args.occlusion)
-        if getattr(args, 'task_name', 'classification') != 'classification':
-            raise ValueError("--occlusion with --task_name regression: the maps follow a class score; classification only")
+    for flag, parser, follows, _ in EXPLAIN_FLAGS:
+        if parser is not None and _flag_on(args, flag):
+            module, _, name = parser.rpartition('.')
+            getattr(importlib.import_module(module), name)(getattr(args, flag))
+            if getattr(args, 'task_name', 'classification') != 'classification':
+                raise ValueError(f"--{flag} with --task_name regression: {follows}; classification only")
     from data_provider.eeg_chain import EEGChain
     EEGChain.from_args(args).check(getattr(args, 'data', None))      # the --eeg_* flags: the data they need, the rates they name
     from utils.optim_rule import check_optim_options
@@ -437,12 +434,9 @@ def main(argv=None):
                 pickle.dump({'test_loss': test_loss, 'test_metrics': test_metrics, 'test_df': test_df,
                              'args': vars(args)}, f)
             print(f"accuracy: {test_metrics.accuracy:.4f}  loss: {test_metrics.loss:.4f}")
-        if rank == 0 and getattr(args, 'evidence', 'none') != 'none':
-            write_evidence(experiment, args.evidence, f"{os.path.dirname(ckpt)}/evidence.npz")
-        if rank == 0 and str(getattr(args, 'faithfulness', 'none')).strip().lower() != 'none':
-            write_faithfulness(experiment, args.faithfulness, os.path.dirname(ckpt))
-        if rank == 0 and str(getattr(args, 'occlusion', 'none')).strip().lower() != 'none':
-            write_occlusion(experiment, args.occlusion, f"{os.path.dirname(ckpt)}/occlusion.npz")
+        for flag, _, _, writer in EXPLAIN_FLAGS:
+            if rank == 0 and _flag_on(args, flag):
+                writer(experiment, getattr(args, flag), os.path.dirname(ckpt))
 
 
 def write_evidence(experiment, explain, path):
@@ -483,6 +477,20 @@ def write_occlusion(experiment, spec, path):
     np.savez(path, **arrays)
     print(f"occlusion ({spec.explain}, {int(arrays['windows'])} windows x {int(arrays['groups'])} groups, {occ.map.shape[0]} samples): "
           f"{', '.join(f'{k} {v.shape}' for k, v in arrays.items())} -> {path}")
+
+
+def _flag_on(args, flag):
+    return str(getattr(args, flag, 'none')).strip().lower() != 'none'
+
+
+# The explanation flags that act after the test, in the order they are served: (flag, its parser -- imported only when the flag is on
+# -- or None: argparse's choices check it, what a regression run is told, writer(experiment, the flag's value, the checkpoint's folder)).
+EXPLAIN_FLAGS = (
+    ("evidence", None, None, lambda experiment, explain, out_dir: write_evidence(experiment, explain, f"{out_dir}/evidence.npz")),
+    ("faithfulness", "utils.faithfulness.parse_faithfulness", "the curves follow a class logit", write_faithfulness),
+    ("occlusion", "utils.occlusion.parse_occlusion", "the maps follow a class score",
+     lambda experiment, spec, out_dir: write_occlusion(experiment, spec, f"{out_dir}/occlusion.npz")),
+)
 
 
 if __name__ == "__main__":

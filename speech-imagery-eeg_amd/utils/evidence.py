@@ -25,7 +25,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from utils.saliency import EXPLAIN, _fcn_expert, _interpretable_expert
+from utils.explain import EXPLAIN, explained, require_linear_head, resolve_target, session
 
 
 @dataclass
@@ -90,18 +90,7 @@ def cam_spread_rule(cam, R):
 
 
 def _resolve_target(target, logits):
-    B, N = logits.shape
-    if target is None:
-        return logits.argmax(dim=1)
-    if torch.is_tensor(target):
-        idx = target.to(device=logits.device, dtype=torch.long).reshape(-1)
-        if idx.numel() != B:
-            raise ValueError(f"evidence_map: target has {idx.numel()} entries for a batch of {B}")
-    else:
-        idx = torch.full((B,), int(target), device=logits.device, dtype=torch.long)
-    if bool(((idx < 0) | (idx >= N)).any()):
-        raise ValueError(f"evidence_map: target outside [0, {N})")
-    return idx
+    return resolve_target(target, logits, "evidence_map")
 
 
 def _sbm_maps(sbm, info, T, idx, scale):
@@ -132,7 +121,7 @@ def evidence_map(model, x, target=None, explain="sbm", gating_value=None, mask=N
     """-> Evidence, every tensor on x's device: the logit of class target[b] of sample b laid out over the input.
 
     ``model``: a ShapeBottleneckModel, a DistThresholdSBM ('LTS') or an InterpGN; with explain="dnn" also a FullyConvNetwork -- the
-    dispatch, and the TypeErrors, of utils.saliency.input_saliency.  ``explain``: "sbm" the interpretable expert's logits
+    dispatch, and the TypeErrors, of utils.explain.explained.  ``explain``: "sbm" the interpretable expert's logits
     (``ModelInfo.shapelet_preds``), "dnn" the FCN expert's, "gated" the mixture an InterpGN returns, with ``gating_value`` passed to
     its forward as Experiment.test does (where eta snaps to 1 the FCN map and the remainder are exactly zero).  ``x``: (B,T,C)
     float32 on the GPU.  ``target``: an int, a (B,) integer tensor, or None for the arg-max of the explained logits.  ``mask``: the
@@ -146,52 +135,21 @@ def evidence_map(model, x, target=None, explain="sbm", gating_value=None, mask=N
     who = "evidence_map"
     if explain not in EXPLAIN:
         raise ValueError(f"{who}: explain must be one of {EXPLAIN}, got {explain!r}")
-    sbm = fcn = None
-    if explain == "sbm":
-        sbm = scope = _interpretable_expert(model, who)
-    else:
-        fcn = _fcn_expert(model, explain, who)
-        scope = model if explain == "gated" else fcn
-        sbm = model.sbm if explain == "gated" else None
-    if sbm is not None and sbm.configs.sbm_cls != 'linear':
-        raise ValueError(f"{who}: --sbm_cls {sbm.configs.sbm_cls} is not additive in the shapelet activations p (the logit has "
-                         f"products of them), so no share per shapelet exists; evidence maps need the linear head")
+    scope, sbm, fcn, call = explained(model, explain, who, gating_value)
+    require_linear_head(sbm, who)
     if x.dim() != 3:
         raise ValueError(f"{who}: x must be (B,T,C), got {tuple(x.shape)}")
     T = x.shape[1]
-    modes = [(mod, mod.training) for mod in scope.modules()]
-    had_switch = fcn is not None and "keep_last" in vars(fcn)
-    switch = fcn.keep_last if fcn is not None else None
     ev = Evidence()
-    try:
-        scope.eval()
+    with session(scope, fcn=fcn, switch="keep_last"):
+        logits, info = call(x.detach().float(), mask)
+        idx = resolve_target(target, logits, who)
+        if explain == "gated":
+            ev.eta = info.eta.reshape(-1).float().contiguous()
+        if sbm is not None:
+            ev.sbm, ev.contrib = _sbm_maps(sbm, info, T, idx, ev.eta)
         if fcn is not None:
-            fcn.keep_last = True
-        with torch.no_grad(), torch.autocast(device_type=x.device.type, enabled=False):
-            xf = x.detach().float()
-            if explain == "sbm":
-                logits, info = sbm(xf, mask)
-                idx = _resolve_target(target, logits)
-                ev.sbm, ev.contrib = _sbm_maps(sbm, info, T, idx, None)
-            elif explain == "dnn":
-                logits = fcn(xf)
-                idx = _resolve_target(target, logits)
-                ev.dnn, ev.cam, ev.remainder = _fcn_maps(fcn, T, idx, None)
-            else:
-                logits, info = model(xf, mask, None, None, gating_value=gating_value)
-                idx = _resolve_target(target, logits)
-                ev.eta = info.eta.reshape(-1).float().contiguous()
-                ev.sbm, ev.contrib = _sbm_maps(sbm, info, T, idx, ev.eta)
-                ev.dnn, ev.cam, ev.remainder = _fcn_maps(fcn, T, idx, 1.0 - ev.eta)
-            ev.target = idx
-            ev.logit = logits.float().gather(1, idx[:, None]).squeeze(1)
-    finally:
-        for mod, flag in modes:
-            mod.training = flag
-        if fcn is not None:
-            vars(fcn).pop("last_block", None)
-            if had_switch:
-                fcn.keep_last = switch
-            else:
-                vars(fcn).pop("keep_last", None)
+            ev.dnn, ev.cam, ev.remainder = _fcn_maps(fcn, T, idx, None if ev.eta is None else 1.0 - ev.eta)
+        ev.target = idx
+        ev.logit = logits.float().gather(1, idx[:, None]).squeeze(1)
     return ev

@@ -23,7 +23,8 @@ from typing import NamedTuple, Optional
 
 import numpy as np
 
-from utils.flag_items import FlagItems
+from utils.explain import EXPLAIN_ALL, explained, lengths_of, mean_fill, require_linear_head, resolve_target, session
+from utils.flag_items import FlagItems, parse_spec
 
 MAX_STEPS = 31                                          # steps + 1 thresholds per sample <= IGN_RANK_MAX_K = ops.RANK_MAX_K
 ATTRIBUTIONS = ("evidence", "saliency", "random")       # the default request
@@ -118,13 +119,12 @@ class FaithSpec(NamedTuple):
 _GRAMMAR = ("none | explain=sbm|gated|dnn|model[,attr=evidence+saliency+random+occlusion][,steps=N][,mode=deletion|insertion]"
             "[,fill=mean|zero][,unit=cell|time][,seed=S][,window=W][,stride=S][,groups=all|each|PATH.npy]")
 _ITEMS = FlagItems("--faithfulness", _GRAMMAR, ("explain", "attr", "steps", "mode", "fill", "unit", "seed", "window", "stride", "groups"))
-_EXPLAIN = ("sbm", "gated", "dnn", "model")             # utils.saliency.EXPLAIN restated (this parser imports no torch), and the whole model
 
 
 def check_spec(explain, attributions, steps, mode, fill, unit, seed=0, window=0, stride=0, groups="all", who="--faithfulness"):
     """The domain of ``faithfulness_curves`` (what it refuses with ValueError)."""
-    if explain not in _EXPLAIN:
-        raise ValueError(f"{who}: explain must be one of {_EXPLAIN}, got {explain!r}")
+    if explain not in EXPLAIN_ALL:
+        raise ValueError(f"{who}: explain must be one of {EXPLAIN_ALL}, got {explain!r}")
     attributions = tuple(attributions)
     allowed = MODEL_ATTRIBUTIONS if explain == "model" else ALLOWED_ATTRIBUTIONS
     if not attributions or len(set(attributions)) != len(attributions) or any(a not in allowed for a in attributions):
@@ -145,24 +145,8 @@ def parse_faithfulness(spec):
     """``none`` / ``''`` / None -> None (the flag is off), or ``explain=sbm,attr=evidence+random,steps=10,mode=deletion,fill=mean,
     unit=cell,seed=0`` (``explain`` is required, the rest in any order) -> FaithSpec.  Unknown or repeated keys, a missing
     ``explain`` and values outside the domain raise ValueError."""
-    if isinstance(spec, FaithSpec):
-        return spec
-    text = _ITEMS.clean(spec)
-    if text is None:
-        return None
-    got = {}
-    for key, val in _ITEMS.items(text):
-        if key in ("steps", "seed", "window", "stride"):
-            got[key] = _ITEMS.integer(key, val)
-        elif key == "attr":
-            got["attributions"] = tuple(a.strip() for a in val.split("+"))
-        else:
-            got[key] = val
-    if "explain" not in got:
-        raise ValueError(f"--faithfulness: {text!r} names no explain=sbm|gated|dnn|model{_ITEMS.tail}")
-    out = FaithSpec(**got)
-    check_spec(*out)
-    return out
+    return parse_spec(_ITEMS, spec, FaithSpec, check_spec, "explain=sbm|gated|dnn|model", integers=("steps", "seed", "window", "stride"),
+                      convert={"attr": ("attributions", lambda val: tuple(a.strip() for a in val.split("+")))})
 
 
 # --------------------------------------------------------------------------------------------------------- the curves
@@ -263,59 +247,48 @@ def faithfulness_curves(model, x, mask=None, target=None, explain="sbm", attribu
     with autocast disabled; every module's training flag is restored on return."""
     import torch
     from ign_hip import ops
-    from utils.evidence import _resolve_target
-    from utils.occlusion import explained_forward, mean_fill
     who = "faithfulness_curves"
     check_spec(explain, attributions, steps, mode, fill, unit, seed, window, stride, groups, who=who)
     attributions, steps = tuple(attributions), int(steps)
-    run, scope, sbm = explained_forward(model, explain, who, gating_value)
-    if explain != "model" and sbm is not None and sbm.configs.sbm_cls != 'linear' and not set(attributions) <= set(MODEL_ATTRIBUTIONS):
-        raise ValueError(f"{who}: --sbm_cls {sbm.configs.sbm_cls} is not additive in the shapelet activations p, so no evidence map "
-                         f"exists; the curves share evidence_map's dispatch and need the linear head")
+    scope, sbm, _, call = explained(model, explain, who, gating_value)
+    if explain != "model" and not set(attributions) <= set(MODEL_ATTRIBUTIONS):     # "occlusion" and "random" need no additivity
+        require_linear_head(sbm, who)
     if x.dim() != 3:
         raise ValueError(f"{who}: x must be (B,T,C), got {tuple(x.shape)}")
     B, T, C = x.shape
 
     def forward(xb):
-        return run(xb, mask)
+        return call(xb, mask)[0].float()
 
-    modes = [(mod, mod.training) for mod in scope.modules()]
     out = Faithfulness(mode=mode)
-    try:
-        scope.eval()
-        with torch.no_grad(), torch.autocast(device_type=x.device.type, enabled=False):
-            xf = x.detach().float().contiguous()
-            idx = _resolve_target(target, forward(xf))          # fixed before anything is perturbed
-            lengths = sbm.padding_lengths((mask,)) if sbm is not None else None
-            if lengths is not None:
-                lengths = lengths.clamp(0, T).to(torch.int32).contiguous()
-            fill_bc = mean_fill(xf, lengths) if fill == "mean" else None
-            steps_j = torch.arange(steps + 1, device=x.device, dtype=torch.int64)
-            gen = torch.Generator(device=x.device).manual_seed(int(seed))
-            out.fractions = steps_j.double() / steps
-            out.target = idx
-            for name in attributions:
-                score = _scores(name, model, xf, mask, idx, explain, gating_value, gen, fill, window, stride, groups)
-                if unit == "time" and score.shape[2] != 1:
-                    score = score.sum(2, keepdim=True)
-                score = score.detach().float().contiguous()
-                n_b = (lengths.long() if lengths is not None else torch.full((B,), T, device=x.device)) * score.shape[2]
-                k = ((steps_j[None, :] * n_b[:, None]) // steps).to(torch.int32).contiguous()
-                thr_key, thr_idx = ops.rank_threshold(score, k, lengths=lengths)
-                lg, pr, am = [], [], []
-                for j in range(steps + 1):
-                    xp = ops.perturb(xf, score, thr_key, thr_idx, j, fill=fill_bc, insert=(mode == "insertion"), lengths=lengths)
-                    logits = forward(xp)
-                    lg.append(logits.gather(1, idx[:, None]).squeeze(1))
-                    pr.append(torch.softmax(logits, dim=1).gather(1, idx[:, None]).squeeze(1))
-                    am.append(logits.argmax(1) != idx)
-                out.logit[name], out.prob[name] = torch.stack(lg), torch.stack(pr)
-                left = torch.stack(am)                           # (steps+1, B): the arg-max has left the target
-                first = torch.where(left, steps_j[:, None], steps).min(0).values if B else steps_j[:0]
-                out.flip_at[name] = first.double() / steps
-    finally:
-        for mod, flag in modes:
-            mod.training = flag
+    with session(scope):
+        xf = x.detach().float().contiguous()
+        idx = resolve_target(target, forward(xf), who)          # fixed before anything is perturbed
+        lengths = lengths_of(sbm, mask, T)
+        fill_bc = mean_fill(xf, lengths) if fill == "mean" else None
+        steps_j = torch.arange(steps + 1, device=x.device, dtype=torch.int64)
+        gen = torch.Generator(device=x.device).manual_seed(int(seed))
+        out.fractions = steps_j.double() / steps
+        out.target = idx
+        for name in attributions:
+            score = _scores(name, model, xf, mask, idx, explain, gating_value, gen, fill, window, stride, groups)
+            if unit == "time" and score.shape[2] != 1:
+                score = score.sum(2, keepdim=True)
+            score = score.detach().float().contiguous()
+            n_b = (lengths.long() if lengths is not None else torch.full((B,), T, device=x.device)) * score.shape[2]
+            k = ((steps_j[None, :] * n_b[:, None]) // steps).to(torch.int32).contiguous()
+            thr_key, thr_idx = ops.rank_threshold(score, k, lengths=lengths)
+            lg, pr, am = [], [], []
+            for j in range(steps + 1):
+                xp = ops.perturb(xf, score, thr_key, thr_idx, j, fill=fill_bc, insert=(mode == "insertion"), lengths=lengths)
+                logits = forward(xp)
+                lg.append(logits.gather(1, idx[:, None]).squeeze(1))
+                pr.append(torch.softmax(logits, dim=1).gather(1, idx[:, None]).squeeze(1))
+                am.append(logits.argmax(1) != idx)
+            out.logit[name], out.prob[name] = torch.stack(lg), torch.stack(pr)
+            left = torch.stack(am)                               # (steps+1, B): the arg-max has left the target
+            first = torch.where(left, steps_j[:, None], steps).min(0).values if B else steps_j[:0]
+            out.flip_at[name] = first.double() / steps
     return summarize(out)
 
 

@@ -1,4 +1,5 @@
-"""The item loop of the four ``--eeg_*`` flags: a comma list of ``key=value`` items and bare keys, one grammar per flag.  ``FlagItems``
+"""The item loop of the four ``--eeg_*`` flags, and (``parse_spec``) the whole parser of ``--faithfulness`` and ``--occlusion``: a comma
+list of ``key=value`` items and bare keys, one grammar per flag.  ``FlagItems``
 splits the text, refuses unknown and repeated keys and converts numbers, and words every refusal as that flag always has; what a
 value means (a band, a ratio, a file) stays with the flag's own parser.  No numpy and no torch in this module."""
 import math
@@ -46,3 +47,27 @@ class FlagItems:
             return int(val)
         except ValueError:
             raise ValueError(f"{self.flag}: {key}={val!r} is not an integer{self.tail}") from None
+
+
+def parse_spec(items, spec, cls, check, required, integers=(), convert=None):
+    """A flag whose items are the fields of the NamedTuple `cls` (--faithfulness, --occlusion): ``none`` / ``''`` / None -> None (the
+    flag is off), a `cls` -> itself, else the ``key=value`` list -> `cls`, checked by ``check(*fields)``.  `items`: the flag's
+    FlagItems; `integers`: the keys converted with ``items.integer``; `convert`: key -> (field, converter) for a value that lands in
+    another field; `required`: ``key=what|it|takes``, the item that must be given, as the refusal words it."""
+    if isinstance(spec, cls):
+        return spec
+    text = items.clean(spec)
+    if text is None:
+        return None
+    got = {}
+    for key, val in items.items(text):
+        if key in integers:
+            got[key] = items.integer(key, val)
+        else:
+            field, fn = (convert or {}).get(key, (key, str))
+            got[field] = fn(val)
+    if required.partition('=')[0] not in got:
+        raise ValueError(f"{items.flag}: {text!r} names no {required}{items.tail}")
+    out = cls(**got)
+    check(*out)
+    return out

@@ -21,10 +21,12 @@ from typing import NamedTuple, Optional
 
 import numpy as np
 
-from utils.flag_items import FlagItems
+from utils.explain import EXPLAIN_ALL, explained, lengths_of, mean_fill, resolve_target, session
+from utils.explain import model_logits, shapelet_expert  # noqa: F401  (kept importable from here)
+from utils.flag_items import FlagItems, parse_spec
 
 MAX_COVER = 64                                          # IGN_OCC_MAX_COVER = ops.OCC_MAX_COVER: most windows over one time step
-EXPLAIN = ("model", "sbm", "gated", "dnn")              # "model": the whole model; the rest as in utils.saliency.EXPLAIN
+EXPLAIN = EXPLAIN_ALL[-1:] + EXPLAIN_ALL[:-1]           # "model" first, as the flag's grammar lists it
 FILLS = ("mean", "zero")
 SCORES = ("logit", "prob")
 
@@ -179,19 +181,7 @@ def parse_occlusion(spec):
     """``none`` / ``''`` / None -> None (the flag is off), or ``explain=model,window=50,stride=25,groups=each,fill=mean,score=logit,
     rows=256`` (``explain`` is required, the rest in any order) -> OccSpec.  Unknown or repeated keys, a missing ``explain`` and
     values outside the domain raise ValueError."""
-    if isinstance(spec, OccSpec):
-        return spec
-    text = _ITEMS.clean(spec)
-    if text is None:
-        return None
-    got = {}
-    for key, val in _ITEMS.items(text):
-        got[key] = _ITEMS.integer(key, val) if key in ("window", "stride", "rows") else val
-    if "explain" not in got:
-        raise ValueError(f"--occlusion: {text!r} names no explain=model|sbm|gated|dnn{_ITEMS.tail}")
-    out = OccSpec(**got)
-    check_spec(*out)
-    return out
+    return parse_spec(_ITEMS, spec, OccSpec, check_spec, "explain=model|sbm|gated|dnn", integers=("window", "stride", "rows"))
 
 
 # --------------------------------------------------------------------------------------------------------- the map
@@ -204,70 +194,13 @@ class Occlusion(NamedTuple):
     base: Optional[object] = None
 
 
-def shapelet_expert(model):
-    """The shapelet expert whose ``mask_padding`` decides whether a padding mask gives lengths: the model itself (SBM / LTS), the
-    ``sbm`` of an InterpGN, or None."""
-    from models.InterpGN import InterpGN
-    from models.Shapelet import ShapeBottleneckModel
-    if isinstance(model, InterpGN):
-        return model.sbm
-    return model if isinstance(model, ShapeBottleneckModel) else None
-
-
-def model_logits(model, x, mask=None, gating_value=None):
-    """The logits of a registry model on a (B,T,C) batch -- the calling convention of Experiment._forward at test time, by the
-    model's type: EEGCNN takes the (B,C,T) permuted view and no mask, InterpGN takes ``gating_value``, the deep baselines (--model
-    DNN) return bare logits, the others (logits, info)."""
-    from models.InterpGN import InterpGN
-    from models.eegcnn import EEGCNNTransformer
-    if isinstance(model, EEGCNNTransformer):
-        out = model(x.permute(0, 2, 1))
-    elif isinstance(model, InterpGN):
-        out = model(x, mask, None, None, gating_value=gating_value)
-    else:
-        out = model(x, mask, None, None)
-    return out[0] if isinstance(out, tuple) else out
-
-
-def explained_forward(model, explain, who, gating_value=None):
-    """The dispatch of ``explain`` -> (forward(x, mask) -> float32 logits, scope, sbm): the module tree put in eval mode and the
-    shapelet expert whose ``mask_padding`` gives the lengths (or None).  "sbm" | "gated" | "dnn" keep the meaning and the TypeErrors
-    of utils.saliency; "model" is the whole model."""
-    from utils.saliency import _fcn_expert, _interpretable_expert
-    if explain == "model":
-        import torch
-        if not isinstance(model, torch.nn.Module):
-            raise TypeError(f'{who}(explain="model") needs a torch.nn.Module, not {type(model).__name__}')
-        return (lambda xb, m: model_logits(model, xb, m, gating_value).float()), model, shapelet_expert(model)
-    if explain == "sbm":
-        sbm = _interpretable_expert(model, who)
-        return (lambda xb, m: sbm(xb, m)[0].float()), sbm, sbm
-    fcn = _fcn_expert(model, explain, who)
-    if explain == "dnn":
-        return (lambda xb, m: fcn(xb).float()), fcn, None
-    return (lambda xb, m: model(xb, m, None, None, gating_value=gating_value)[0].float()), model, model.sbm
-
-
-def mean_fill(xf, lengths):
-    """(B,C): the mean of every electrode over the sample's own length (`lengths` int (B,) or None: the whole series) -- what
-    ``fill="mean"`` puts in a replaced cell, for the faithfulness curves and the occlusion maps alike."""
-    import torch
-    T = xf.shape[1]
-    if lengths is None:
-        fill_bc = xf.mean(1)
-    else:
-        keep = (torch.arange(T, device=xf.device)[None, :] < lengths[:, None]).to(xf.dtype)
-        fill_bc = (xf * keep[:, :, None]).sum(1) / lengths.clamp(min=1).to(xf.dtype)[:, None]
-    return fill_bc.contiguous()
-
-
 def occlusion_map(model, x, mask=None, target=None, explain="model", window=0, stride=0, groups="all", fill="mean", score="logit",
                   rows=256, gating_value=None):
     """-> Occlusion, every tensor on x's device.
 
     ``explain``: "model" runs the whole model as Experiment.test calls it (any model of the registry: SBM / LTS / InterpGN with any
     head, distance and deep expert, EEGCNN, the DNN baselines); "sbm" | "gated" | "dnn" explain the shapelet expert, the gated
-    mixture and the FCN expert as utils.saliency does, with its TypeErrors -- but every head and every distance is served, because
+    mixture and the FCN expert (utils.explain.explained, with its TypeErrors) -- but every head and every distance is served, because
     nothing but the output is read.  ``window`` / ``stride``: the time grid (0: the whole series / the window); ``groups``: "all"
     (time-only occlusion, the map is constant across electrodes), "each" (a group per electrode; with ``window=0`` pure electrode
     occlusion), an int array (C,) or a ``.npy`` path (scalp regions, the band blocks of a filter bank).  ``fill``: "mean" replaces a
@@ -281,10 +214,9 @@ def occlusion_map(model, x, mask=None, target=None, explain="model", window=0, s
     module's training flag is restored on return."""
     import torch
     from ign_hip import ops
-    from utils.evidence import _resolve_target
     who = "occlusion_map"
     check_spec(explain, window, stride, groups, fill, score, rows, who=who)
-    forward, scope, sbm = explained_forward(model, explain, who, gating_value)
+    scope, sbm, _, call = explained(model, explain, who, gating_value)
     if x.dim() != 3:
         raise ValueError(f"{who}: x must be (B,T,C), got {tuple(x.shape)}")
     B, T, C = x.shape
@@ -298,32 +230,24 @@ def occlusion_map(model, x, mask=None, target=None, explain="model", window=0, s
         s = torch.softmax(logits, dim=1) if score == "prob" else logits
         return s.gather(1, idx[:, None]).squeeze(1)
 
-    modes = [(mod, mod.training) for mod in scope.modules()]
-    try:
-        scope.eval()
-        with torch.no_grad(), torch.autocast(device_type=x.device.type, enabled=False):
-            xf = x.detach().float().contiguous()
-            logits0 = forward(xf, mask)
-            idx = _resolve_target(target, logits0)              # fixed before anything is occluded
-            base = pick(logits0, idx)
-            lengths = sbm.padding_lengths((mask,)) if sbm is not None else None
-            if lengths is not None:
-                lengths = lengths.clamp(0, T).to(torch.int32).contiguous()
-            fill_bc = mean_fill(xf, lengths) if fill == "mean" else None
-            if B == 0:
-                return Occlusion(map=xf.new_zeros(0, T, C), drop=xf.new_zeros(0, P), target=idx, base=base)
-            chunk = max(1, int(rows) // B)
-            drops = []
-            for p0 in range(0, P, chunk):
-                n = min(chunk, P - p0)
-                xo = ops.occlude(xf, p0, n, gid, G, window, stride, fill=fill_bc, lengths=lengths)
-                logits = forward(xo, None if mask is None else mask.repeat_interleave(n, dim=0))
-                drops.append(base[:, None] - pick(logits, idx.repeat_interleave(n)).view(B, n))
-            drop = torch.cat(drops, dim=1).contiguous()
-            out = ops.occlusion_spread(drop, gid, G, window, stride, T, lengths=lengths)
-    finally:
-        for mod, flag in modes:
-            mod.training = flag
+    with session(scope):
+        xf = x.detach().float().contiguous()
+        logits0 = call(xf, mask)[0].float()
+        idx = resolve_target(target, logits0, who)              # fixed before anything is occluded
+        base = pick(logits0, idx)
+        lengths = lengths_of(sbm, mask, T)
+        fill_bc = mean_fill(xf, lengths) if fill == "mean" else None
+        if B == 0:
+            return Occlusion(map=xf.new_zeros(0, T, C), drop=xf.new_zeros(0, P), target=idx, base=base)
+        chunk = max(1, int(rows) // B)
+        drops = []
+        for p0 in range(0, P, chunk):
+            n = min(chunk, P - p0)
+            xo = ops.occlude(xf, p0, n, gid, G, window, stride, fill=fill_bc, lengths=lengths)
+            logits = call(xo, None if mask is None else mask.repeat_interleave(n, dim=0))[0].float()
+            drops.append(base[:, None] - pick(logits, idx.repeat_interleave(n)).view(B, n))
+        drop = torch.cat(drops, dim=1).contiguous()
+        out = ops.occlusion_spread(drop, gid, G, window, stride, T, lengths=lengths)
     return Occlusion(map=out, drop=drop, target=idx, base=base)
 
 

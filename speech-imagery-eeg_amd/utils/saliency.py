@@ -8,36 +8,11 @@ Complements the match locations in ``ModelInfo.t``: those say WHERE each shapele
            logits included -- the gate backward (ign_gate_bwd) feeds both experts, the FCN side ends in the data-gradient GEMM
            into the raw series (ign_clconv_dgrad_input*);
   "dnn"    the FCN expert's logits (``ModelInfo.dnn_preds``) alone.
-There is no CPU path.
+There is no CPU path.  What ``explain`` dispatches to, and the session the call runs in, are utils/explain.py's.
 """
 import torch
 
-from models.FullyConvNet import FullyConvNetwork
-from models.InterpGN import InterpGN
-from models.Shapelet import ShapeBottleneckModel
-
-EXPLAIN = ("sbm", "gated", "dnn")
-
-
-def _interpretable_expert(model, who="input_saliency"):
-    if isinstance(model, InterpGN):
-        return model.sbm
-    if isinstance(model, ShapeBottleneckModel):
-        return model
-    raise TypeError(f"{who} explains a shapelet expert (SBM, LTS or the SBM inside InterpGN), not {type(model).__name__}")
-
-
-def _fcn_expert(model, explain, who="input_saliency"):
-    """The FCN expert behind explain="gated" / "dnn"; the other deep experts have no input-gradient (or class-activation) kernels.
-    `who`: the caller named in the error (utils.evidence shares the dispatch)."""
-    fcn = model.deep_model if isinstance(model, InterpGN) else model if (explain == "dnn" and isinstance(model, FullyConvNetwork)) else None
-    if fcn is None:
-        want = "an InterpGN" if explain == "gated" else "an InterpGN or a FullyConvNetwork"
-        raise TypeError(f'{who}(explain="{explain}") needs {want} with the FCN deep expert, not {type(model).__name__}')
-    if not isinstance(fcn, FullyConvNetwork):
-        raise TypeError(f'{who}(explain="{explain}"): FCN is the supported deep expert (--dnn_type FCN), '
-                        f'not {type(fcn).__name__}')
-    return fcn
+from utils.explain import EXPLAIN, explained, resolve_target, session
 
 
 def input_saliency(model, x, target=None, explain="sbm", gating_value=None):
@@ -57,58 +32,19 @@ def input_saliency(model, x, target=None, explain="sbm", gating_value=None):
     -- and no parameter's ``.grad`` is touched.  Every module's training flag, every ``requires_grad`` flag and the FCN expert's
     ``input_grad`` switch are restored on return; ``x`` is not modified.
     """
+    who = "input_saliency"
     if explain not in EXPLAIN:
-        raise ValueError(f"input_saliency: explain must be one of {EXPLAIN}, got {explain!r}")
-    fcn = None
-    if explain == "sbm":
-        scope = _interpretable_expert(model)
-        run = lambda xg: scope(xg)[0]
-    else:
-        fcn = _fcn_expert(model, explain)
-        if explain == "gated":
-            scope = model
-            run = lambda xg: model(xg, gating_value=gating_value)[0]
-        else:
-            scope = fcn
-            run = lambda xg: fcn(xg)
+        raise ValueError(f"{who}: explain must be one of {EXPLAIN}, got {explain!r}")
+    scope, _, fcn, _ = explained(model, explain, who)
+    # its own forward, not Explained.call: no mask reaches the model here (utils/explain.py lists what differs between the explainers)
+    run = {"sbm": lambda xg: scope(xg)[0], "gated": lambda xg: model(xg, gating_value=gating_value)[0], "dnn": lambda xg: fcn(xg)}[explain]
     if x.dim() != 3:
-        raise ValueError(f"input_saliency: x must be (B,T,C), got {tuple(x.shape)}")
-    frozen = [p for p in scope.parameters() if p.requires_grad]
-    modes = [(mod, mod.training) for mod in scope.modules()]           # per module: mixed train / eval set-ups come back as they were
-    had_switch = fcn is not None and "input_grad" in vars(fcn)
-    switch = fcn.input_grad if fcn is not None else None
+        raise ValueError(f"{who}: x must be (B,T,C), got {tuple(x.shape)}")
     xg = x.detach().clone().requires_grad_(True)
-    try:
-        scope.eval()
-        for p in frozen:
-            p.requires_grad_(False)
-        if fcn is not None:
-            fcn.input_grad = True
-        with torch.enable_grad():
-            logits = run(xg)
-            B = logits.shape[0]
-            if target is None:
-                idx = logits.detach().argmax(dim=1)
-            elif torch.is_tensor(target):
-                idx = target.to(device=logits.device, dtype=torch.long).reshape(-1)
-                if idx.numel() != B:
-                    raise ValueError(f"input_saliency: target has {idx.numel()} entries for a batch of {B}")
-            else:
-                idx = torch.full((B,), int(target), device=logits.device, dtype=torch.long)
-            if bool(((idx < 0) | (idx >= logits.shape[1])).any()):
-                raise ValueError(f"input_saliency: target outside [0, {logits.shape[1]})")
-            # samples are independent (instance norm and the bank act per sample, BatchNorm uses its running statistics), so the
-            # gradient of the sum of the selected logits is, row by row, the gradient of each sample's own logit
-            picked = logits.gather(1, idx[:, None]).sum()
-            grad, = torch.autograd.grad(picked, xg)
-    finally:
-        for p in frozen:
-            p.requires_grad_(True)
-        for mod, flag in modes:
-            mod.training = flag
-        if fcn is not None:
-            if had_switch:
-                fcn.input_grad = switch
-            else:
-                vars(fcn).pop("input_grad", None)
+    with session(scope, grad=True, freeze=True, fcn=fcn, switch="input_grad"):
+        logits = run(xg)
+        idx = resolve_target(target, logits, who)
+        # samples are independent (instance norm and the bank act per sample, BatchNorm uses its running statistics), so the
+        # gradient of the sum of the selected logits is, row by row, the gradient of each sample's own logit
+        grad, = torch.autograd.grad(logits.gather(1, idx[:, None]).sum(), xg)
     return grad

@@ -153,8 +153,12 @@ def test_evidence_flag_parses_and_defaults_to_none():
     # neither run.py nor the experiment module imports utils.evidence at module level
     import inspect
     import exp.experiment_classification as X
-    guard = [ln for ln in inspect.getsource(run.main).splitlines() if "write_evidence(" in ln or "'evidence'" in ln]
-    assert len(guard) == 2 and "!= 'none'" in guard[0]
+    guard = [ln for ln in inspect.getsource(run.main).splitlines() if "EXPLAIN_FLAGS" in ln or "writer(" in ln or "_flag_on(" in ln]
+    assert len(guard) == 3 and "_flag_on(args, flag)" in guard[1] and "!= 'none'" in inspect.getsource(run._flag_on)
+    assert "evidence" not in inspect.getsource(run.main)
+    rows = [row for row in run.EXPLAIN_FLAGS if row[0] == "evidence"]
+    assert len(rows) == 1 and rows[0][1] is None and "write_evidence(" in inspect.getsource(rows[0][3])
+    assert not run._flag_on(run.build_parser().parse_args(base), "evidence")
     assert not hasattr(run, "evidence_map") and not hasattr(X, "evidence_map") and not hasattr(X, "Evidence")
 
 

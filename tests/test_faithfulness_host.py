@@ -202,8 +202,14 @@ def test_default_none_parses_imports_and_launches_nothing(monkeypatch):
     import inspect
     import run
     import exp.experiment_classification as X
-    guard = [ln for ln in inspect.getsource(run.main).splitlines() if "faithfulness" in ln]
-    assert len(guard) == 2 and "!= 'none'" in guard[0] and "write_faithfulness(" in guard[1]
+    # run.main reaches the writer through the one table of explanation flags, behind the one "flag is on" predicate
+    guard = [ln for ln in inspect.getsource(run.main).splitlines() if "EXPLAIN_FLAGS" in ln or "writer(" in ln or "_flag_on(" in ln]
+    assert len(guard) == 3 and "_flag_on(args, flag)" in guard[1] and "!= 'none'" in inspect.getsource(run._flag_on)
+    assert "faithfulness" not in inspect.getsource(run.main)
+    rows = [row for row in run.EXPLAIN_FLAGS if "faithfulness" in str(row[:3])]
+    assert len(rows) == 1 and rows[0][0] == "faithfulness" and rows[0][1] == "utils.faithfulness.parse_faithfulness"
+    assert rows[0][3] is run.write_faithfulness
+    assert not run._flag_on(run.build_parser().parse_args(["--model", "SBM", "--data", "SYNTH"]), "faithfulness")
     assert not any(hasattr(m, n) for m in (run, X) for n in ("faithfulness_curves", "parse_faithfulness", "Faithfulness"))
     monkeypatch.delitem(sys.modules, "utils.faithfulness")
     run.check_args(run.build_parser().parse_args(["--model", "SBM", "--data", "SYNTH"]))

@@ -200,9 +200,14 @@ def test_default_none_parses_imports_and_launches_nothing(monkeypatch):
     import inspect
     import run
     import exp.experiment_classification as X
-    guard = [ln for ln in inspect.getsource(run.main).splitlines() if "occlusion" in ln]
-    assert len(guard) == 2 and "!= 'none'" in guard[0] and "write_occlusion(" in guard[1]
-    assert not any(word in ln for ln in guard for word in ("evidence", "faithfulness"))
+    # run.main reaches the writer through the one table of explanation flags, behind the one "flag is on" predicate
+    guard = [ln for ln in inspect.getsource(run.main).splitlines() if "EXPLAIN_FLAGS" in ln or "writer(" in ln or "_flag_on(" in ln]
+    assert len(guard) == 3 and "_flag_on(args, flag)" in guard[1] and "!= 'none'" in inspect.getsource(run._flag_on)
+    assert "occlusion" not in inspect.getsource(run.main)
+    rows = [row for row in run.EXPLAIN_FLAGS if "occlusion" in str(row[:3])]
+    assert len(rows) == 1 and rows[0][0] == "occlusion" and rows[0][1] == "utils.occlusion.parse_occlusion"
+    assert "write_occlusion(" in inspect.getsource(rows[0][3])
+    assert not run._flag_on(run.build_parser().parse_args(["--model", "SBM", "--data", "SYNTH"]), "occlusion")
     assert not any(hasattr(m, n) for m in (run, X) for n in ("occlusion_map", "parse_occlusion", "Occlusion"))
     monkeypatch.delitem(sys.modules, "utils.occlusion")
     run.check_args(run.build_parser().parse_args(["--model", "SBM", "--data", "SYNTH"]))
