@@ -403,7 +403,7 @@ int ign_shapelet_project_step_bank(const float* xn_bct, const float* dmin, const
                                    int accumulate, int B, int C, int T, const int* K, const int* L, const int* stride, void* stream);
 
 /* Augmentation (csrc/ign_augment.hip; run.py --augment): the training batch x (B,T,C) -> out (B,T,C), one launch, out of place
- * (x == out: IGN_E_ARG; the buffers must not overlap), no workspace, no atomics, bitwise repeatable.  len_b (B) int32 on the DEVICE
+ * (x == out or overlapping buffers: IGN_E_ARG), no workspace, no atomics, bitwise repeatable.  len_b (B) int32 on the DEVICE
  * or NULL (every sample has T steps); n = len_b[b] clamped to 0..T.
  *   out[b,t,c] = keepC[b,c] * keepT[b,t] * (a[b,c] * x[b, (t - s_b) mod n, c] + sigma * n[b,t,c])   for t <  n
  *   out[b,t,c] = x[b,t,c]                                                                          for t >= n (padding: no noise)

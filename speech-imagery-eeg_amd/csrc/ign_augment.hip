@@ -11,7 +11,7 @@
 // Per-sample draws are block-uniform (one Philox call per lane, the same in every lane); per-(b, c) draws are taken once per
 // block into LDS, and only when the gain or the electrode dropout is on.  The noise path is a separate instantiation: with
 // sigma == 0 no Philox call, logarithm, square root or sine is issued per element.
-#include "ign_common.h"
+#include "ign_btc.h"
 #include "ign_augment.h"
 
 constexpr int AUG_THREADS = 256;
@@ -38,7 +38,7 @@ __global__ void __launch_bounds__(AUG_THREADS) augment_kernel(const AugArgs a) {
     const int b = blockIdx.x / a.nchunk;
     const int chunk = blockIdx.x - b * a.nchunk;
     const int C = a.C, TC = a.T * C;
-    const int len = a.len ? min(max(a.len[b], 0), a.T) : a.T;    // device data: clamped, never trusted as an index bound
+    const int len = IGN_BTC_LEN(a.len, b, a.T);
     const int n = len * C;                                        // flat indices of data; padding from there to TC
     const IgnAugSample sp = ign_aug_sample(a.seed, (uint32_t)b, len, a.shift, a.time_mask);
     const int shc = sp.sh * C;                                    // in [0, n)
@@ -102,20 +102,15 @@ __global__ void __launch_bounds__(AUG_THREADS) augment_kernel(const AugArgs a) {
     }
 }
 
-static bool aug_rate_ok(float r) { return r >= 0.f && r < 1.f; }  // false for NaN
-
 extern "C" int ign_augment_btc(const float* x, float* out, const int32_t* len_b, int B, int T, int C, unsigned long long seed,
                                float shift, float scale, float sigma, unsigned chan_thr, float time_mask, void* stream) {
     static const char* who = "ign_augment_btc";
-    if (!x || !out || B < 1 || T < 1 || C < 1) {
-        ign_set_error("%s: null pointer or non-positive dimension (B=%d T=%d C=%d)", who, B, T, C);
-        return IGN_E_ARG;
+    if (C > AUG_CMAX) {                                           // ahead of the overlap rule, whose span grows with C
+        ign_set_error("%s: C=%d above %d channels", who, C, AUG_CMAX);
+        return IGN_E_TOOBIG;
     }
-    if (x == out) {
-        ign_set_error("%s: out of place only (a shifted row reads what another lane writes): x == out", who);
-        return IGN_E_ARG;
-    }
-    if (!aug_rate_ok(shift) || !aug_rate_ok(scale) || !aug_rate_ok(time_mask) || chan_thr >= 65536u) {
+    if (const int rc = ign_btc_check(who, x, out, B, T, C)) return rc;
+    if (!ign_rate_ok(shift) || !ign_rate_ok(scale) || !ign_rate_ok(time_mask) || chan_thr >= 65536u) {
         ign_set_error("%s: shift=%g scale=%g time_mask=%g must lie in [0, 1) and chan_thr=%u below 65536", who, (double)shift,
                       (double)scale, (double)time_mask, chan_thr);
         return IGN_E_ARG;
@@ -124,16 +119,8 @@ extern "C" int ign_augment_btc(const float* x, float* out, const int32_t* len_b,
         ign_set_error("%s: sigma=%g must be finite and non-negative", who, (double)sigma);
         return IGN_E_ARG;
     }
-    const long long TC = (long long)T * C;
-    if (C > AUG_CMAX || TC > 0x7fff0000LL) {
-        ign_set_error("%s: C=%d above %d channels, or T*C=%lld does not fit a 32-bit index", who, C, AUG_CMAX, TC);
-        return IGN_E_TOOBIG;
-    }
-    const long long nchunk = (TC + AUG_CHUNK - 1) / AUG_CHUNK;
-    if ((long long)B * nchunk > 0x7fffffffLL) {
-        ign_set_error("%s: B=%d T=%d C=%d needs more blocks than a grid has", who, B, T, C);
-        return IGN_E_TOOBIG;
-    }
+    const long long nchunk = ((long long)T * C + AUG_CHUNK - 1) / AUG_CHUNK;
+    if (const int rc = ign_btc_grid_check(who, B, T, C, nchunk)) return rc;
     AugArgs a;
     a.x = x; a.out = out; a.len = len_b; a.T = T; a.C = C; a.nchunk = (int)nchunk; a.seed = seed;
     a.shift = shift; a.scale = scale; a.sigma = sigma; a.time_mask = time_mask; a.chan_thr = chan_thr;

@@ -10,7 +10,7 @@
 // per element, not separate paths.  A sample with lam == 1 and an empty span, and every quad of the padding, is a copy that never
 // reads the partner: 1 * x + 0 * x_p would turn an infinite partner into NaN.
 #include <cstdint>
-#include "ign_common.h"
+#include "ign_btc.h"
 
 constexpr int MIX_THREADS = 256;
 constexpr int MIX_QUADS = 4;                                   // quads per lane
@@ -39,7 +39,7 @@ __global__ void __launch_bounds__(MIX_THREADS) mix_kernel(const MixArgs a) {
     const int b = blockIdx.x / a.nchunk;
     const int chunk = blockIdx.x - b * a.nchunk;
     const int C = a.C, TC = a.T * C;
-    const int len = a.len ? min(max(a.len[b], 0), a.T) : a.T;    // device data: clamped, never trusted as an index bound
+    const int len = IGN_BTC_LEN(a.len, b, a.T);
     const int n = len * C;                                        // flat indices of data; padding from there to TC
     int start = 0, m = 0;
     if (a.span) {
@@ -82,30 +82,13 @@ __global__ void __launch_bounds__(MIX_THREADS) mix_kernel(const MixArgs a) {
 extern "C" int ign_mix_btc(const float* x, float* out, const int32_t* len_b, const float* lam_b, const int32_t* span_b2, int roll,
                            int B, int T, int C, void* stream) {
     static const char* who = "ign_mix_btc";
-    if (!x || !out || !lam_b || B < 1 || T < 1 || C < 1) {
-        ign_set_error("%s: null pointer or non-positive dimension (B=%d T=%d C=%d)", who, B, T, C);
+    if (const int rc = ign_btc_check(who, x, out, B, T, C)) return rc;
+    if (!lam_b || roll < 0 || roll >= B) {
+        ign_set_error("%s: null lam_b, or roll=%d outside [0, B) with B=%d", who, roll, B);
         return IGN_E_ARG;
     }
-    if (roll < 0 || roll >= B) {
-        ign_set_error("%s: roll=%d outside [0, B) with B=%d", who, roll, B);
-        return IGN_E_ARG;
-    }
-    const long long TC = (long long)T * C;
-    if (TC > 0x7fff0000LL) {
-        ign_set_error("%s: T*C=%lld does not fit a 32-bit index", who, TC);
-        return IGN_E_TOOBIG;
-    }
-    const long long nchunk = (TC + MIX_CHUNK - 1) / MIX_CHUNK;
-    if ((long long)B * nchunk > 0x7fffffffLL) {
-        ign_set_error("%s: B=%d T=%d C=%d needs more blocks than a grid has", who, B, T, C);
-        return IGN_E_TOOBIG;
-    }
-    const uintptr_t xa = (uintptr_t)x, oa = (uintptr_t)out, bytes = (uintptr_t)B * (uintptr_t)TC * sizeof(float);
-    if ((xa <= oa ? oa - xa : xa - oa) < bytes) {
-        ign_set_error("%s: out of place only (a sample reads its partner's rows, which another block writes): x and out overlap",
-                      who);
-        return IGN_E_ARG;
-    }
+    const long long nchunk = ((long long)T * C + MIX_CHUNK - 1) / MIX_CHUNK;
+    if (const int rc = ign_btc_grid_check(who, B, T, C, nchunk)) return rc;
     MixArgs a;
     a.x = x; a.out = out; a.len = len_b; a.lam = lam_b; a.span = span_b2; a.roll = roll; a.B = B; a.T = T; a.C = C;
     a.nchunk = (int)nchunk;

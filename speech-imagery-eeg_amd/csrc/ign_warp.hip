@@ -11,7 +11,7 @@
 // lanes with LX the smallest power of two that holds a row's units (at most 256), so for a short row a wave carries several rows.
 // A tile of the padding, a sample that is not warped and a call with every rate 0 take the copy path: no LDS, no arithmetic.
 #include <cstdint>
-#include "ign_common.h"
+#include "ign_btc.h"
 #include "ign_warp.h"
 
 constexpr int WARP_THREADS = 256;
@@ -44,7 +44,7 @@ __global__ void __launch_bounds__(WARP_THREADS) warp_kernel(const WarpArgs a) {
     const int r0 = (blockIdx.x - b * a.ntile) * a.rows;
     const int nr = min(a.rows, a.T - r0);                          // rows of this tile, >= 1
     const int C = a.C, U = C / VEC;
-    const int n = a.len ? min(max(a.len[b], 0), a.T) : a.T;       // device data: clamped, never trusted as an index bound
+    const int n = IGN_BTC_LEN(a.len, b, a.T);
     const bool rates = a.twarp > 0.f || a.mwarp > 0.f || a.wwarp > 0.f;
     IgnWarpSample sp = {false, 0, 0, 1.0f};
     if (rates && r0 < n) sp = ign_warp_sample(a.seed, (uint32_t)b, n, a.wwarp, a.prob);      // block-uniform; false for n < 2
@@ -95,10 +95,8 @@ __global__ void __launch_bounds__(WARP_THREADS) warp_kernel(const WarpArgs a) {
     }
 }
 
-static bool warp_rate_ok(float r) { return r >= 0.f && r < 1.f; }  // false for NaN
-
 static int warp_check_rule(const char* who, float twarp, float mwarp, float wwarp, int knots, float prob) {
-    if (!warp_rate_ok(twarp) || !warp_rate_ok(mwarp) || !warp_rate_ok(wwarp)) {
+    if (!ign_rate_ok(twarp) || !ign_rate_ok(mwarp) || !ign_rate_ok(wwarp)) {
         ign_set_error("%s: twarp=%g mwarp=%g wwarp=%g must lie in [0, 1)", who, (double)twarp, (double)mwarp, (double)wwarp);
         return IGN_E_ARG;
     }
@@ -141,29 +139,18 @@ extern "C" int ign_warp_map(unsigned long long seed, int b, int n, float twarp, 
 extern "C" int ign_warp_btc(const float* x, float* out, const int32_t* len_b, int B, int T, int C, unsigned long long seed,
                             float twarp, float mwarp, float wwarp, int knots, float prob, void* stream) {
     static const char* who = "ign_warp_btc";
-    if (!x || !out || B < 1 || T < 1 || C < 1) {
-        ign_set_error("%s: null pointer or non-positive dimension (B=%d T=%d C=%d)", who, B, T, C);
-        return IGN_E_ARG;
-    }
+    if (const int rc = ign_btc_check(who, x, out, B, T, C)) return rc;
     if (const int rc = warp_check_rule(who, twarp, mwarp, wwarp, knots, prob)) return rc;
-    const long long TC = (long long)T * C;
-    if (T > IGN_WARP_MAX_T || TC > 0x7fff0000LL) {
-        ign_set_error("%s: T=%d above IGN_WARP_MAX_T=%d, or T*C=%lld does not fit a 32-bit index", who, T, IGN_WARP_MAX_T, TC);
+    if (T > IGN_WARP_MAX_T) {
+        ign_set_error("%s: T=%d above IGN_WARP_MAX_T=%d", who, T, IGN_WARP_MAX_T);
         return IGN_E_TOOBIG;
     }
     int rows = WARP_TILE_ELEMS / C;
     rows = rows < 1 ? 1 : rows > WARP_MAX_ROWS ? WARP_MAX_ROWS : rows;
     rows = rows < T ? rows : T;
     const long long ntile = ((long long)T + rows - 1) / rows;
-    if ((long long)B * ntile > 0x7fffffffLL) {
-        ign_set_error("%s: B=%d T=%d C=%d needs more blocks than a grid has", who, B, T, C);
-        return IGN_E_TOOBIG;
-    }
-    const uintptr_t xa = (uintptr_t)x, oa = (uintptr_t)out, bytes = (uintptr_t)B * (uintptr_t)TC * sizeof(float);
-    if ((xa <= oa ? oa - xa : xa - oa) < bytes) {
-        ign_set_error("%s: out of place only (an output row reads two source rows that another lane writes): x and out overlap", who);
-        return IGN_E_ARG;
-    }
+    if (const int rc = ign_btc_grid_check(who, B, T, C, ntile)) return rc;
+    const uintptr_t xa = (uintptr_t)x, oa = (uintptr_t)out;
     const int vec = (C % 4 == 0 && ((xa | oa) & 15) == 0) ? 4 : (C % 2 == 0 && ((xa | oa) & 7) == 0) ? 2 : 1;
     const int U = C / vec;
     int lx_log2 = 0;

@@ -101,9 +101,7 @@ class Experiment(object):
         self._report_eeg_artifact()     # --eeg_artifact ...,report: one pass over the raw training trials, before the model is built
         self._get_params_from_data()
         self._resolve_loss_options()
-        self._resolve_warp()
-        self._resolve_augment()
-        self._resolve_mix()
+        self._resolve_train_transforms()
         # host -> device double buffering (and, for raw CHISCO shards, the on-GPU standardise + transpose)
         self.train_loader, self.val_loader, self.test_loader = (self._prefetch(l) for l in
                                                                 (self.train_loader, self.val_loader, self.test_loader))
@@ -192,102 +190,12 @@ class Experiment(object):
             print(f"class weights ({self.args.class_weight if spec == 'balanced' else 'given'}): "
                   f"{[round(float(v), 4) for v in w]}")
 
-    def _resolve_warp(self):
-        """--warp -> self._warp_spec (None when off: nothing is parsed beyond the word and the training loops do nothing extra -- no
-        launch, no mask sum, no seed arithmetic) and the base seed of utils.augment.step_seed, by --augment's rule: --seed when it
-        is >= 0, else torch's initial seed (reading it does not advance the generator)."""
-        text = getattr(self.args, 'warp', None)
-        self._warp_spec = None
-        if text is None or (isinstance(text, str) and text.strip().lower() in ('', 'none')):
-            return
-        from utils.warp import parse_warp
-        spec = parse_warp(text)
-        if not spec.active:
-            return
-        self._warp_spec = spec
-        seed = int(getattr(self.args, 'seed', -1))
-        self._warp_base = seed if seed >= 0 else int(torch.initial_seed())
-        if self.rank == 0:
-            print(f"warp: {', '.join(f'{k}={v:g}' for k, v in spec._asdict().items() if v and (k != 'prob' or v != 1.0))}")
-
-    def _warp(self, batch_x, padding_mask, train_step):
-        """The training batch of step `train_step`, warped along time on the device in one launch (ops.warp; seed = step_seed(base,
-        rank, step), so ranks draw different warps and the eager and captured loops the same ones), in front of _augment.  Each
-        sample is warped inside its own length -- the keep-mask's row sum, taken on the device without a host sync; an all-ones mask
-        gives what no lengths give -- so the padding and the mask stay as they are.  Labels and regression targets are per trial and
-        do not move.  Training only: validation, test, saliency, the k-means initialisation, the projection, the alignment fit and
-        the artifact report never call it."""
-        if self._warp_spec is None:
-            return batch_x
-        from utils.augment import step_seed
-        lengths = padding_mask.sum(1).to(torch.int32)
-        return ign_ops.warp(batch_x.contiguous(), step_seed(self._warp_base, self.rank, train_step), lengths=lengths,
-                            **self._warp_spec._asdict())
-
-    def _resolve_augment(self):
-        """--augment -> self._augment_spec (None when off: the training loops then do nothing extra -- no launch, no mask sum, no
-        seed arithmetic, no generator use) and the base seed of utils.augment.step_seed: --seed when it is >= 0, else torch's
-        initial seed (reading it does not advance the generator)."""
-        from utils.augment import parse_augment
-        spec = parse_augment(getattr(self.args, 'augment', None))
-        self._augment_spec = spec if spec.active else None
-        if self._augment_spec is not None:
-            seed = int(getattr(self.args, 'seed', -1))
-            self._augment_base = seed if seed >= 0 else int(torch.initial_seed())
-            if self.rank == 0:
-                print(f"augment: {', '.join(f'{k}={v:g}' for k, v in spec._asdict().items() if v)}")
-
-    def _augment(self, batch_x, padding_mask, train_step):
-        """The training batch of step `train_step`, augmented on the device in one launch (ops.augment; seed = step_seed(base, rank,
-        step), so ranks draw different augmentations and the eager and captured loops the same ones).  Each sample is shifted,
-        masked and noised inside its own length -- the keep-mask's row sum, taken on the device without a host sync; an all-ones
-        mask gives what no lengths give.  Training only: validation, test, saliency and the k-means initialisation never call it."""
-        if self._augment_spec is None:
-            return batch_x
-        from utils.augment import step_seed
-        lengths = padding_mask.sum(1).to(torch.int32)
-        return ign_ops.augment(batch_x.contiguous(), step_seed(self._augment_base, self.rank, train_step), lengths=lengths,
-                               **self._augment_spec._asdict())
-
-    def _resolve_mix(self):
-        """--mix -> self._mix_spec (None when off: the training loops then do nothing extra -- no draw, no launch, no further static
-        input, today's loss entry points).  The draws share --augment's per-step seed rule (utils.augment.step_seed) and base seed.
-        The regression task refuses the flag: its CRPS tails take one real-valued target per row."""
-        from utils.mix import parse_mix
-        spec = parse_mix(getattr(self.args, 'mix', None))
-        self._mix_spec = spec if spec.active else None
-        if self._mix_spec is None:
-            return
-        if getattr(self.args, 'task_name', 'classification') == 'regression':
-            raise ValueError("--mix with --task_name regression: mixup / CutMix mix class labels through the cross-entropy tails; "
-                             "the CRPS tails have no soft-label form")
-        seed = int(getattr(self.args, 'seed', -1))
-        self._mix_base = seed if seed >= 0 else int(torch.initial_seed())
-        if self.rank == 0:
-            print(f"mix: {', '.join(f'{k}={v:g}' for k, v in spec._asdict().items() if v and (k != 'prob' or v != 1.0))}")
-
-    def _mix(self, batch_x, label, padding_mask, train_step):
-        """The training batch of step `train_step` mixed on the device in one launch (ops.mix) -> (batch, (label_b, lam)): the soft
-        labels _train_loss takes after `label`; (batch_x, ()) when --mix is off.  The draws are made on the host
-        (utils.mix.mix_draws under step_seed(base, rank, step): ranks differ, the eager and captured loops agree, no torch generator
-        is consumed) and reach the device from pinned memory without blocking.  Sample b is paired with (b + roll) mod B -- the
-        loader has shuffled already -- and mixed inside its own length, the keep-mask's row sum; only CutMix, whose span depends on
-        the length, reads the lengths back to the host (one small synchronising copy per step; mixup alone draws as for full
-        lengths and never waits for the device).  Training only: validation, test, saliency, the k-means initialisation and
-        the projection never call it."""
-        if self._mix_spec is None:
-            return batch_x, ()
-        from utils.augment import step_seed
-        from utils.mix import mix_draws
-        B, T = batch_x.shape[0], batch_x.shape[1]
-        lengths = padding_mask.sum(1).to(torch.int32)
-        host_lengths = lengths.cpu().numpy() if self._mix_spec.cutmix > 0.0 else T
-        roll, lam, span = mix_draws(step_seed(self._mix_base, self.rank, train_step), B, host_lengths, self._mix_spec)
-        put = (lambda a: torch.from_numpy(a).pin_memory().to(self.device, non_blocking=True)) if self.device.type == 'cuda' \
-            else torch.from_numpy
-        lam = put(lam)
-        span = put(span) if self._mix_spec.cutmix > 0.0 else None
-        return ign_ops.mix(batch_x.contiguous(), lam, roll, span=span, lengths=lengths), (label.roll(-roll), lam)
+    def _resolve_train_transforms(self):
+        """--warp / --augment / --mix -> self._transforms, the chain that both training loops call once per step
+        (utils/train_transforms.py); false when all three are off: the loops then do nothing extra.  What is refused (--mix with
+        the regression task) raises here, for callers that build the namespace themselves."""
+        from utils.train_transforms import TrainTransforms
+        self._transforms = TrainTransforms.from_args(self.args, self.rank)
 
     def _resolve_optim_options(self):
         """--weight_decay / --lr_schedule / --ema -> self._optim_options (weight decay, LrSchedule, EMA decay) and self._optim_active
@@ -448,9 +356,7 @@ class Experiment(object):
         for batch_x, label, padding_mask in self.train_loader:
             train_step += 1
             batch_x, label, padding_mask = self._to_device(batch_x, label, padding_mask)
-            batch_x = self._warp(batch_x, padding_mask, train_step)
-            batch_x = self._augment(batch_x, padding_mask, train_step)
-            batch_x, soft = self._mix(batch_x, label, padding_mask, train_step)
+            batch_x, soft = self._transforms(batch_x, label, padding_mask, train_step)
             with torch.autocast(device_type=self.device.type, dtype=torch.bfloat16, enabled=amp):
                 logits, info = self._forward(batch_x, padding_mask)
                 loss = self._train_loss(logits, info, label, compute_beta(epoch, a.train_epochs, a.beta_schedule), amp, *soft)
@@ -494,7 +400,7 @@ class Experiment(object):
     def _train_loss(self, logits, info, label, beta, amp, label_b=None, lam=None):
         """The training loss of one step (IGN/exp/experiment_classification.py:319-329); `beta` weighs InterpGN's SBM term.
         Every cross-entropy of it takes the run's class weights and label smoothing (_resolve_loss_options), and under --mix the
-        soft labels (label, label_b, lam) of _mix: the fused tail's soft-label entry point for InterpGN, utils.mix.mix_cross_entropy
+        soft labels (label, label_b, lam) of self._transforms: the fused tail's soft-label entry point for InterpGN, utils.mix.mix_cross_entropy
         where the criterion is torch's."""
         a = self.args
         w, eps = self.class_weight, self.label_smoothing
@@ -586,9 +492,8 @@ class Experiment(object):
         for batch_x, label, padding_mask in self.train_loader:
             train_step += 1
             batch_x, label, padding_mask = self._to_device(batch_x, label, padding_mask)
-            batch_x = self._warp(batch_x, padding_mask, train_step)         # outside the graph, as the two calls below
-            batch_x = self._augment(batch_x, padding_mask, train_step)      # outside the graph: its static input takes this batch
-            batch_x, soft = self._mix(batch_x, label, padding_mask, train_step)     # likewise; label_b / lam are static inputs too
+            # outside the graph: its static inputs take this batch and, under --mix, label_b / lam
+            batch_x, soft = self._transforms(batch_x, label, padding_mask, train_step)
             inputs = (batch_x, label, padding_mask, *soft)
             kind, fn = ('close', step_fn) if train_step % K == 0 else ('micro', micro_fn)
             if batch_x.shape[0] != a.batch_size:                  # ragged last batch: eager

@@ -382,6 +382,29 @@ def eeg_artifact(x_nct, clip=None, flat=None, noisy=None, neighbors=None, out=No
     return y, verdict, stats
 
 
+_UNSEEDED = object()
+
+
+def _batch_transform(name, acts, x, lengths, check, seed=_UNSEEDED, more=()):
+    """The shared opening of ops.augment / ops.warp / ops.mix, in the order in which each of them refuses: fp32 on the GPU (`x` and
+    `more`), a contiguous (B,T,C) batch without a gradient, for a seeded op no graph capture, then the op's own `check()`; ->
+    (out, lengths, seed): a new tensor like `x`, and for B > 0 the checked lengths and the seed as 64 bits.  B == 0: nothing to launch."""
+    _need_gpu(name, x, *more)
+    if x.dim() != 3 or not x.is_contiguous():
+        raise _lib.IgnError(f"{name}: expected a contiguous (B,T,C) tensor, got shape {tuple(x.shape)} strides {x.stride()}")
+    if x.requires_grad:
+        raise _lib.IgnError(f"{name}: the input requires a gradient; {acts} acts on data (there is no backward pass)")
+    if seed is not _UNSEEDED and torch.cuda.is_current_stream_capturing():
+        raise _lib.IgnError(f"{name} inside a hipGraph capture: the per-call seed would be frozen into the graph ({name} the batch "
+                            f"before the captured step)")
+    check()
+    out = torch.empty_like(x)
+    if x.shape[0]:
+        lengths = None if lengths is None else _lengths(name, lengths, x.shape[0])
+        seed = None if seed is _UNSEEDED else int(seed) & 0xFFFFFFFFFFFFFFFF
+    return out, lengths, seed
+
+
 def augment(x, seed, *, lengths=None, shift=0.0, scale=0.0, noise=0.0, channel_drop=0.0, time_mask=0.0):
     """Training augmentation of a contiguous fp32 (B,T,C) batch on the GPU -> a new tensor (ign_augment_btc; the rule is
     csrc/ign_augment.h, restated in utils/augment.py): a circular shift by up to `shift` * length, a per-channel gain in
@@ -392,31 +415,22 @@ def augment(x, seed, *, lengths=None, shift=0.0, scale=0.0, noise=0.0, channel_d
     Refused for an input that requires a gradient (a training batch never does) and during graph capture (the seed is a host
     value: a replay would repeat one augmentation)."""
     name = "augment"
-    _need_gpu(name, x)
-    if x.dim() != 3 or not x.is_contiguous():
-        raise _lib.IgnError(f"{name}: expected a contiguous (B,T,C) tensor, got shape {tuple(x.shape)} strides {x.stride()}")
-    if x.requires_grad:
-        raise _lib.IgnError(f"{name}: the input requires a gradient; augmentation acts on data (there is no backward pass)")
-    if torch.cuda.is_current_stream_capturing():
-        raise _lib.IgnError(f"{name} inside a hipGraph capture: the per-call seed would be frozen into the graph (augment the batch "
-                            f"before the captured step)")
-    for what, v in (("shift", shift), ("scale", scale), ("time_mask", time_mask)):
-        if not 0.0 <= ctypes.c_float(v).value < 1.0:
-            raise ValueError(f"{name}: {what} = {v} outside [0, 1)")
-    if not 0.0 <= ctypes.c_float(noise).value < float("inf"):
-        raise ValueError(f"{name}: noise = {noise} must be finite and >= 0")
-    try:
-        thr = dropout_threshold(channel_drop)[0]               # the keep rule of attention dropout: halfword >= round(p * 65536)
-    except ValueError:
-        raise ValueError(f"{name}: channel_drop = {channel_drop} outside [0, 1)") from None
+
+    def check():
+        for what, v in (("shift", shift), ("scale", scale), ("time_mask", time_mask)):
+            if not 0.0 <= ctypes.c_float(v).value < 1.0:
+                raise ValueError(f"{name}: {what} = {v} outside [0, 1)")
+        if not 0.0 <= ctypes.c_float(noise).value < float("inf"):
+            raise ValueError(f"{name}: noise = {noise} must be finite and >= 0")
+        try:
+            dropout_threshold(channel_drop)                        # the keep rule of attention dropout: halfword >= round(p * 65536)
+        except ValueError:
+            raise ValueError(f"{name}: channel_drop = {channel_drop} outside [0, 1)") from None
+    out, lengths, seed = _batch_transform(name, "augmentation", x, lengths, check, seed)
     B, T, C = x.shape
-    out = torch.empty_like(x)
-    if B == 0:
-        return out
-    if lengths is not None:
-        lengths = _lengths(name, lengths, B)
-    _lib.check(_lib.lib().ign_augment_btc(_ptr(x), _ptr(out), _ptr(lengths), B, T, C, int(seed) & 0xFFFFFFFFFFFFFFFF, shift, scale,
-                                          noise, thr, time_mask, _stream()), "ign_augment_btc")
+    if B:
+        _lib.check(_lib.lib().ign_augment_btc(_ptr(x), _ptr(out), _ptr(lengths), B, T, C, seed, shift, scale, noise,
+                                              dropout_threshold(channel_drop)[0], time_mask, _stream()), "ign_augment_btc")
     return out
 
 
@@ -431,24 +445,13 @@ def warp(x, seed, lengths=None, twarp=0.0, mwarp=0.0, wwarp=0.0, knots=4, prob=1
     Refused for an input that requires a gradient (a training batch never does) and during graph capture (the seed is a host
     value: a replay would repeat one warp)."""
     name = "warp"
-    _need_gpu(name, x)
-    if x.dim() != 3 or not x.is_contiguous():
-        raise _lib.IgnError(f"{name}: expected a contiguous (B,T,C) tensor, got shape {tuple(x.shape)} strides {x.stride()}")
-    if x.requires_grad:
-        raise _lib.IgnError(f"{name}: the input requires a gradient; warping acts on data (there is no backward pass)")
-    if torch.cuda.is_current_stream_capturing():
-        raise _lib.IgnError(f"{name} inside a hipGraph capture: the per-call seed would be frozen into the graph (warp the batch "
-                            f"before the captured step)")
     from utils.warp import check_spec
-    check_spec(twarp, mwarp, wwarp, knots, prob, who=name)
+    out, lengths, seed = _batch_transform(name, "warping", x, lengths, lambda: check_spec(twarp, mwarp, wwarp, knots, prob, who=name),
+                                          seed)
     B, T, C = x.shape
-    out = torch.empty_like(x)
-    if B == 0:
-        return out
-    if lengths is not None:
-        lengths = _lengths(name, lengths, B)
-    _lib.check(_lib.lib().ign_warp_btc(_ptr(x), _ptr(out), _ptr(lengths), B, T, C, int(seed) & 0xFFFFFFFFFFFFFFFF, twarp, mwarp,
-                                       wwarp, int(knots), prob, _stream()), "ign_warp_btc")
+    if B:
+        _lib.check(_lib.lib().ign_warp_btc(_ptr(x), _ptr(out), _ptr(lengths), B, T, C, seed, twarp, mwarp, wwarp, int(knots), prob,
+                                           _stream()), "ign_warp_btc")
     return out
 
 
@@ -460,27 +463,22 @@ def mix(x, lam, roll, span=None, lengths=None):
     the GPU; `roll`: a host integer in [0, B).  The draws come from utils.mix.mix_draws.  Refused for an input that requires a
     gradient (a training batch never does).  Every argument but `roll` is device data, so the call may be captured."""
     name = "mix"
-    _need_gpu(name, x, lam)
-    if x.dim() != 3 or not x.is_contiguous():
-        raise _lib.IgnError(f"{name}: expected a contiguous (B,T,C) tensor, got shape {tuple(x.shape)} strides {x.stride()}")
-    if x.requires_grad:
-        raise _lib.IgnError(f"{name}: the input requires a gradient; mixing acts on data (there is no backward pass)")
+
+    def check():
+        B = x.shape[0]
+        if tuple(lam.shape) != (B,):
+            raise _lib.IgnError(f"{name}: lam must be a float32 tensor of shape ({B},), got {tuple(lam.shape)}")
+        if span is not None and not (torch.is_tensor(span) and span.is_cuda and span.dtype == torch.int32 and tuple(span.shape) == (B, 2)):
+            what = f"{span.dtype} {tuple(span.shape)} on {span.device}" if torch.is_tensor(span) else type(span).__name__
+            raise _lib.IgnError(f"{name}: span must be an int32 tensor of shape ({B}, 2) on the GPU, got {what}")
+        if not 0 <= int(roll) < max(B, 1):
+            raise _lib.IgnError(f"{name}: roll = {int(roll)} outside [0, {B})")
+    out, lengths, _ = _batch_transform(name, "mixing", x, lengths, check, more=(lam,))
     B, T, C = x.shape
-    if tuple(lam.shape) != (B,):
-        raise _lib.IgnError(f"{name}: lam must be a float32 tensor of shape ({B},), got {tuple(lam.shape)}")
-    if span is not None and not (torch.is_tensor(span) and span.is_cuda and span.dtype == torch.int32 and tuple(span.shape) == (B, 2)):
-        what = f"{span.dtype} {tuple(span.shape)} on {span.device}" if torch.is_tensor(span) else type(span).__name__
-        raise _lib.IgnError(f"{name}: span must be an int32 tensor of shape ({B}, 2) on the GPU, got {what}")
-    roll = int(roll)
-    if not 0 <= roll < max(B, 1):
-        raise _lib.IgnError(f"{name}: roll = {roll} outside [0, {B})")
-    out = torch.empty_like(x)
-    if B == 0:
-        return out
-    if lengths is not None:
-        lengths = _lengths(name, lengths, B)
-    _lib.check(_lib.lib().ign_mix_btc(_ptr(x), _ptr(out), _ptr(lengths), _ptr(lam.contiguous()),
-                                      _ptr(None if span is None else span.contiguous()), roll, B, T, C, _stream()), "ign_mix_btc")
+    if B:
+        _lib.check(_lib.lib().ign_mix_btc(_ptr(x), _ptr(out), _ptr(lengths), _ptr(lam.contiguous()),
+                                          _ptr(None if span is None else span.contiguous()), int(roll), B, T, C, _stream()),
+                   "ign_mix_btc")
     return out
 
 

@@ -334,14 +334,8 @@ def check_args(args):
                          "(there is no length-aware k-means step); use --shapelet_init normal")
     from utils.class_weight import check_loss_options
     check_loss_options(args, _num_class_from_flags(args))
-    from utils.augment import parse_augment
-    parse_augment(getattr(args, 'augment', None))
-    from utils.warp import parse_warp
-    parse_warp(getattr(args, 'warp', None))
-    from utils.mix import parse_mix
-    if parse_mix(getattr(args, 'mix', None)).active and getattr(args, 'task_name', 'classification') == 'regression':
-        raise ValueError("--mix with --task_name regression: mixup / CutMix mix class labels through the cross-entropy tails; the "
-                         "CRPS tails have no soft-label form")
+    from utils.train_transforms import parse_flags
+    parse_flags(args)                               # --warp / --augment / --mix, and --mix with the regression task
     for flag, parser, follows, _ in EXPLAIN_FLAGS:
         if parser is not None and _flag_on(args, flag):
             module, _, name = parser.rpartition('.')

@@ -12,6 +12,8 @@ from typing import NamedTuple
 
 import numpy as np
 
+from utils.flag_items import FlagItems
+
 _M0, _M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
 _W0, _W1 = np.uint64(0x9E3779B9), np.uint64(0xBB67AE85)
 _MASK32, _SH32 = np.uint64(0xFFFFFFFF), np.uint64(32)
@@ -34,6 +36,7 @@ class AugmentSpec(NamedTuple):
 
 
 _KEYS = {'shift': 'shift', 'scale': 'scale', 'noise': 'noise', 'chan_drop': 'channel_drop', 'time_mask': 'time_mask'}
+_ITEMS = FlagItems("--augment", f"{'|'.join(_KEYS)}=VALUE", _KEYS, need_value=False, expected=False, strip_value=False)
 
 
 def channel_threshold(p):
@@ -47,21 +50,12 @@ def parse_augment(spec):
     repeated keys and values out of range raise ValueError."""
     if isinstance(spec, AugmentSpec):
         return spec
-    text = '' if spec is None else str(spec).strip()
-    if text.lower() in ('', 'none'):
+    text = _ITEMS.clean(spec)
+    if text is None:
         return AugmentSpec()
     got = {}
-    for item in text.split(','):
-        key, eq, val = item.partition('=')
-        key = key.strip()
-        if not eq or key not in _KEYS:
-            raise ValueError(f"--augment: {item!r} is not one of {'|'.join(_KEYS)}=VALUE")
-        if key in got:
-            raise ValueError(f"--augment: {key} given twice")
-        try:
-            v = float(val)
-        except ValueError:
-            raise ValueError(f"--augment: {key}={val!r} is not a number") from None
+    for key, val in _ITEMS.items(text):
+        v = _ITEMS.number(key, val, finite=False)
         if key == 'noise':
             if not (math.isfinite(v) and v >= 0.0):
                 raise ValueError(f"--augment: noise must be finite and >= 0, got {v}")

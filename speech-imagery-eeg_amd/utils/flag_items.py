@@ -8,10 +8,11 @@ import math
 class FlagItems:
     """`keys`: every key of the flag; `bare`: those that stand without ``=`` (``fit``, ``envelope``); `need_value`: an empty value
     behind ``=`` is refused here (else the flag's parser words it); `expected`: refusals other than "is not one of" end with
-    ``; expected <grammar>``."""
+    ``; expected <grammar>``; `strip_value`: False hands the value on as typed, for a flag whose refusals quote it so."""
 
-    def __init__(self, flag, grammar, keys, bare=(), need_value=True, expected=True):
+    def __init__(self, flag, grammar, keys, bare=(), need_value=True, expected=True, strip_value=True):
         self.flag, self.grammar, self.keys, self.bare, self.need_value = flag, grammar, tuple(keys), tuple(bare), bool(need_value)
+        self.strip_value = bool(strip_value)
         self.tail = f"; expected {grammar}" if expected else ""
 
     def clean(self, text):
@@ -20,12 +21,12 @@ class FlagItems:
         return None if text.lower() in ('', 'none') else text
 
     def items(self, text):
-        """(key, stripped value) per item, in the order given ('' for a bare key); the caller converts inside the loop, so the first
+        """(key, value) per item, in the order given ('' for a bare key); the caller converts inside the loop, so the first
         refusal is the left-most item's"""
         seen = set()
         for item in text.split(','):
             key, eq, val = item.partition('=')
-            key, val = key.strip(), val.strip()
+            key, val = key.strip(), val.strip() if self.strip_value else val
             if key not in self.keys or (key in self.bare) == bool(eq) or (self.need_value and eq and not val):
                 raise ValueError(f"{self.flag}: {item!r} is not one of {self.grammar}")
             if key in seen:

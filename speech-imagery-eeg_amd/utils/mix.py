@@ -31,6 +31,8 @@ from typing import NamedTuple
 
 import numpy as np
 
+from utils.flag_items import FlagItems
+
 
 class MixSpec(NamedTuple):
     """The parsed ``--mix`` flag: the Beta parameters of mixup and CutMix (0 = off) and the chance that a sample is mixed."""
@@ -43,7 +45,8 @@ class MixSpec(NamedTuple):
         return self.mixup > 0.0 or self.cutmix > 0.0
 
 
-_KEYS = ('mixup', 'cutmix', 'prob')
+_ITEMS = FlagItems("--mix", "mixup|cutmix|prob=VALUE", ('mixup', 'cutmix', 'prob'), need_value=False, expected=False,
+                   strip_value=False)
 
 
 def parse_mix(spec):
@@ -51,21 +54,12 @@ def parse_mix(spec):
     A > 0 (finite) is the Beta(A, A) parameter, prob in (0, 1].  Unknown or repeated keys and values out of range raise ValueError."""
     if isinstance(spec, MixSpec):
         return spec
-    text = '' if spec is None else str(spec).strip()
-    if text.lower() in ('', 'none'):
+    text = _ITEMS.clean(spec)
+    if text is None:
         return MixSpec()
     got = {}
-    for item in text.split(','):
-        key, eq, val = item.partition('=')
-        key = key.strip()
-        if not eq or key not in _KEYS:
-            raise ValueError(f"--mix: {item!r} is not one of {'|'.join(_KEYS)}=VALUE")
-        if key in got:
-            raise ValueError(f"--mix: {key} given twice")
-        try:
-            v = float(val)
-        except ValueError:
-            raise ValueError(f"--mix: {key}={val!r} is not a number") from None
+    for key, val in _ITEMS.items(text):
+        v = _ITEMS.number(key, val, finite=False)
         if key == 'prob':
             if not 0.0 < v <= 1.0:
                 raise ValueError(f"--mix: prob must be in (0, 1], got {v}")

@@ -194,7 +194,9 @@ def test_c_abi_refuses_in_place_and_bad_rates():
         return L.ign_augment_btc(src, dst, None, B, T, C, 7, shift, scale, sigma, thr, tm, _lib.stream())
     assert call(p, p) == -1001                                                          # IGN_E_ARG
     msg = L.ign_last_error().decode()
-    assert "ign_augment_btc" in msg and "x == out" in msg
+    assert "ign_augment_btc" in msg and "overlap" in msg
+    assert call(p, ctypes.c_void_p(x.data_ptr() + 4 * (2 * 8 * 3 - 1))) == -1001           # out at the last element of x
+    assert call(ctypes.c_void_p(out.data_ptr() + 4), q) == -1001                        # x begins inside out
     for kw in (dict(shift=1.0), dict(scale=1.0), dict(tm=1.0), dict(thr=65536), dict(sigma=-1.0), dict(sigma=float("nan")),
                dict(shift=float("nan")), dict(T=0), dict(B=0), dict(C=0)):
         assert call(p, q, **kw) == -1001, kw
@@ -312,15 +314,16 @@ def test_harness_ragged_batch_and_evaluation_untouched(tmp_path, monkeypatch):
     for b, n in enumerate(lens):
         mask[b, :n] = 1
         x[b, n:] = SENTINEL
-    out = e._augment(x, mask, 3)
+    out, soft = e._transforms(x, None, mask, 3)                   # --augment alone: the chain is that one stage
+    assert soft == () and (e._transforms.warp, e._transforms.mix) == (None, None)
     for b, n in enumerate(lens):
         assert bool((out[b, n:] == SENTINEL).all())
         assert n < 2 or not torch.equal(out[b, :n], x[b, :n])
-    spec = e._augment_spec._asdict()
+    spec = e._transforms.augment._asdict()
     want = ops.augment(x, step_seed(0, 0, 3), lengths=torch.tensor(lens, dtype=torch.int32, device=dev), **spec)
     assert torch.equal(out, want)
-    assert torch.equal(e._augment(x, torch.ones(B, T, device=dev), 3), ops.augment(x, step_seed(0, 0, 3), **spec))
-    assert plain._augment_spec is None and plain._augment(x, mask, 3) is x
+    assert torch.equal(e._transforms(x, None, torch.ones(B, T, device=dev), 3)[0], ops.augment(x, step_seed(0, 0, 3), **spec))
+    assert plain._transforms.augment is None and plain._transforms(x, None, mask, 3)[0] is x
     # validation() and test() never augment: same weights (same seed), same numbers, no launch
     for (n1, p1), (n2, p2) in zip(e.model.state_dict().items(), plain.model.state_dict().items()):
         assert n1 == n2 and torch.equal(p1, p2)

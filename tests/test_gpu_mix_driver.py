@@ -69,7 +69,7 @@ def runs(tmp_path_factory):
                                      ("again", ("--mix", MIX), False), ("graph", ("--mix", MIX, "--hipgraph"), False)):
                 del calls[:], soft[:]
                 e = _experiment(tag, extra, drop)
-                assert (e._mix_spec is None) == (tag in ("absent", "none"))
+                assert (e._transforms.mix is None) == (tag in ("absent", "none"))
                 out[tag] = _train(e) + (len(calls), len(soft))
                 if tag == "graph":
                     assert getattr(e, "_graphed", None) is not None and e.optimizer.capturable     # the graph path really ran
@@ -127,14 +127,16 @@ def test_with_augment_and_a_ragged_batch_and_evaluation_untouched(tmp_path, monk
     for b, n in enumerate(lens):
         mask[b, :n] = 1
         x[b, n:] = 777.0
-    out, (label_b, lam) = e._mix(x, label, mask, 3)
-    roll, lam_h, span_h = mix_draws(step_seed(0, 0, 3), B, np.asarray(lens), e._mix_spec)
+    import dataclasses
+    only_mix = dataclasses.replace(e._transforms, augment=None)      # the chain's mix stage on its own: same spec, base seed and rank
+    out, (label_b, lam) = only_mix(x, label, mask, 3)
+    roll, lam_h, span_h = mix_draws(step_seed(0, 0, 3), B, np.asarray(lens), e._transforms.mix)
     assert torch.equal(lam.cpu(), torch.from_numpy(lam_h)) and torch.equal(label_b, label[(torch.arange(B, device=dev) + roll) % B])
     want = ops.mix(x, lam, roll, span=torch.from_numpy(span_h).to(dev), lengths=torch.tensor(lens, dtype=torch.int32, device=dev))
     assert torch.equal(out, want)
     for b, n in enumerate(lens):
         assert bool((out[b, n:] == 777.0).all())
-    assert plain._mix_spec is None and plain._mix(x, label, mask, 3) == (x, ())
+    assert plain._transforms.mix is None and plain._transforms(x, label, mask, 3) == (x, ())
     # validation() and test() never mix: same weights (same seed), same numbers, no launch
     for (n1, p1), (n2, p2) in zip(e.model.state_dict().items(), plain.model.state_dict().items()):
         assert n1 == n2 and torch.equal(p1, p2)
@@ -183,7 +185,7 @@ def test_regression_refuses_the_flag():
     e = Experiment.__new__(Experiment)                       # the set-up step itself, for a caller that builds its own namespace
     e.args, e.rank = Namespace(mix="mixup=0.4", task_name="regression", seed=0), 0
     with pytest.raises(ValueError, match="regression"):
-        e._resolve_mix()
+        e._resolve_train_transforms()
     e.args = Namespace(mix="none", task_name="regression", seed=0)
-    e._resolve_mix()
-    assert e._mix_spec is None
+    e._resolve_train_transforms()
+    assert e._transforms.mix is None

@@ -247,7 +247,7 @@ def runs(tmp_path_factory):
                                      ("graph", ("--warp", WARP, "--hipgraph"), False)):
                 del calls[:]
                 e = _experiment(tag, extra, drop)
-                assert (e._warp_spec is None) == (tag in ("absent", "none"))
+                assert (e._transforms.warp is None) == (tag in ("absent", "none"))
                 launches = None
                 if tag == "none":
                     _lib.timing_enable(True)
@@ -298,15 +298,16 @@ def test_harness_ragged_batch_regression_and_evaluation_untouched(tmp_path, monk
     for b, n in enumerate(lens):
         mask[b, :n] = 1
         x[b, n:] = SENTINEL
-    out = e._warp(x, mask, 3)
+    out, soft = e._transforms(x, None, mask, 3)                   # --warp alone: the chain is that one stage
+    assert soft == () and (e._transforms.augment, e._transforms.mix) == (None, None)
     for b, n in enumerate(lens):
         assert bool((out[b, n:] == SENTINEL).all())
         assert n < 3 or not torch.equal(out[b, :n], x[b, :n])
-    spec = e._warp_spec._asdict()
+    spec = e._transforms.warp._asdict()
     want = ops.warp(x, step_seed(0, 0, 3), lengths=torch.tensor(lens, dtype=torch.int32, device=dev), **spec)
     assert torch.equal(out, want)
-    assert torch.equal(e._warp(x, torch.ones(B, T, device=dev), 3), ops.warp(x, step_seed(0, 0, 3), **spec))
-    assert plain._warp_spec is None and plain._warp(x, mask, 3) is x
+    assert torch.equal(e._transforms(x, None, torch.ones(B, T, device=dev), 3)[0], ops.warp(x, step_seed(0, 0, 3), **spec))
+    assert plain._transforms.warp is None and plain._transforms(x, None, mask, 3)[0] is x
     # validation() and test() never warp: same weights (same seed), same numbers, no launch
     for (n1, p1), (n2, p2) in zip(e.model.state_dict().items(), plain.model.state_dict().items()):
         assert n1 == n2 and torch.equal(p1, p2)

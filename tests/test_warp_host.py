@@ -445,9 +445,7 @@ def _bare_experiment(monkeypatch, order, graphed, **flags):
         order.append(("forward", (float(batch_x.mean()),), {}))
         raise _Stop
     e._forward = forward
-    e._resolve_warp()
-    e._resolve_augment()
-    e._resolve_mix()
+    e._resolve_train_transforms()
     return e
 
 
@@ -455,7 +453,7 @@ def _bare_experiment(monkeypatch, order, graphed, **flags):
 def test_training_loops_warp_then_augment_then_mix_with_the_step_seed(monkeypatch, graphed):
     order = []
     e = _bare_experiment(monkeypatch, order, graphed, warp="twarp=0.2,mwarp=0.1,knots=3,prob=0.5", augment="shift=0.1", mix="mixup=0.4")
-    assert e._warp_spec == W.WarpSpec(twarp=0.2, mwarp=0.1, knots=3, prob=0.5) and e._warp_base == 11
+    assert e._transforms.warp == W.WarpSpec(twarp=0.2, mwarp=0.1, knots=3, prob=0.5) and e._transforms.base == 11
     with pytest.raises(_Stop):
         e.train_one_epoch(0, 40)
     assert [o[0] for o in order] == ["warp", "augment", "mix", "forward"]
@@ -474,9 +472,10 @@ def test_training_loops_warp_then_augment_then_mix_with_the_step_seed(monkeypatc
 def test_no_call_when_the_flag_is_off(monkeypatch, graphed, flags):
     order = []
     e = _bare_experiment(monkeypatch, order, graphed, **flags)
-    assert e._warp_spec is None and not hasattr(e, "_warp_base")
+    assert e._transforms.warp is None and e._transforms.base is None and not e._transforms
     x = torch.zeros(2, 3, 1)
-    assert e._warp(x, None, 1) is x                                    # nothing is touched: no mask sum, no seed arithmetic
+    out, soft = e._transforms(x, None, None, 1)                        # nothing is touched: no mask sum, no seed arithmetic
+    assert out is x and soft == ()
     with pytest.raises(_Stop):
         e.train_one_epoch(0, 0)
     assert [o[0] for o in order] == ["forward"] and order[0][1] == (0.0,)
@@ -487,7 +486,7 @@ def test_none_is_not_parsed_beyond_the_word(monkeypatch):
         raise AssertionError("--warp none must not reach the parser")
     monkeypatch.setattr(W, "parse_warp", refuse)
     e = _bare_experiment(monkeypatch, [], False, warp="none")
-    assert e._warp_spec is None
+    assert e._transforms.warp is None
     with pytest.raises(AssertionError):
         _bare_experiment(monkeypatch, [], False, warp="twarp=0.2")
     monkeypatch.undo()
@@ -496,22 +495,26 @@ def test_none_is_not_parsed_beyond_the_word(monkeypatch):
 
 
 def test_only_the_training_loops_warp():
-    """_warp is called from the two training loops and nowhere else: validation, test, saliency, the k-means initialisation, the
-    projection, the alignment fit and the artifact report have no call"""
-    calls = {}
+    """the chain is called from the two training loops and nowhere else, and the three ops from the chain alone: validation, test,
+    saliency, the k-means initialisation, the projection, the alignment fit and the artifact report have no call"""
+    chain, ops = {}, {}
     base = os.path.join(ROOT, "speech-imagery-eeg_amd")
     for folder, _, files in os.walk(base):
         for f in files:
             if f.endswith(".py"):
                 text = open(os.path.join(folder, f)).read()
-                n = len(re.findall(r"\._warp\(|ops\.warp\(", text))
-                if n:
-                    calls[os.path.relpath(os.path.join(folder, f), base)] = n
-    assert calls == {os.path.join("exp", "experiment_classification.py"): 3}             # two loops, and _warp's own call of the op
+                rel = os.path.relpath(os.path.join(folder, f), base)
+                for found, pattern in ((chain, r"\._transforms\("), (ops, r"ops\.(?:warp|augment|mix)\(")):
+                    n = len(re.findall(pattern, text))
+                    if n:
+                        found[rel] = n
+    assert chain == {os.path.join("exp", "experiment_classification.py"): 2}             # the two loops
+    assert ops == {os.path.join("utils", "train_transforms.py"): 3}                      # one call of each op
     import inspect
     from exp import experiment_classification as E
+    from utils import train_transforms as TT
     for fn in (E.Experiment.train_one_epoch, E.Experiment._train_one_epoch_graphed):
-        src = inspect.getsource(fn)
-        assert src.index("self._warp(") < src.index("self._augment(") < src.index("self._mix(")
+        assert inspect.getsource(fn).count("self._transforms(") == 1
+    assert TT.ORDER == ("warp", "augment", "mix")                     # the order is the chain's, as data
     for fn in (E.Experiment.validation, E.Experiment.test):
-        assert "_warp" not in inspect.getsource(fn)
+        assert "_transforms" not in inspect.getsource(fn) and "_warp" not in inspect.getsource(fn)
